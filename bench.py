@@ -12,9 +12,17 @@ arithmetic) is timed in the same run and printed beside it as `exact_fp32`.  One
 driver launches this file through torch.distributed.run and the ranks exchange gradients over
 RCCL/xGMI (weak scaling: B per GPU fixed).
 
-Prints ONE JSON line on rank 0 with `roofline` (dominant kernel family of one extra, untimed step
-with HIP events around every launch) and `cpu_baseline` (the CPU
-oracle of the same step timed on the host cores, bounded sample).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the
+headline (`value`, `ms_per_step`, ...); everything else it can measure runs only with `--full`:
+`roofline` (dominant kernel family of one extra, untimed step with HIP events around every launch),
+`exact_fp32`, `frozen_weights`, `fast_mode` (the step in the other arithmetics / with frozen weights)
+and `cpu_baseline` (the CPU oracle of the same step timed on the host cores, bounded sample); these
+fields are null in a plain run, and --no-roofline / --no-fast-mode / --no-cpu-baseline drop single
+parts of a --full run.
+
+--dump-outputs DIR writes what the last timed step computed (the losses and a fixed, seeded sample of
+the gradients, or the inferred audio) as DIR/<name>.npy, so that two builds can be compared output for
+output: with the same arguments the inputs are the same from run to run.
 """
 from __future__ import annotations
 
@@ -81,6 +89,13 @@ def parse():
     ap.add_argument("--optimizer", action="store_true",
                     help="also run the fused ScaledAdam + Eden2 step inside the timed region "
                          "(a complete train step; the BASELINE metric itself is fwd/bwd)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure the roofline pass, the other arithmetics, the "
+                         "frozen-weights step and the CPU baseline (a plain run times the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32): the losses "
+                         "and a fixed, seeded sample of every gradient (and, with --optimizer, of every "
+                         "parameter), or the inferred audio")
     return ap.parse_args()
 
 
@@ -174,6 +189,7 @@ def main():
     # Fourier branch's / period discriminator's bucket starts its all-reduce when its launch lane has
     # finished its backward, the rest from autograd hooks while backward is still running
     COMM = [0, 0]       # bytes handed to the all-reduce, steps
+    LAST = {}           # what the latest step returned to its caller (detached: no graph kept alive)
 
     def step():
         COMM[1] += 1
@@ -182,6 +198,7 @@ def main():
             reducer.prepare(d_params, groups=d_groups)
             cond = logmel(audio_d)
             mp, mr = gan(cond, audio_d, lens, nts, True)
+            LAST["d_losses"] = (mp.detach(), mr.detach())
             (D_WEIGHTS[0] * mp + D_WEIGHTS[1] * mr).backward()
             COMM[0] += reducer.finish()
             optimize(opt_d, sch_d, d_params)
@@ -189,6 +206,7 @@ def main():
             reducer.prepare(g_params, groups=g_groups)
             cond = logmel(audio_g)
             ls = gan(cond, audio_g, lens, nts, False)
+            LAST["g_losses"] = tuple(l.detach() for l in ls)
             sum(w * l for w, l in zip(G_WEIGHTS, ls)).backward()
             COMM[0] += reducer.finish()
             optimize(opt_g, sch_g, g_params)
@@ -197,7 +215,9 @@ def main():
             gen.train()
             reducer.prepare(g_params, groups=g_groups)
             cond = logmel(audio_g)
-            gen(cond, audio_g, lens).backward()
+            loss = gen(cond, audio_g, lens)
+            LAST["loss"] = (loss.detach(),)
+            loss.backward()
             COMM[0] += reducer.finish()
             optimize(opt_g, sch_g, g_params)
             return B * (T / sr)
@@ -210,6 +230,7 @@ def main():
                 # the ~600 launches of a 4-step inference replayed from one captured HIP graph per
                 # GEMM mode (launch lanes = parallel graph branches): the host no longer bounds it
                 out = infer_runner()(cond)
+        LAST["audio"] = out
         return B * out.shape[1] / sr
 
     _runners = {}
@@ -260,8 +281,24 @@ def main():
     for _ in range(args.warmup):
         step()
     _mark_rebuild()
+    # the timed steps draw their noise / t / branch choices from freshly seeded generators: what they
+    # compute depends on the arguments alone (--dump-outputs), not on what the warm-up drew
+    import random
+    torch.manual_seed(4321)
+    random.seed(4321)
     audio_s, elapsed = timed(0, args.steps)
     value = world * audio_s / elapsed
+    if args.dump_outputs and rank == 0:
+        outs = {k: torch.cat([t.reshape(-1) for t in v]) for k, v in LAST.items() if k != "audio"}
+        if "audio" in LAST:
+            outs["audio"] = LAST["audio"]
+        if args.workload != "infer4":
+            subs = [("g", g_params)] + ([("d", d_params)] if args.workload == "gan_stage2" else [])
+            for tag, ps in subs:
+                outs[tag + "_grad_sample"] = sample_of([p.grad for p in ps])
+                if args.optimizer:
+                    outs[tag + "_param_sample"] = sample_of(ps)
+        dump_outputs(args.dump_outputs, outs)
     comm = None
     if world > 1 or force_dist:
         # what makes the N > 1 line checkable on its own: the ranks that took part (counted by an
@@ -390,7 +427,7 @@ def main():
                               for k, v in sorted(hbm.items())}}
 
     roofline = None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         roofline = roofline_of(args.gemm)
         iso = os.path.join(ROOT, "profiles", "hbm_class_isolated.json")
         if os.path.exists(iso):
@@ -405,7 +442,8 @@ def main():
     exact = None
     fast = None
     frozen = None
-    if not args.frozen_weights and not args.optimizer and args.workload != "infer4" and not args.no_fast_mode:
+    if (args.full and not args.frozen_weights and not args.optimizer and args.workload != "infer4"
+            and not args.no_fast_mode):
         # the same step with the weights frozen (derived weight images free after warm-up): what rounds 1-5
         # reported as `value`; a side field now
         FROZEN[0] = True
@@ -413,7 +451,7 @@ def main():
         FROZEN[0] = False
         frozen = {"value": round(world * af / ef, 2), "unit": "audio-s/s", "ms_per_step": round(1e3 * ef / half, 2),
                   "note": "weights never change, derived weight images cached across steps (--frozen-weights)"}
-    if not args.no_fast_mode and args.gemm == "bf16x6":
+    if args.full and not args.no_fast_mode and args.gemm == "bf16x6":
         # the reference's own arithmetic (exact fp32 MFMA, v_mfma_f32_32x32x2_f32: bit-for-bit a k-ordered
         # fmaf chain) measured in the same run, with its own per-launch roofline pass
         ops.set_gemm_precision("fp32")
@@ -427,7 +465,7 @@ def main():
                                                     "traffic", "algorithmic_bytes_per_launch",
                                                     "launches_per_step", "avg_launch_us", "mfma_class")}
         ops.set_gemm_precision(args.gemm)
-    if not args.no_fast_mode and args.gemm in ("fp32", "bf16x6"):
+    if args.full and not args.no_fast_mode and args.gemm in ("fp32", "bf16x6"):
         # also report the split-bf16 GEMM mode (3 bf16 MFMAs per product, fp32 accumulate): same
         # <= 1e-4 RMS waveform parity (tests/test_hip_generator.py passes in both modes), not fp32-exact
         ops.set_gemm_precision("bf16x3")
@@ -477,7 +515,7 @@ def main():
         ops.set_gemm_precision(args.gemm)
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:  # N = 1 only: ranks must not wait on it
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:  # N = 1 only: ranks must not wait on it
         # separate process (fresh OpenMP pool, no GPU context) under a hard time limit, so that the
         # reported baseline can never stall the benchmark
         import subprocess
@@ -547,6 +585,49 @@ def main():
         print(json.dumps(line), flush=True)
     if world > 1 or force_dist:
         fdist.cleanup_dist()
+
+
+DUMP_LIMIT = 64 << 20         # bytes of all --dump-outputs files together
+SAMPLE_PER_TENSOR = 4096      # elements of one gradient / parameter tensor in its sample
+SAMPLE_PER_ARRAY = 4 << 20    # elements of any other output above which it is sampled too
+
+
+def _seeded_positions(numel: int, n: int, seed: int):
+    """n fixed positions in [0, numel), drawn from a CPU generator seeded with `seed`, sorted."""
+    g = torch.Generator().manual_seed(seed)
+    return torch.randint(0, numel, (n,), generator=g).sort().values
+
+
+def sample_of(tensors) -> torch.Tensor:
+    """Fixed, seeded sample of a list of tensors, flattened and concatenated in list order: every element
+    of a tensor with at most SAMPLE_PER_TENSOR of them, else SAMPLE_PER_TENSOR elements at positions seeded
+    by the tensor's index in the list (None entries -- no gradient -- contribute nothing)."""
+    parts = []
+    for i, t in enumerate(tensors):
+        if t is None:
+            continue
+        flat = t.detach().reshape(-1)
+        if flat.numel() > SAMPLE_PER_TENSOR:
+            flat = flat[_seeded_positions(flat.numel(), SAMPLE_PER_TENSOR, i).to(flat.device)]
+        parts.append(flat)
+    return torch.cat(parts) if parts else torch.empty(0)
+
+
+def dump_outputs(outdir: str, outs: dict) -> None:
+    """outs: name -> tensor, written as outdir/<name>.npy in float32 (float64 stays float64); an output of
+    more than SAMPLE_PER_ARRAY elements is replaced by a fixed, seeded sample of that many, flattened."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {}
+    for name, t in outs.items():
+        t = t.detach()
+        if t.numel() > SAMPLE_PER_ARRAY:
+            t = t.reshape(-1)[_seeded_positions(t.numel(), SAMPLE_PER_ARRAY, 0).to(t.device)]
+        arrays[name] = t.to(torch.float64 if t.dtype == torch.float64 else torch.float32).cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT, f"--dump-outputs: {total} bytes > {DUMP_LIMIT}"
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def _lib_version() -> str:

@@ -368,9 +368,9 @@ def _small_net(seed):
     return torch.nn.Sequential(torch.nn.Linear(6, 5), torch.nn.Tanh(), torch.nn.Linear(5, 2))
 
 
-def test_checkpoint_roundtrip_and_model_averaging(tmp_path):
+def test_checkpoint_roundtrip_and_model_averaging(tmp_path, golden):
     """reference file layout, DDP prefix, running average, range average, plain
-    average of files; cross-checked against the reference's own functions where it is present."""
+    average of files; cross-checked against the reference's own functions' recorded outputs."""
     import copy
     from flow2gan_amd import checkpoint as ck
 
@@ -416,18 +416,13 @@ def test_checkpoint_roundtrip_and_model_averaging(tmp_path):
     rest = ck.load_checkpoint(tmp_path / "ddp.pt", m2, model_avg=avg2)
     assert rest["batch_idx_train"] == 4 and "model" not in rest and "model_avg" not in rest
     assert all(torch.equal(v, a[k]) for k, v in m2.state_dict().items())
-    # the reference's own implementation, when the build container has it
-    import sys
-    sys.path.insert(0, os.path.join(ROOT, "oracle"))
-    import ref_shims
-    if ref_shims.reference_available():
-        ref_shims.install()
-        from flow2gan import checkpoint as rck
-        ref = rck.average_checkpoints_with_averaged_model(str(files[0]), str(files[1]))
-        for k, v in rng.items():
-            assert torch.equal(v, ref[k]), k
-        ref_plain = rck.average_checkpoints([str(f) for f in files])
-        assert all(torch.equal(plain[k], ref_plain[k]) for k in plain)
+    # what the reference's own functions return for these two files (oracle/make_golden_checkpoint.py)
+    ref = golden("checkpoint_avg")
+    assert sorted(rng) == sorted(k[len("range/"):] for k in ref if k.startswith("range/"))
+    for k, v in rng.items():
+        assert torch.equal(v, torch.from_numpy(ref["range/" + k])), k
+    assert sorted(plain) == sorted(k[len("plain/"):] for k in ref if k.startswith("plain/"))
+    assert all(torch.equal(plain[k], torch.from_numpy(ref["plain/" + k])) for k in plain)
 
 
 def test_weight_gradient_split_rule():

@@ -8,16 +8,16 @@ rm -rf $O; mkdir -p $O
 cd $R
 python tools/hbm_kernel_bench.py $O/hbm_class_isolated.json > $O/hbm_kernels.txt 2>/dev/null
 cp $O/hbm_class_isolated.json profiles/hbm_class_isolated.json      # (so that the default line below carries it)
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-F2G_GEMM_REPORT=90 python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-fast-mode 2> $O/shapes_x6.txt > /dev/null
-F2G_GEMM_REPORT=90 python bench.py --gemm fp32 --steps 3 --warmup 2 --no-cpu-baseline --no-fast-mode 2> $O/shapes_fp32.txt > /dev/null
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+F2G_GEMM_REPORT=90 python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-fast-mode 2> $O/shapes_x6.txt > /dev/null
+F2G_GEMM_REPORT=90 python bench.py --full --gemm fp32 --steps 3 --warmup 2 --no-cpu-baseline --no-fast-mode 2> $O/shapes_fp32.txt > /dev/null
 for w in stage1 infer4; do
-  python bench.py --workload $w --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_$w.json
+  python bench.py --full --workload $w --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_$w.json
 done
-python bench.py --model mel_44k_128band_512x_base --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_44k.json
-python bench.py --n-timesteps 4 --steps 4 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_n4.json
+python bench.py --full --model mel_44k_128band_512x_base --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_44k.json
+python bench.py --full --n-timesteps 4 --steps 4 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_n4.json
 python bench.py --optimizer --steps 8 --warmup 3 --no-cpu-baseline --no-roofline --no-fast-mode 2>/dev/null | tail -1 > $O/bench_opt.json
-python bench.py --workload infer4 --steps 10 --warmup 3 --no-cpu-baseline --no-fast-mode --gemm bf16 2>/dev/null | tail -1 > $O/bench_infer4_bf16.json
+python bench.py --full --workload infer4 --steps 10 --warmup 3 --no-cpu-baseline --no-fast-mode --gemm bf16 2>/dev/null | tail -1 > $O/bench_infer4_bf16.json
 ( for m in bf16x6 fp32; do for k in "" mrd mpd mel "mpd,mrd" "mpd,mrd,mel"; do MODE=$m KO=$k python tools/knockout.py 2>&1 | tail -1; done; done ) > $O/knockout.txt
 ( for m in fp32 bf16x6; do echo "## MODE=$m"; MODE=$m python tools/conv32_probe.py 2>&1 | grep -v amdgpu.ids; done ) > $O/conv32_probe.txt
 cd /tmp && export TMPDIR=/tmp

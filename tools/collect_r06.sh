@@ -22,21 +22,21 @@ cd $R
 G=gpurun_out/r06 MODE=bf16x6 python3 tools/pmc_traffic_json.py $O/pmc_x6_traffic.json
 G=gpurun_out/r06 MODE=fp32 python3 tools/pmc_traffic_json.py $O/pmc_gemm_traffic.json
 cp $O/pmc_x6_traffic.json profiles/r06_pmc_x6_traffic.json; cp $O/pmc_gemm_traffic.json profiles/r06_pmc_gemm_traffic.json
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-F2G_GEMM_REPORT=90 python bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-fast-mode 2> $O/shapes_x6.txt > /dev/null
-F2G_GEMM_REPORT=90 python bench.py --gemm fp32 --steps 3 --warmup 2 --no-cpu-baseline --no-fast-mode 2> $O/shapes_fp32.txt > /dev/null
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+F2G_GEMM_REPORT=90 python bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-fast-mode 2> $O/shapes_x6.txt > /dev/null
+F2G_GEMM_REPORT=90 python bench.py --full --gemm fp32 --steps 3 --warmup 2 --no-cpu-baseline --no-fast-mode 2> $O/shapes_fp32.txt > /dev/null
 for w in stage1 infer4; do
-  python bench.py --workload $w --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_$w.json
+  python bench.py --full --workload $w --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_$w.json
 done
-python bench.py --model mel_44k_128band_512x_base --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_44k.json
-python bench.py --n-timesteps 4 --steps 4 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_n4.json
+python bench.py --full --model mel_44k_128band_512x_base --steps 6 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_44k.json
+python bench.py --full --n-timesteps 4 --steps 4 --warmup 2 --no-cpu-baseline 2>/dev/null | tail -1 > $O/bench_n4.json
 python bench.py --optimizer --steps 8 --warmup 3 --no-cpu-baseline --no-roofline --no-fast-mode 2>/dev/null | tail -1 > $O/bench_opt.json
 python bench.py --frozen-weights --steps 8 --warmup 3 --no-cpu-baseline --no-roofline --no-fast-mode 2>/dev/null | tail -1 > $O/bench_frozen.json
 python bench.py --workload stage1 --frozen-weights --steps 10 --warmup 3 --no-cpu-baseline --no-roofline --no-fast-mode 2>/dev/null | tail -1 > $O/bench_stage1_frozen.json
-F2G_GEMM_REPORT=40 F2G_GEMM_REPORT_EPI=1 python bench.py --workload stage1 --steps 4 --warmup 2 --no-cpu-baseline --no-fast-mode 2> $O/shapes_stage1_epi.txt > /dev/null
+F2G_GEMM_REPORT=40 F2G_GEMM_REPORT_EPI=1 python bench.py --full --workload stage1 --steps 4 --warmup 2 --no-cpu-baseline --no-fast-mode 2> $O/shapes_stage1_epi.txt > /dev/null
 bash tools/dbg/copybuffer_context.sh > /dev/null 2>&1; cp gpurun_out/copybuffer_context.txt $O/steady_state_kernels.txt
 ./tools/micro/x6_stream_peak > $O/x6_stream_peak.txt 2>&1
-python bench.py --workload infer4 --steps 10 --warmup 3 --no-cpu-baseline --no-fast-mode --gemm bf16 2>/dev/null | tail -1 > $O/bench_infer4_bf16.json
+python bench.py --full --workload infer4 --steps 10 --warmup 3 --no-cpu-baseline --no-fast-mode --gemm bf16 2>/dev/null | tail -1 > $O/bench_infer4_bf16.json
 ( for m in bf16x6 fp32; do for k in "" mrd mpd mel "mpd,mrd" "mpd,mrd,mel"; do MODE=$m KO=$k python tools/knockout.py 2>&1 | tail -1; done; done ) > $O/knockout.txt
 ( for m in fp32 bf16x6; do echo "## MODE=$m"; MODE=$m python tools/conv32_probe.py 2>&1 | grep -v amdgpu.ids; done ) > $O/conv32_probe.txt
 cd /tmp && export TMPDIR=/tmp
