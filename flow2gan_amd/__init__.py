@@ -9,11 +9,13 @@ from __future__ import annotations
 
 from typing import Optional, Tuple
 
-from . import _lib  # noqa: F401  (fails loudly when the HIP library is not built)
+from . import _lib, _opts  # (_lib fails loudly when the HIP library is not built)
 from .checkpoint import load_checkpoint
 from .models.config import HF_MODEL_NAMES, HF_REPO, AttributeDict, get_generator_config
 from .models.generator import MelAudioGenerator
 from .models.modules import LogMelSpectrogram
+
+_opts.warn_unknown(_lib.has_option)   # (every module that declares a tunable is imported by now)
 
 __all__ = ["get_model", "MelAudioGenerator", "LogMelSpectrogram", "load_checkpoint"]
 

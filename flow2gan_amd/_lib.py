@@ -308,6 +308,10 @@ def get_option(name: str) -> int:
     return v.value
 
 
+def has_option(name: str) -> bool:
+    return lib.f2g_get_option(name.encode(), C.byref(C.c_int32())) == 0
+
+
 def stream_ptr() -> int:
     return torch.cuda.current_stream().cuda_stream
 

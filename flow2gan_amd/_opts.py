@@ -1,8 +1,13 @@
 """Tunables of the host side, in ONE place: module constants with built-in defaults that
 `F2G_OPTS="name=value,..."` may override at import (the same variable carries the library's own dispatch
-options, csrc/common.h: names neither side knows are ignored by that side).  Tests and tools change a
+options, csrc/common.h; names match in any letter case).  A name that neither side knows -- a retired or
+misspelt switch -- draws one warning when the package is imported (warn_unknown).  Tests and tools change a
 tunable by assigning the module attribute (`ops.X6F_MIN_K = 32`) or, for the library's,
 `flow2gan_amd._lib.set_option("x6p", 2)`.
+
+Only switches that something still needs are tunables: a test that flips them or takes one path as its
+reference, bench.py, a debug cross-check, a cap, or a threshold that tests lower to reach a kernel on small
+shapes.  The comment at each declaration says which.
 
 Environment switches that remain on their own (user-facing, or needed before anything is imported):
 F2G_GEMM (arithmetic of the GEMMs), F2G_STREAMS (launch lanes), F2G_DETERMINISTIC (no splits on the library's
@@ -10,6 +15,7 @@ own initiative), F2G_WEIGHT_CACHE, F2G_LIB_PATH, F2G_DRYRUN, F2G_DIST_TIMEOUT_S.
 from __future__ import annotations
 
 import os
+import warnings
 
 
 def _parse(text: str) -> dict:
@@ -22,13 +28,24 @@ def _parse(text: str) -> dict:
 
 
 _OPTS = _parse(os.environ.get("F2G_OPTS", ""))
+_ASKED: set = set()     # every name opt() was asked for
 
 
 def opt(name: str, default):
     """Value of tunable `name` (lower case): F2G_OPTS's, else `default`; typed like the default."""
+    _ASKED.add(name)
     v = _OPTS.get(name)
     if v is None:
         return default
     if isinstance(default, bool):
         return v not in ("0", "false", "off", "")
     return type(default)(v)
+
+
+def warn_unknown(lib_knows) -> list:
+    """Warn once about the F2G_OPTS names that no tunable declared so far asked for and that `lib_knows(name)`
+    denies (the library's options); returns them."""
+    unknown = sorted(n for n in _OPTS if n not in _ASKED and not lib_knows(n))
+    if unknown:
+        warnings.warn("F2G_OPTS: unknown option name(s) ignored: " + ", ".join(unknown), stacklevel=2)
+    return unknown

@@ -2,6 +2,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <strings.h>
 
 #include <mutex>
 
@@ -31,15 +32,15 @@ extern "C" const char* f2g_last_error(void) { return g_err; }
 // ---- options -----------------------------------------------------------------------------------------------
 namespace {
 struct Opt { const char* name; int value; };
-Opt g_opts[F2G_OPT_COUNT] = {
-    {"lean", 1}, {"lean_tall", 1}, {"lean_tap", 1}, {"lean_wgrad", 1}, {"x6_tap", 1}, {"x6_wide", 1}, {"x6p", 1},
-    {"w6t", 1}, {"deterministic", 0}, {"streamk", 1}, {"conv2ch_v2", 1}, {"conv32_v2", 1}, {"conv32_wgrad_v2", 1},
-    {"mlp_rt", 0}, {"mlp_split", 0}, {"multi_rt384", 4}, {"multi_rt512", 3}, {"streamk_min", 4}};
+Opt g_opts[F2G_OPT_COUNT] = {   // (in f2g_opt_id order)
+    {"lean_tall", 1}, {"lean_wgrad", 1}, {"x6p", 1}, {"deterministic", 0}, {"streamk", 1}, {"mlp_rt", 0},
+    {"mlp_split", 0}, {"multi_rt384", 4}, {"multi_rt512", 3}, {"streamk_min", 4}};
 std::once_flag g_opts_once;
 
+// names match without regard to case, as the Python side's F2G_OPTS parser (flow2gan_amd/_opts.py) reads them
 int opt_index(const char* name, size_t len) {
   for (int i = 0; i < F2G_OPT_COUNT; ++i)
-    if (strlen(g_opts[i].name) == len && strncmp(g_opts[i].name, name, len) == 0) return i;
+    if (strlen(g_opts[i].name) == len && strncasecmp(g_opts[i].name, name, len) == 0) return i;
   return -1;
 }
 

@@ -173,77 +173,10 @@ __global__ __launch_bounds__(256) void conv2ch_fwd_p_kernel(const f2g_conv2ch_de
 // fragment (g[px][co]) comes from the gradient tile staged in LDS with 16-byte loads (read as single
 // floats straight from global memory it cost a 4-byte load per lane and MFMA pair: 224 us per launch
 // for a 197 MB map), the B fragment is gathered from the staged patch.  A block walks
-// `tiles_per_block` tiles and leaves with one atomic per output element.
-__global__ __launch_bounds__(256) void conv2ch_wgrad_kernel(const f2g_conv2ch_desc d, int tiles_h,
-                                                            int tiles_w, int tiles_per_block) {
-  __shared__ float plane[2 * FPH * PW];
-  __shared__ __attribute__((aligned(16))) float gt[FTH * TW * CO];   // gradient tile [row][col][co]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, h = lane >> 5;
-  const int ntiles = d.S * tiles_h * tiles_w;
-  // this lane's two gather columns n = li, li + 32 -> (tap, ci) -> offset inside the patch
-  int boff[2];
-  bool bok[2];
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-    const int n = li + 32 * nt;
-    bok[nt] = n < NTAP * 2;
-    const int t = bok[nt] ? n >> 1 : 0, ci = n & 1;
-    const int dh = t / KW, j = t - dh * KW;
-    boff[nt] = ci * (FPH * PW) + dh * PW + j;
-  }
-  f32x16 acc[2];
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[nt][e] = 0.f;
-  const int t0 = blockIdx.x * tiles_per_block;
-  for (int ti = t0; ti < t0 + tiles_per_block && ti < ntiles; ++ti) {
-    const int s = ti / (tiles_h * tiles_w), rem = ti - s * (tiles_h * tiles_w);
-    const int th = rem / tiles_w, tw = rem - th * tiles_w;
-    const int h0 = th * FTH, w0 = tw * TW;
-    __syncthreads();   // the previous tile's readers are done
-    stage_patch(plane, d, d.x + (long long)s * d.x_seq, h0, w0, FPH, tid, 256);
-    for (int i = tid; i < FTH * TW * (CO / 4); i += 256) {
-      const int c4 = i & 7, px = i >> 3;
-      const int row = px / TW, col = px - row * TW;
-      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-      if (h0 + row < d.H && w0 + col < d.W)
-        v = *reinterpret_cast<const float4*>(d.y + (((long long)s * d.H + h0 + row) * (long long)d.W + w0 + col) * CO + c4 * 4);
-      *reinterpret_cast<float4*>(gt + px * CO + c4 * 4) = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int rr = 0; rr < FTH / 4; ++rr) {
-      const int row = wave + 4 * rr;
-      if (h0 + row >= d.H) break;
-      const float* grow = gt + row * TW * CO + li;
-#pragma unroll
-      for (int st = 0; st < TW / 2; ++st) {
-        const int col = 2 * st + h;                  // k slot h of step st = tile column
-        const float a = grow[col * CO];
-        const float b0 = bok[0] ? plane[boff[0] + row * PW + col] : 0.f;
-        const float b1 = bok[1] ? plane[boff[1] + row * PW + col] : 0.f;
-        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b0, acc[0], 0, 0, 0);
-        acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b1, acc[1], 0, 0, 0);
-      }
-    }
-  }
-#pragma unroll
-  for (int nt = 0; nt < 2; ++nt) {
-    const int n = li + 32 * nt;
-    if (n >= NTAP * 2) continue;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int co = (e & 3) + 8 * (e >> 2) + 4 * h;
-      atomicAdd(d.gw + co * (NTAP * 2) + n, acc[nt][e]);
-    }
-  }
-}
-
-// The same with the NEXT tile's gradient rows (8 x 16 bytes per thread) and patch requested before the
-// current tile's 64 MFMAs per wave and written to LDS after them (round 4: conv2ch_wgrad_kernel's blocks
-// wait a full memory round trip per tile; PMC: matrix pipe 21 % busy, 1.2 TB/s on the gradient map).
+// `tiles_per_block` tiles and leaves with one atomic per output element.  The NEXT tile's gradient rows
+// (8 x 16 bytes per thread) and patch are requested before the current tile's 64 MFMAs per wave and written
+// to LDS after them (round 4: blocks that waited a full memory round trip per tile kept the matrix pipe 21 %
+// busy, 1.2 TB/s on the gradient map).
 __global__ __launch_bounds__(256) void conv2ch_wgrad_p_kernel(const f2g_conv2ch_desc d, int tiles_h,
                                                               int tiles_w, int tiles_per_block) {
   __shared__ float plane[2 * FPH * PW];
@@ -550,8 +483,7 @@ static bool conv2ch_ok(const f2g_conv2ch_desc* d) {
 extern "C" int f2g_conv2ch_fwd(const f2g_conv2ch_desc* d, f2g_stream_t stream) {
   if (!d || !d->x || !d->w || !d->y || (d->x_line & 1) || (d->x_seq & 1)) return F2G_EINVAL;
   if (!conv2ch_ok(d)) return F2G_OK;
-  const bool persistent = f2g_opt(F2G_OPT_CONV2CH_V2) != 0;
-  if (persistent && (long long)((d->W + TW - 1) / TW) * d->S >= 256) {   // column tiles x sequences fill the chip
+  if ((long long)((d->W + TW - 1) / TW) * d->S >= 256) {   // column tiles x sequences fill the chip
     hipLaunchKernelGGL(conv2ch_fwd_p_kernel, dim3((d->W + TW - 1) / TW, d->S), dim3(256), 0, ST, *d);
     return f2g_check_launch();
   }
@@ -568,13 +500,8 @@ extern "C" int f2g_conv2ch_wgrad(const f2g_conv2ch_desc* d, f2g_stream_t stream)
   const int ntiles = d->S * tiles_h * tiles_w;
   int per = (ntiles + 511) / 512;        // <= 512 blocks: 0.9 M atomics on 1728 addresses per launch
   if (per < 1) per = 1;
-  const bool persistent = f2g_opt(F2G_OPT_CONV2CH_V2) != 0;
-  if (persistent)
-    hipLaunchKernelGGL(conv2ch_wgrad_p_kernel, dim3((ntiles + per - 1) / per), dim3(256), 0, ST, *d,
-                       tiles_h, tiles_w, per);
-  else
-    hipLaunchKernelGGL(conv2ch_wgrad_kernel, dim3((ntiles + per - 1) / per), dim3(256), 0, ST, *d,
-                       tiles_h, tiles_w, per);
+  hipLaunchKernelGGL(conv2ch_wgrad_p_kernel, dim3((ntiles + per - 1) / per), dim3(256), 0, ST, *d,
+                     tiles_h, tiles_w, per);
   return f2g_check_launch();
 }
 

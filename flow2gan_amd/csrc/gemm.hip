@@ -1632,9 +1632,8 @@ int launch_lean(const f2g_gemm_desc& d, int M, int N, int K, int split, int upb,
   const bool tall = (pm == 1 || pm == 3) && upb == 0 && zs == 1 && tall_mode > 0 &&
                     (tall_mode > 1 || (tall_tiles >= 400 && K >= 640));
   const int bm = tall ? 256 : 128;
-  // tap-reusing variant for stride-1 conv windows (option lean_tap = 0 turns it off)
-  const bool tap_on = f2g_opt(F2G_OPT_LEAN_TAP) != 0;
-  const bool tap = tall && pm == 1 && tap_on && lean_tap_ok(d.A);
+  // tap-reusing variant for stride-1 conv windows
+  const bool tap = tall && pm == 1 && lean_tap_ok(d.A);
   const size_t smem = tap ? (size_t)(2 * 320 + 2 * 128) * LDR * sizeof(float)
                           : (size_t)(2 * bm + 2 * 128) * LDR * sizeof(float);
   dim3 grid((M + bm - 1) / bm, (N + 127) / 128, zs);
@@ -2363,7 +2362,7 @@ inline bool leanw_ok(const f2g_gemm_desc& d) {
 // hide the short K loops better: 92 vs 83).  option lean_wgrad: 0 off, 1 auto (default), 2 always.  ONE rule for
 // f2g_gemm's dispatch and for the host's query (f2g_gemm_wgrad_lean).
 inline bool leanw_fp32_takes(const f2g_gemm_desc& d, int split) {
-  const int leanw_mode = f2g_opt(F2G_OPT_LEAN) == 0 ? 0 : f2g_opt(F2G_OPT_LEAN_WGRAD);
+  const int leanw_mode = f2g_opt(F2G_OPT_LEAN_WGRAD);
   if (d.form != 2 || d.A.split || d.B.split || split < 1) return false;
   // (its scalar row walk assumes that a slab crosses at most two sequence ends)
   return leanw_mode > 0 && d.precision == 0 && d.E.atomic && leanw_ok(d) &&
@@ -3177,8 +3176,7 @@ static bool x6_shape_ok(const f2g_gemm_desc& d) {
 // stride-1 conv windows of TAPS positions x C channels over a halo map image (gemm_x6t_kernel)
 static bool x6_tap_ok(const f2g_gemm_desc& d, int taps) {
   const f2g_operand& A = d.A;
-  const bool on = f2g_opt(F2G_OPT_X6_TAP) != 0;
-  if (!on || host_plain(A) || A.P1 != 1 || A.step0 != 1 || A.unit < 32 || (A.unit % 32)) return false;
+  if (host_plain(A) || A.P1 != 1 || A.step0 != 1 || A.unit < 32 || (A.unit % 32)) return false;
   if (A.cols != taps * A.unit || A.seglen < A.cols || (A.seq_stride % A.unit) || (A.pad0 > 0)) return false;
   const int HpIn = (int)(A.seq_stride / A.unit);
   if (A.P0 < 8 || HpIn < A.P0) return false;
@@ -3186,9 +3184,9 @@ static bool x6_tap_ok(const f2g_gemm_desc& d, int taps) {
   return 128 + taps - 1 + (HpIn - A.P0) * (128 / A.P0 + 1) <= 160;
 }
 
-// 1: the launch takes the wide epilogue (x6_epilogue.h; option x6_wide = 0: the generic one + image read-back)
+// 1: the launch takes the wide epilogue (x6_epilogue.h; else the generic one + image read-back)
 static int x6_wide(const f2g_gemm_desc& d) {
-  return f2g_opt(F2G_OPT_X6_WIDE) != 0 && x6e::wide_ok(d.E, d.B.rows) ? 1 : 0;
+  return x6e::wide_ok(d.E, d.B.rows) ? 1 : 0;
 }
 
 static int launch_x6(const f2g_gemm_desc& d, hipStream_t st) {
@@ -3313,8 +3311,6 @@ extern "C" int f2g_split_bf16x3(void* dst, const float* src, int64_t ld, int32_t
 
 extern "C" int f2g_gemm_last_path(void) { return g_last_path; }
 
-// Would f2g_gemm run this form-0 descriptor on the lean kernel (whatever its precision)?  The host
-// asks before it pre-splits the operands of a split-bf16 GEMM.
 // 1 if f2g_gemm would run this form-2 descriptor (exact fp32, E.atomic, split_k as set) on the K-major lean
 // weight-gradient kernel -- two blocks per CU, so the host deals its blocks in rounds of 512 (ops.split_for)
 extern "C" int f2g_gemm_wgrad_lean(const f2g_gemm_desc* dp) {
@@ -3322,14 +3318,15 @@ extern "C" int f2g_gemm_wgrad_lean(const f2g_gemm_desc* dp) {
   return leanw_fp32_takes(*dp, dp->split_k < 1 ? 1 : dp->split_k) ? 1 : 0;
 }
 
+// Would f2g_gemm run this form-0 descriptor on the lean kernel (whatever its precision)?  The host
+// asks before it pre-splits the operands of a split-bf16 GEMM.
 extern "C" int f2g_gemm_lean_ok(const f2g_gemm_desc* dp) {
   if (!dp || !dp->A.base || !dp->B.base) return 0;
-  const bool lean_on = f2g_opt(F2G_OPT_LEAN) != 0;
   const f2g_gemm_desc& d = *dp;
-  if (d.form == 2) return lean_on && leanw_ok(d) ? 1 : 0;   // split-bf16 weight-gradient kernel
+  if (d.form == 2) return leanw_ok(d) ? 1 : 0;   // split-bf16 weight-gradient kernel
   if (d.form != 0) return 0;
   if (d.A.cols != d.B.cols || !host_plain(d.B)) return 0;
-  if (!(lean_on && d.B.rows > 64 && lean_a_ok(d.A) && lean_b_ok(d.B))) return 0;
+  if (!(d.B.rows > 64 && lean_a_ok(d.A) && lean_b_ok(d.B))) return 0;
   return lean_bf16_ok(d.A, d.B) ? 3 : 1;   // bit 1: also as true bf16 tensors (split = 2)
 }
 
@@ -3445,11 +3442,10 @@ extern "C" int f2g_gemm(const f2g_gemm_desc* dp, f2g_stream_t stream) {
     // discriminator and loss -- differ in the last bit from run to run)
     // option deterministic = 1 (F2G_DETERMINISTIC=1): never split on the library's own initiative (bit-reproducible forward)
     const bool no_auto = f2g_opt(F2G_OPT_DETERMINISTIC) != 0;
-    const bool lean_on = f2g_opt(F2G_OPT_LEAN) != 0;
     // pre-split operands (f2g_split_bf16) are understood by the lean kernel's split-bf16 instances only
     const bool presplit = d.A.split != 0 && d.B.split == d.A.split;
     const bool bf16img = d.A.split == 2;
-    const bool lean = !f1 && lean_on && N > 64 && lean_a_ok(d.A) && lean_b_ok(d.B) &&
+    const bool lean = !f1 && N > 64 && lean_a_ok(d.A) && lean_b_ok(d.B) &&
                       (d.precision == 0 || ((d.precision == 1 || d.precision == 2) && presplit)) &&
                       (!bf16img || (d.precision == 2 && lean_bf16_ok(d.A, d.B)));
     if ((d.A.split || d.B.split) && !(lean && d.precision != 0)) return F2G_EINVAL;
@@ -3494,8 +3490,7 @@ extern "C" int f2g_gemm(const f2g_gemm_desc* dp, f2g_stream_t stream) {
     if (split > 1 && !d.E.atomic) return F2G_EINVAL;
     const int M = d.A.cols, N = d.B.cols, K = d.A.rows;
     if (d.A.split || d.B.split) {   // pre-split images: the lean weight-gradient kernel only
-      const bool lean_on = f2g_opt(F2G_OPT_LEAN) != 0;
-      if (!(d.precision == 1 && d.A.split && d.B.split && lean_on && leanw_ok(d))) return F2G_EINVAL;
+      if (!(d.precision == 1 && d.A.split && d.B.split && leanw_ok(d))) return F2G_EINVAL;
       return launch_leanw3(d, M, N, K, split, st);
     }
     if (leanw_fp32_takes(d, split)) return launch_leanw(d, M, N, K, split, st);

@@ -549,7 +549,6 @@ int f2g_launch_x6p(const f2g_gemm_desc& d, int taps, long long a_extent, hipStre
 
 // ---- tap-walking weight gradients: host side
 int f2g_leanw6t_ok(const f2g_gemm_desc& d, int split) {
-  if (f2g_opt(F2G_OPT_W6T) == 0) return 0;
   const f2g_operand& A = d.A;
   const f2g_operand& B = d.B;
   if (d.form != 2 || d.precision != 3 || !d.E.atomic || d.E.P0o > 0 || d.E.bias || d.E.res) return 0;

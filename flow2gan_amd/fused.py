@@ -16,7 +16,6 @@ from typing import List, Optional
 import torch
 
 from . import ops
-from ._opts import opt
 from .models.modules import dft_matrices
 from .ops import gemm, mat, win1d
 
@@ -120,7 +119,7 @@ def block_fwd(bp: _Blk, x, B, F, lens, cproj=None, ldcp=0, Fc=0, up=1, cp_off=0,
     dev = x.device
     rows, Cc, Hh = B * F, bp.C, bp.H
     fmt = ops.operand_formats_ok(Cc, Hh)
-    if fmt == 2 and not keep and ops.FUSED_BLOCK and bp.K == 7 and ops.fused_mlp_applies(Cc, Hh) \
+    if fmt == 2 and not keep and bp.K == 7 and ops.fused_mlp_applies(Cc, Hh) \
             and x.stride(0) % 4 == 0:
         # plain-bf16 inference (BASELINE config 2): the whole block in one launch -- z is computed in
         # the fused kernel's prologue and lives in LDS only, the hidden activation on chip
@@ -370,8 +369,7 @@ class CondPathFn(GradAwareFunction):
         wstack = _stack_rows(wcs, Dc, dev)
         bstack = _stack_vecs(bcs, dev)
         cproj = ops.empty(rows, nblk * Cc, device=dev)
-        if (not keep) and ops.GEMM_PRECISION == 2 and ops.BF16_IMAGES and ops.LEAN_SPLIT \
-                and Dc % 64 == 0 and Hc % 64 == 0:
+        if (not keep) and ops.GEMM_PRECISION == 2 and Dc % 64 == 0 and Hc % 64 == 0:
             # plain-bf16 inference: the two intermediate results leave their GEMMs as the bf16
             # tensors the next GEMM reads (no conversion launches in between)
             a = torch.empty(rows, Hc, device=dev, dtype=torch.bfloat16)
@@ -475,15 +473,12 @@ class _BranchView:
 
 # Spectra carry n_fft + 2 = 514 / 258 / 130 channels: no multiple of a K slab, which sends every
 # GEMM that reduces over them (in_proj, inverse DFT, STFT backward, out_proj data gradient) to the
-# element-wise loaders.  With the lean kernels available the spectrum rows are padded to a multiple
-# of 64 columns that are ZERO BY CONSTRUCTION -- the producing GEMM runs against weights / DFT
-# tables with zero rows appended, so it writes the zeros itself -- and the consumers reduce over the
-# padded width against zero-padded weights: same sums (plus exact zeros), lean kernels.
-SPEC_PAD = opt("spec_pad", True) and ops.L.get_option("lean") != 0
-
-
+# element-wise loaders.  So the spectrum rows are padded to a multiple of 64 columns that are ZERO BY
+# CONSTRUCTION -- the producing GEMM runs against weights / DFT tables with zero rows appended, so it
+# writes the zeros itself -- and the consumers reduce over the padded width against zero-padded
+# weights: same sums (plus exact zeros), lean kernels.
 def _spec_ld(Cin: int) -> int:
-    return (Cin + 63) // 64 * 64 if SPEC_PAD else ops.pad4(Cin)
+    return (Cin + 63) // 64 * 64
 
 
 def _pad_cols(w2d, Kp: int):
@@ -590,30 +585,28 @@ def _branch_pre(bv: _BranchView, meta, x, t, cproj, training, keep, te_pre=None)
     rows = B * F
     Cc, Cin = bv.C, bv.Cin
     Wd, Wi = dft_matrices(N, dev)
-    ldp = _spec_ld(Cin)
-    Kc = ldp if SPEC_PAD else Cin        # reduction width over a spectrum row
+    ldp = _spec_ld(Cin)        # row stride and reduction width of a (zero-padded) spectrum row
     # plain-bf16 inference: a GEMM result whose only reader is the next GEMM leaves its producer as
     # bf16 (the lean kernel's plain-store epilogue) instead of passing through a conversion launch
-    bf16_chain = (not keep) and ops.GEMM_PRECISION == 2 and SPEC_PAD and ops.BF16_IMAGES \
-        and ops.LEAN_SPLIT and Kc % 64 == 0 and N % 64 == 0
+    bf16_chain = (not keep) and ops.GEMM_PRECISION == 2 and N % 64 == 0
     if ops.fft_applies(N):
         # LDS-butterfly FFT; the kernel writes the zero padding of the rows itself, and in the
         # plain-bf16 inference chain the spectrum as the bf16 tensor in_proj's GEMM reads
         packed = torch.empty(rows, ldp, device=dev, dtype=torch.bfloat16) if bf16_chain \
             else ops.empty(rows, ldp, device=dev)
         ops.stft_fft(x, N, hop, F, packed, zero_pad=True)
-        pk = mat(packed, rows, Kc, split=2 if bf16_chain else 0)
+        pk = mat(packed, rows, ldp, split=2 if bf16_chain else 0)
     elif bf16_chain:
         packed = torch.empty(rows, ldp, device=dev, dtype=torch.bfloat16)
-        gemm(ops.stft_frames(x, N, hop, F), mat(_pad_rows(Wd, Kc)), packed, split_k=1, true_n=Cin)
-        pk = mat(packed, rows, Kc, split=2)
+        gemm(ops.stft_frames(x, N, hop, F), mat(_pad_rows(Wd, ldp)), packed, split_k=1, true_n=Cin)
+        pk = mat(packed, rows, ldp, split=2)
     else:
         packed = ops.empty(rows, ldp, device=dev)
-        gemm(ops.stft_frames(x, N, hop, F), mat(_pad_rows(Wd, Kc)), packed, split_k=1, true_n=Cin)   # bit-reproducible
-        pk = mat(packed, rows, Kc)
+        gemm(ops.stft_frames(x, N, hop, F), mat(_pad_rows(Wd, ldp)), packed, split_k=1, true_n=Cin)   # bit-reproducible
+        pk = mat(packed, rows, ldp)
     h0 = ops.empty(rows, Cc, device=dev)
     # (never split, as before the padding: the forward stays bit-reproducible from run to run)
-    gemm(pk, mat(_pad_cols(bv.w_in.reshape(Cc, Cin), Kc)), h0, bias=bv.b_in, split_k=1, true_k=Cin)
+    gemm(pk, mat(_pad_cols(bv.w_in.reshape(Cc, Cin), ldp)), h0, bias=bv.b_in, split_k=1, true_k=Cin)
     flags = [_limit_draw(training)]
     xcur = ops.empty(rows, Cc, device=dev)
     ops.biasnorm_fwd(h0, xcur, rows, Cc, bv.beta_in, bv.ls_in.reshape(1))
@@ -624,7 +617,7 @@ def _branch_pre(bv: _BranchView, meta, x, t, cproj, training, keep, te_pre=None)
     else:
         emb, th, ts, te, tew, te_all = _time_path(bv, t)
     return dict(packed=packed, h0=h0, xcur=xcur, emb=emb, th=th, ts=ts, te=te, tew=tew, te_all=te_all,
-                flags=flags, F=F, rows=rows, NC=NC, Fce=cproj.shape[0] // B, ldp=ldp, Kc=Kc,
+                flags=flags, F=F, rows=rows, NC=NC, Fce=cproj.shape[0] // B, ldp=ldp,
                 bf16_chain=bf16_chain, blocks=[])
 
 
@@ -635,7 +628,7 @@ def _branch_post(st, bv: _BranchView, meta, x_shape, wbranch_row, wscale, pred, 
     with one launch)."""
     n_fft, hop, up, window = meta
     B, T = x_shape
-    N, F, rows, ldp, Kc = n_fft, st["F"], st["rows"], st["ldp"], st["Kc"]
+    N, F, rows, ldp = n_fft, st["F"], st["rows"], st["ldp"]
     Cc, Cin = bv.C, bv.Cin
     xcur = st["xcur"]
     dev = xcur.device
@@ -643,15 +636,15 @@ def _branch_post(st, bv: _BranchView, meta, x_shape, wbranch_row, wscale, pred, 
     ifft = ops.fft_applies(N)       # inverse transform through the LDS FFT instead of the DFT GEMM
     ybf = st["bf16_chain"] and lens_f is None       # (the inverse FFT reads bf16 spectra as well)
     yspec = torch.empty(rows, ldp, device=dev, dtype=torch.bfloat16) if ybf else ops.empty(rows, ldp, device=dev)
-    gemm(mat(xcur, rows, Cc), mat(_pad_rows(bv.w_out.reshape(Cin, Cc), Kc)), yspec,
-         bias=_pad_vec(bv.b_out, Kc), split_k=1, true_n=Cin)
+    gemm(mat(xcur, rows, Cc), mat(_pad_rows(bv.w_out.reshape(Cin, Cc), ldp)), yspec,
+         bias=_pad_vec(bv.b_out, ldp), split_k=1, true_n=Cin)
     if lens_f is not None:
         ops.mask_rows(yspec, B, F, Cin, lens_f)
     frames = ops.empty(rows, N, device=dev)
     if ifft:
         ops.istft_fft(yspec, N, F, frames)
     else:
-        gemm(mat(yspec, rows, Kc, split=2 if ybf else 0), mat(_pad_cols(Wi, Kc)), frames, split_k=1, true_k=Cin)
+        gemm(mat(yspec, rows, ldp, split=2 if ybf else 0), mat(_pad_cols(Wi, ldp)), frames, split_k=1, true_k=Cin)
     if not ola:
         return frames
     if lanes is not None:
@@ -689,7 +682,7 @@ def _branch_forward(bv: _BranchView, meta, x, t, cproj, wbranch_row, wscale, pre
 def _multi_applies(views, x, keep) -> bool:
     """All branches' ConvNeXt blocks of a layer as ONE launch (ops.fused_block_multi): plain-bf16
     inference, 2-4 branches of equal depth whose shapes the fused block kernel has instances for."""
-    if keep or not (ops.FUSED_MULTI and ops.FUSED_BLOCK):
+    if keep or not ops.FUSED_MULTI:
         return False
     if not (2 <= len(views) <= 4) or len({bv.nblk for bv in views}) != 1:
         return False
@@ -757,7 +750,6 @@ def _branch_backward(bv: _BranchView, meta, sv, x_shape, cproj, g_pred, wbranch_
     NC = bv.nblk * Cc
     Wd, Wi = dft_matrices(N, dev)
     ldp = _spec_ld(Cin)
-    Kc = ldp if SPEC_PAD else Cin
     Fce = cproj.shape[0] // B
     gfr = ops.empty(rows, N, device=dev)
     ops.istft_ola_bwd(g_pred, gfr, B, F, N, hop, T, window, wbranch_row, wscale)
@@ -766,7 +758,7 @@ def _branch_backward(bv: _BranchView, meta, sv, x_shape, cproj, g_pred, wbranch_
         ops.istft_fft_adjoint(gfr, N, F, gy, zero_pad=True)             # (pad columns written as zeros)
     else:
         gy = ops.empty(rows, ldp, device=dev)
-        gemm(mat(gfr, rows, N), mat(_pad_cols(Wi, Kc)), gy, form=1, true_n=Cin)      # pad columns come out zero
+        gemm(mat(gfr, rows, N), mat(_pad_cols(Wi, ldp)), gy, form=1, true_n=Cin)      # pad columns come out zero
     if lens_f is not None:
         ops.mask_rows(gy, B, F, Cin, lens_f)
     # every gradient accumulator of the branch outside its blocks from ONE zeroed allocation (one fill)
@@ -778,7 +770,7 @@ def _branch_backward(bv: _BranchView, meta, sv, x_shape, cproj, g_pred, wbranch_
     x_last = sv["x_last"]
     ops.wgrad(gy, Cin, ldp, mat(x_last, rows, Cc), g_wout)
     g = ops.empty(rows, Cc, device=dev)
-    gemm(mat(gy, rows, Kc), mat(_pad_rows(bv.w_out.reshape(Cin, Cc), Kc)), g, form=1, true_k=Cin)
+    gemm(mat(gy, rows, ldp), mat(_pad_rows(bv.w_out.reshape(Cin, Cc), ldp)), g, form=1, true_k=Cin)
     block_grads = [None] * bv.nblk
     flags = sv["flags"]
     for j in reversed(range(bv.nblk)):
@@ -797,12 +789,12 @@ def _branch_backward(bv: _BranchView, meta, sv, x_shape, cproj, g_pred, wbranch_
     ops.wgrad(gh0, Cc, gh0.stride(0), mat(sv["packed"], rows, Cin), g_win)
     if need_gx:
         gpacked = ops.empty(rows, ldp, device=dev)
-        gemm(mat(gh0, rows, Cc), mat(_pad_cols(bv.w_in.reshape(Cc, Cin), Kc)), gpacked, form=1, true_n=Cin)
+        gemm(mat(gh0, rows, Cc), mat(_pad_cols(bv.w_in.reshape(Cc, Cin), ldp)), gpacked, form=1, true_n=Cin)
         gxf = ops.empty(rows, N, device=dev)
         if ops.fft_applies(N):
             ops.stft_fft_adjoint(gpacked, N, F, gxf)
         else:
-            gemm(mat(gpacked, rows, Kc), mat(_pad_rows(Wd, Kc)), gxf, form=1, true_k=Cin)
+            gemm(mat(gpacked, rows, ldp), mat(_pad_rows(Wd, ldp)), gxf, form=1, true_k=Cin)
         if lanes is not None:
             lanes.chain_enter()  # g_x is accumulated branch after branch
         ops.frames_fold(gxf, g_x, B, F, N, hop, T, accumulate_gx)

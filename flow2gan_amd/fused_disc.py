@@ -18,7 +18,6 @@ from typing import List
 import torch
 
 from . import ops
-from ._opts import opt
 from .fused import filterbank_spec, filterbank_spec_bwd
 from .models.modules import dft_matrices
 from .ops import gemm, mat, win1d, win2d
@@ -122,33 +121,24 @@ def _mpd_forward_one(x2, p: int, prm: list, keep_images: bool = False):
         Hout = (H + 4 - 5) // st + 1
         wp = ops.derived(w, "pack", pack_conv_weight)
         y = _halo_rows(S, Hout, Cout, dev, x3=(0 < l < 4))   # (the next layer's GEMM operand)
-        if l == 0 and ops.MPD0_DIRECT and Cout == 32 and st == 3:
+        if l == 0:
             # 1 -> 32 channels, 5 taps: an HBM stream, not a GEMM (mpd0.hip)
             ops.mpd0_fwd(x, S, H, Hout, HALO, w.reshape(Cout, 5), b, SLOPE, y)
-            acts.append(y)
-            hs.append(Hout)
-            x, H = y, Hout
-            continue
-        if l == 0:   # the folded waveform has no halo (one channel): bounds-tested windows
-            A = win1d(x, S, H, Cin, Hout, st, 2, 5)
-        else:        # window of output row h starts at padded row h*st
-            A = win1d(x, S, H + 2 * HALO, Cin, Hout, st, 0, 5)
-        if keep_images and l > 0:
-            shares[l] = ops.split_sharing(x)
-            with shares[l]:
-                gemm(A, mat(wp), y, bias=b, lrelu=SLOPE, rowmap=_halo_map(Hout, Cout), x3_out=(l < 4))
         else:
-            gemm(A, mat(wp), y, bias=b, lrelu=SLOPE, rowmap=_halo_map(Hout, Cout), x3_out=(0 < l < 4))
+            A = win1d(x, S, H + 2 * HALO, Cin, Hout, st, 0, 5)    # window of output row h starts at padded row h*st
+            if keep_images:
+                shares[l] = ops.split_sharing(x)
+                with shares[l]:
+                    gemm(A, mat(wp), y, bias=b, lrelu=SLOPE, rowmap=_halo_map(Hout, Cout), x3_out=(l < 4))
+            else:
+                gemm(A, mat(wp), y, bias=b, lrelu=SLOPE, rowmap=_halo_map(Hout, Cout), x3_out=(l < 4))
         acts.append(y)
         hs.append(Hout)
         x, H = y, Hout
     wpost, bpost = prm[10], prm[11]
     wpp = ops.derived(wpost, "pack", pack_conv_weight)
     scores = ops.empty(S * H, 1, device=dev)
-    if ops.MPD0_DIRECT and x.shape[1] == 1024:    # 1024 -> 1 channel, 3 taps: an HBM stream (mpd0.hip)
-        ops.mpdpost_fwd(x, S, H, HALO, wpp, bpost, scores)
-    else:
-        gemm(win1d(x, S, H + 2 * HALO, 1024, H, 1, -(HALO - 1), 3), mat(wpp), scores, bias=bpost)
+    ops.mpdpost_fwd(x, S, H, HALO, wpp, bpost, scores)    # 1024 -> 1 channel, 3 taps: an HBM stream (mpd0.hip)
     return dict(acts=acts, hs=hs, scores=scores, S=S, p=p, shares=shares)
 
 
@@ -164,34 +154,26 @@ def _dgrad_weight(w, stride: int, j0: int, nt: int):
     return ops.derived(w, ("dgradT", stride, j0, nt), build)
 
 
-def _conv1d_dgrad(g_pre, S, Hout, Cout, w, stride, pad, Hin, g_off=0, g_halo=True, out_halo=True,
-                  mask=None, fm=None, colsum=None):
-    """g_x from g_pre (S sequences of Hout rows x Cout, starting g_off floats in; halo layout when
-    g_halo).  Returns g_x in the halo layout (S, Hin + 2*HALO, Cin) when out_halo, else (S*Hin, Cin).
-    One forward-form GEMM per stride residue against the cached re-laid weights."""
+def _conv1d_dgrad(g_pre, S, Hout, Cout, w, stride, pad, Hin, mask=None, fm=None, colsum=None):
+    """g_x from g_pre (S sequences of Hout rows x Cout, halo layout).  Returns g_x in the halo layout
+    (S, Hin + 2*HALO, Cin).  One forward-form GEMM per stride residue against the cached re-laid weights."""
     Cin, K = w.shape[1], w.shape[2] * w.shape[3]
     dev = g_pre.device
     # (bf16x6 mode: the gradient map's image for the data gradient of the layer below -- only where that GEMM
     # reads images: its residues reduce over at most two taps x Cin, and below X6_MIN_K the kernel splits the
     # fp32 map itself; the 512-channel map's image was written for nobody: 192 KB per 256 x 128 tile)
     want_img = 2 * Cin >= ops.X6_MIN_K
-    gx = _halo_rows(S, Hin, Cin, dev, x3=want_img) if out_halo else ops.empty(S * Hin, Cin, device=dev)
+    gx = _halo_rows(S, Hin, Cin, dev, x3=want_img)
     for rho, j0, nt, e0, Lq in _residues(K, stride, pad, Hin):
         if Lq == 0:
             continue
         wq = _dgrad_weight(w, stride, j0, nt)
         wpad = (nt - 1) - e0
-        if g_halo:
-            A = win1d(g_pre, S, Hout + 2 * HALO, Cout, Lq, 1, wpad - HALO, nt, offset=g_off)
-        else:
-            A = win1d(g_pre, S, Hout, Cout, Lq, 1, wpad, nt, offset=g_off)
-        if out_halo:
-            rm = (Lq, (Hin + 2 * HALO) * Cin, stride * Cin, (HALO + rho) * Cin)
-        else:
-            rm = (Lq, Hin * Cin, stride * Cin, rho * Cin)
+        A = win1d(g_pre, S, Hout + 2 * HALO, Cout, Lq, 1, wpad - HALO, nt)
+        rm = (Lq, (Hin + 2 * HALO) * Cin, stride * Cin, (HALO + rho) * Cin)
         # mask / fm / colsum: leaky-ReLU backward of the layer whose output gradient this is (every
         # element of gx is written by exactly one stride residue)
-        gemm(A, mat(wq), gx, rowmap=rm, mask=mask, fm=fm, colsum=colsum, x3_out=out_halo and want_img)
+        gemm(A, mat(wq), gx, rowmap=rm, mask=mask, fm=fm, colsum=colsum, x3_out=want_img)
     return gx
 
 
@@ -277,10 +259,7 @@ class MPDLossFn(torch.autograd.Function):
                     zshapes += [(MPD_CH[l + 1], 5 * MPD_CH[l]), (MPD_CH[l + 1],)]
                 zbuf = ops.zeros_many(zshapes, dev)
                 gwp = zbuf[0]
-                if ops.MPD0_DIRECT and y5.shape[1] == 1024:
-                    ops.mpdpost_wgrad(y5, S, H5, HALO, gs, gwp)
-                else:
-                    ops.wgrad(gs, 1, 1, win1d(y5, S, H5 + 2 * HALO, 1024, H5, 1, -(HALO - 1), 3), gwp)
+                ops.mpdpost_wgrad(y5, S, H5, HALO, gs, gwp)
                 unpack = [(10, gwp, wpost.shape)]     # (re-laid at the end of the period: ONE f2g_multi launch)
                 gb = zbuf[1]
                 ops.colsum(gb, gs, S * H5, 1)
@@ -302,12 +281,15 @@ class MPDLossFn(torch.autograd.Function):
 
             def land(gmap, l_out, producer):
                 """Run `producer(mask, fm, colsum)` -> gradient map landing on acts[l_out], with its
-                leaky-ReLU backward fused (FUSE_LRELU & 1) or as a separate pass."""
+                leaky-ReLU backward fused or as a separate pass."""
                 mk, fk, ck = below(l_out)
-                # (bf16x6 mode: where the data gradient runs on the six-product kernel -- the 1024-channel
-                # layers, K >= 2048 -- that kernel has the generic epilogue anyway, and the image it
-                # leaves for the next data gradient must be of the final map)
-                if (FUSE_LRELU & 1) or (ops.GEMM_PRECISION == 3 and l_out in (3, 4)):
+                # (fused only in bf16x6 mode where the data gradient runs on the six-product kernel -- the
+                # 1024-channel layers, K >= 2048 --: that kernel has the generic epilogue anyway, and the
+                # image it leaves for the next data gradient must be of the final map.  Elsewhere the
+                # separate pass won: on the stage-2 step separate passes 257.5 ms, fused into every MPD
+                # epilogue 258.6 -- the HBM-bound pass overlaps with other lanes' MFMA work, while masking in
+                # the epilogue holds an MFMA wave's registers and LDS idle)
+                if ops.GEMM_PRECISION == 3 and l_out in (3, 4):
                     return producer(mk, fk, ck)
                 gm = producer(None, None, None)
                 gm._f2g_x3_bad = True      # (changed in place below: no producer-written image of it)
@@ -322,19 +304,11 @@ class MPDLossFn(torch.autograd.Function):
                     ops.lrelu_bwd(gm, y, None, 0.0, SLOPE, 1, n_, n_, y_off=mk[1])
                 return gm
 
-            def post_dgrad(mk, fk, ck):
-                if ops.MPD0_DIRECT and y5.shape[1] == 1024 and (mk is None or MPDPOST_FUSE):
-                    # (round 5) the stream kernel applies the mask / feature-matching term / bias sums itself and
-                    # leaves the image the fp32-class data gradient of the 1024-channel layer reads next
-                    gy5 = _halo_rows(Sx, H5, 1024, dev, x3=mk is not None)
-                    return ops.mpdpost_dgrad(gs, Sx, H5, HALO, ops.derived(wpost, "pack", pack_conv_weight),
-                                             gy5, g_off=roff * H5, mask=mk, fm=fk, colsum=ck)
-                return _conv1d_dgrad(gs, Sx, H5, 1, wpost, 1, 1, H5, g_off=roff * H5, g_halo=False,
-                                     mask=mk, fm=fk, colsum=ck)
-            if ops.MPD0_DIRECT and y5.shape[1] == 1024 and MPDPOST_FUSE:
-                g = post_dgrad(*below(5))
-            else:
-                g = land(None, 5, post_dgrad)
+            # conv_post's data gradient (round 5): the stream kernel applies the mask / feature-matching term /
+            # bias sums itself and leaves the image the fp32-class data gradient of the 1024-channel layer reads next
+            mk, fk, ck = below(5)
+            g = ops.mpdpost_dgrad(gs, Sx, H5, HALO, ops.derived(wpost, "pack", pack_conv_weight),
+                                  _halo_rows(Sx, H5, 1024, dev, x3=True), g_off=roff * H5, mask=mk, fm=fk, colsum=ck)
             for l in reversed(range(5)):
                 w = prm[2 * l]
                 Cin, Cout, stv = MPD_CH[l], MPD_CH[l + 1], MPD_STRIDE[l]
@@ -349,24 +323,19 @@ class MPDLossFn(torch.autograd.Function):
                         # reduction over ALL rows of the padded gradient map (its halo rows are 0, so
                         # the windows they pair with -- partly outside the input -- contribute nothing)
                         gwp = zbuf[2 + 2 * l]
-                        if l == 0 and ops.MPD0_DIRECT and Cout == 32 and stv == 3:
+                        if l == 0:
                             ops.mpd0_wgrad(acts[0], S, Hin, Hout, HALO, g, gwp)
                         else:
-                            if l == 0:
-                                X = win1d(acts[0], S, Hin, Cin, Hp, stv, 2 + HALO * stv, 5)
-                            else:
-                                X = win1d(acts[l], S, Hin + 2 * HALO, Cin, Hp, stv, HALO * stv, 5,
-                                          unbounded=True)   # g's halo rows are zero
+                            X = win1d(acts[l], S, Hin + 2 * HALO, Cin, Hp, stv, HALO * stv, 5,
+                                      unbounded=True)   # g's halo rows are zero
                             ops.wgrad(g, Cout, Cout, X, gwp)
                         unpack.append((2 * l, gwp, w.shape))
                     if l > 0:
                         g = land(None, l, lambda mk, fk, ck, g=g, w=w, Hout=Hout, Cout=Cout, stv=stv, Hin=Hin:
                                  _conv1d_dgrad(g, Sx, Hout, Cout, w, stv, 2, Hin, mask=mk, fm=fk, colsum=ck))
-                    elif not train_disc and ops.MPD0_DIRECT and Cout == 32 and stv == 3:
+                    elif not train_disc:
                         gx0 = ops.empty(Sx * Hin, 1, device=dev)
                         g = ops.mpd0_dgrad(g, Sx, Hin, Hout, HALO, w.reshape(Cout, 5), gx0)
-                    elif not train_disc:
-                        g = _conv1d_dgrad(g, Sx, Hout, Cout, w, stv, 2, Hin, out_halo=False)
             if not train_disc:
                 # g: (B*p*H0, 1) gradient of the folded image of the generated half
                 lanes.chain_enter()  # g_fake is accumulated period after period
@@ -419,27 +388,6 @@ def mrd_params(mrd) -> list:
 N_MRD_PARAMS = 5 * 5 * 2 + 2
 
 
-import os as _os
-
-# F2G_DIRECT_CONV=0 routes the band layers through the implicit GEMM again (A/B switch)
-DIRECT_CONV32 = opt("direct_conv", True)
-# leaky-ReLU backward fused into the data-gradient epilogue that lands on a map (1) or run as its
-# own pass over the map afterwards (0): bit 0 = MPD, bit 1 = MRD.  Measured on the stage-2 step
-# (B = 64, 10 steps each): separate passes 257.5 ms, MPD fused 258.6, MRD fused 260.6, both 261.2 --
-# the HBM-bound passes overlap with other lanes' MFMA work, while masking in the epilogue (two more
-# loads per element, strided by the row map) holds an MFMA wave's registers and LDS idle.  Default 0.
-FUSE_LRELU = opt("fuse_lrelu", 0)
-# the five frequency bands of a resolution as nested launch lanes (their conv stacks are independent
-# until conv_post; the narrow bands' launches fill a fraction of the chip): 0 = one after the other
-BAND_LANES = opt("band_lanes", False)
-# D-step of the MRD on the direct fp32-class kernels: leaky-ReLU backward mask + bias-gradient sums fused into
-# the data gradients (conv32x6.hip requests a tile's mask before its MFMAs); 0 = the separate passes
-MRD_FUSE_MASK = opt("mrd_fuse_mask", True)
-# conv_post's data gradient (mpd0.hip stream kernel) with the leaky-ReLU backward of the layer below, its bias
-# sums and the result's image fused; 0 = the separate pass over the 1024-channel map
-MPDPOST_FUSE = opt("mpdpost_fuse", True)
-
-
 def _band_edges(n_fft: int):
     nb = n_fft // 2 + 1
     return [(int(lo * nb), int(hi * nb)) for lo, hi in MRD_BANDS]
@@ -477,9 +425,7 @@ def _mrd_forward_one(x2, win: int, prm: list):
     for bi in range(len(bands)):
         foffs.append(foff)
         foff += widths[bi][5]
-    blanes = ops.Lanes(dev, len(bands) if BAND_LANES else 1, "mrd_band%d" % win)
     for bi, (lo, hi) in enumerate(bands):
-      with blanes.lane(bi if BAND_LANES else 0):
         foff = foffs[bi]
         ws = widths[bi]
         layer_out = []
@@ -494,18 +440,18 @@ def _mrd_forward_one(x2, win: int, prm: list):
                           seq_stride=Ft * ldp, offset=lo * 2)
             else:
                 A = win2d(x, S, Ft, Win, Cin, Wout, 3, kw, sw, 1, kw // 2)
-            if l == 0 and DIRECT_CONV32 and ops.GEMM_PRECISION in (0, 1, 3):
+            if l == 0 and ops.GEMM_PRECISION in (0, 1, 3):
                 # 2 -> 32 channels over the band of the spectrogram: direct kernel (conv2ch.hip)
                 y = ops.empty(S * Ft * Wout, MRD_CH, device=dev)
                 ops.conv2ch_fwd(packed, Ft * ldp, ldp, lo * 2, S, Ft, Win, wp, b, SLOPE, y)
-            elif l in (1, 2, 3) and DIRECT_CONV32 and ops.GEMM_PRECISION in (0, 1, 3):
+            elif l in (1, 2, 3) and ops.GEMM_PRECISION in (0, 1, 3):
                 # 32 -> 32 channels, (3, 9) taps, stride (1, 2): direct LDS-tiled kernel (conv32.hip)
                 y = ops.empty(S * Ft * Wout, MRD_CH, device=dev)
                 ops.conv32_s2_fwd(x, S, Ft, Win, Wout, wp, b, SLOPE, y)
             elif l < 4:
                 y = ops.empty(S * Ft * Wout, MRD_CH, device=dev)
                 gemm(A, mat(wp), y, bias=b, lrelu=SLOPE)
-            elif DIRECT_CONV32 and ops.GEMM_PRECISION == 3 and ops.CONV33_X6 and Wout <= ops.CONV33_MAX_W:
+            elif ops.GEMM_PRECISION == 3 and Wout <= ops.CONV33_MAX_W:
                 # 32 -> 32 channels, (3, 3) taps, stride 1, into the band's slice of the concatenated map
                 y = None
                 ops.conv33(x, S, Ft, Wout, wp, b, SLOPE, cat, y_off=foff * MRD_CH, y_line=Wcat * MRD_CH,
@@ -517,11 +463,10 @@ def _mrd_forward_one(x2, win: int, prm: list):
             layer_out.append(y)
             x, x_is_spec = y, False
         acts.append(layer_out)
-    blanes.join()
     wpost, bpost = prm[50], prm[51]
     scores = ops.empty(S * Ft * Wcat, 1, device=dev)
     w9 = ops.derived(wpost, "pack", pack_conv_weight)      # (1, 9*32): [tap][ci]
-    if DIRECT_CONV32 and ops.GEMM_PRECISION in (0, 1, 3):
+    if ops.GEMM_PRECISION in (0, 1, 3):
         ops.convpost_fwd(cat, S, Ft, Wcat, w9, bpost, scores)
     else:
         gemm(win2d(cat, S, Ft, Wcat, MRD_CH, Wcat, 3, 3, 1, 1, 1), mat(w9), scores, bias=bpost)
@@ -537,7 +482,7 @@ def _conv2d_dgrad(g_pre, S, H, Wout, Cout, w, sw, Win, gx, *, g_line=None, g_seq
     Cin, kh, kw = w.shape[1], w.shape[2], w.shape[3]
     dev = g_pre.device
     pw = kw // 2
-    if (DIRECT_CONV32 and ops.GEMM_PRECISION in (0, 1, 3) and Cin == MRD_CH and Cout == MRD_CH and kw == 9
+    if (ops.GEMM_PRECISION in (0, 1, 3) and Cin == MRD_CH and Cout == MRD_CH and kw == 9
             and sw == 2 and x_line is None and x_off == 0):
         # 32 -> 32 channels, (3, 9) taps, stride (1, 2): direct transposed convolution (conv32.hip)
         def build_t(t):
@@ -548,7 +493,7 @@ def _conv2d_dgrad(g_pre, S, H, Wout, Cout, w, sw, Win, gx, *, g_line=None, g_seq
         ops.conv32_s2_dgrad(g_pre, S, H, Win, Wout, wT, gx, g_seq=g_seq, g_line=g_line, g_off=g_off,
                             mask=mask, fm=fm, colsum=colsum)
         return gx
-    if (DIRECT_CONV32 and ops.GEMM_PRECISION == 3 and ops.CONV33_X6 and Cin == MRD_CH and Cout == MRD_CH
+    if (ops.GEMM_PRECISION == 3 and Cin == MRD_CH and Cout == MRD_CH
             and kh == 3 and kw == 3 and sw == 1 and x_line is None and x_off == 0 and fm is None
             and Win <= ops.CONV33_MAX_W):
         # stride 1: the data gradient is the forward kernel over the gradient map with the taps flipped and
@@ -661,7 +606,7 @@ class MRDLossFn(torch.autograd.Function):
             wpost = prm[50]
             if train_disc:
                 gwp = ops.zeros(1, 9 * C, device=dev)
-                if DIRECT_CONV32 and ops.GEMM_PRECISION in (0, 1, 3):
+                if ops.GEMM_PRECISION in (0, 1, 3):
                     ops.convpost_wgrad(cat, S, Ft, Wcat, gs, gwp)
                 else:
                     ops.wgrad(gs, 1, 1, win2d(cat, S, Ft, Wcat, C, Wcat, 3, 3, 1, 1, 1), gwp)
@@ -671,7 +616,7 @@ class MRDLossFn(torch.autograd.Function):
                 grads_w[51] = gb
             # gradient of the concatenated layer-4 maps (only the sequences in backward)
             gcat = ops.empty(Sx * Ft * Wcat, C, device=dev)
-            if DIRECT_CONV32 and ops.GEMM_PRECISION in (0, 1, 3):
+            if ops.GEMM_PRECISION in (0, 1, 3):
                 ops.convpost_dgrad(gs, Sx, Ft, Wcat, ops.derived(wpost, "pack", pack_conv_weight),
                                    gcat, g_off=soff * Ft * Wcat)
             else:
@@ -684,10 +629,7 @@ class MRDLossFn(torch.autograd.Function):
             for bi in range(len(st["bands"])):
                 foffs.append(foff)
                 foff += st["widths"][bi][5]
-            # (the bands' stacks are independent: disjoint slices of gcat / g_packed, their own maps)
-            blanes = ops.Lanes(dev, len(st["bands"]) if BAND_LANES else 1, "mrd_band%d" % win)
             for bi, (lo, hi) in enumerate(st["bands"]):
-              with blanes.lane(bi if BAND_LANES else 0):
                 foff = foffs[bi]
                 ws = st["widths"][bi]
                 # ---- layer 4 (its output is a strided slice of cat / gcat)
@@ -734,11 +676,11 @@ class MRDLossFn(torch.autograd.Function):
                         else:
                             dY = mat(g, S * Ft * Wout, C)
                         tiles = ((3 * kw * Cin + 255) // 256)
-                        if l == 0 and DIRECT_CONV32 and ops.GEMM_PRECISION in (0, 1, 3):
+                        if l == 0 and ops.GEMM_PRECISION in (0, 1, 3):
                             ops.conv2ch_wgrad(packed, Ft * ldp, ldp, lo * 2, S, Ft, Win, g, gwp)
-                        elif l in (1, 2, 3) and DIRECT_CONV32 and ops.GEMM_PRECISION in (0, 1, 3):
+                        elif l in (1, 2, 3) and ops.GEMM_PRECISION in (0, 1, 3):
                             ops.conv32_s2_wgrad(x_in, g, S, Ft, Win, Wout, gwp)
-                        elif (l == 4 and DIRECT_CONV32 and ops.GEMM_PRECISION == 3 and ops.CONV33_X6
+                        elif (l == 4 and ops.GEMM_PRECISION == 3
                               and Wout <= ops.CONV33_MAX_W):
                             # (round 6) the (3, 3) layer's weight gradient as a direct fp32-class kernel over the
                             # band's slice of the concatenated gradient map (31 TFLOP/s as an implicit GEMM)
@@ -764,9 +706,9 @@ class MRDLossFn(torch.autograd.Function):
                         # (round 5) D-step on the direct fp32-class kernels: their data gradients request the
                         # mask of a tile BEFORE its MFMAs, so the fused leaky-ReLU backward (+ bias-gradient
                         # column sums) costs no exposed round trip and saves a pass over the map
-                        fuse_d = (train_disc and MRD_FUSE_MASK and DIRECT_CONV32 and ops.GEMM_PRECISION == 3
-                                  and ops.CONV32_X6 and (l < 4 or (ops.CONV33_X6 and Win <= ops.CONV33_MAX_W)))
-                        if (FUSE_LRELU & 2) or fuse_d:
+                        fuse_d = (train_disc and ops.GEMM_PRECISION == 3 and ops.CONV32_X6
+                                  and (l < 4 or Win <= ops.CONV33_MAX_W))
+                        if fuse_d:
                             _conv2d_dgrad(dy_t, Sx, Ft, Wout, C, w, sw, Win, gx, g_line=dy_line,
                                           g_seq=dy_seq, g_off=dy_off, mask=mk, fm=fmk,
                                           colsum=gbs[l - 1])
@@ -782,7 +724,7 @@ class MRDLossFn(torch.autograd.Function):
                             else:
                                 ops.lrelu_bwd(gx, yb, None, 0.0, SLOPE, 1, nb_, nb_, y_off=mk[1])
                         g = gx
-                    elif not train_disc and DIRECT_CONV32 and ops.GEMM_PRECISION in (0, 1, 3):
+                    elif not train_disc and ops.GEMM_PRECISION in (0, 1, 3):
                         def build_c2t(t):
                             out = ops.empty(27, 2, C, device=t.device)   # [tap][ci][co]
                             ops.permute4(out, t, (27, 2, C, 1), (1, 27, 2 * 27, 0))
@@ -792,7 +734,6 @@ class MRDLossFn(torch.autograd.Function):
                     elif not train_disc:
                         _conv2d_dgrad(dy_t, Sx, Ft, Wout, C, w, sw, Win, g_packed, g_line=dy_line,
                                       g_seq=dy_seq, g_off=dy_off, x_line=ldp, x_off=lo * 2)
-            blanes.join()
             if not train_disc:
                 gfr = ops.empty(B * Ft, win, device=dev)
                 if ops.fft_applies(win):

@@ -13,9 +13,6 @@ import os
 
 from .. import fused_disc as FD
 from .. import ops
-from .._opts import opt
-
-DISC_LANES = opt("disc_lanes", True)
 from .discriminators import MultiPeriodDiscriminator, MultiResolutionDiscriminator
 from .modules import MelSpectrogram
 
@@ -84,35 +81,27 @@ class GAN(nn.Module):
                 pred_audio = self.generator.infer(cond=cond, audio_lens=audio_lens,
                                                   n_timesteps=n_timesteps, clamp_pred=False,
                                                   noise=noise)
-            # MPD and MRD side by side (F2G_DISC_LANES=0 turns it off): each term forks one launch lane per
-            # sub-discriminator inside; autograd runs each node's backward on its forward stream
-            if DISC_LANES:
-                lanes = ops.Lanes(audio.device, 2, "disc")
-                with lanes.lane(0):
-                    disc_loss_mp, _ = self._mp_terms(audio, pred_audio, True)
-                with lanes.lane(1):
-                    disc_loss_mr, _ = self._mr_terms(audio, pred_audio, True)
-                lanes.join()
-            else:
+            # MPD and MRD side by side (F2G_OPTS=lane_cap_disc=1 or F2G_STREAMS=0 runs them one after the
+            # other): each term forks one launch lane per sub-discriminator inside; autograd runs each node's
+            # backward on its forward stream
+            lanes = ops.Lanes(audio.device, 2, "disc")
+            with lanes.lane(0):
                 disc_loss_mp, _ = self._mp_terms(audio, pred_audio, True)
+            with lanes.lane(1):
                 disc_loss_mr, _ = self._mr_terms(audio, pred_audio, True)
+            lanes.join()
             return disc_loss_mp, disc_loss_mr
         # generator step (gan.py:133-166)
         self.discriminator.eval()
         self.generator.train()
         pred_audio = self.generator.infer(cond=cond, audio_lens=audio_lens,
                                           n_timesteps=n_timesteps, clamp_pred=False, noise=noise)
-        if DISC_LANES:
-            lanes = ops.Lanes(audio.device, 3, "disc")
-            with lanes.lane(0):
-                gen_loss_mp, feat_map_loss_mp = self._mp_terms(audio, pred_audio, False)
-            with lanes.lane(1):
-                gen_loss_mr, feat_map_loss_mr = self._mr_terms(audio, pred_audio, False)
-            with lanes.lane(2):
-                mel_recon_loss = self.mel_recon_loss(real=audio, fake=pred_audio)
-            lanes.join()
-        else:
+        lanes = ops.Lanes(audio.device, 3, "disc")
+        with lanes.lane(0):
             gen_loss_mp, feat_map_loss_mp = self._mp_terms(audio, pred_audio, False)
+        with lanes.lane(1):
             gen_loss_mr, feat_map_loss_mr = self._mr_terms(audio, pred_audio, False)
+        with lanes.lane(2):
             mel_recon_loss = self.mel_recon_loss(real=audio, fake=pred_audio)
+        lanes.join()
         return gen_loss_mp, gen_loss_mr, feat_map_loss_mp, feat_map_loss_mr, mel_recon_loss

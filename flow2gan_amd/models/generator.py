@@ -18,7 +18,7 @@ from .. import fused, ops
 from .._opts import opt
 from .modules import AudioConvNeXt, CondEncoder, LinearFilterSpectrogram
 
-# inference: the time paths of all Euler steps are computed once, ahead of the loop (0: per step)
+# inference: the time paths of all Euler steps are computed once, ahead of the loop (0: per step; tests flip it)
 TIME_AHEAD = opt("time_ahead", True)
 
 

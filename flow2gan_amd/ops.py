@@ -191,7 +191,7 @@ def _derived_multi(ts, tag, build):
 # by their data dependencies (an image of a transposed copy comes after the transpose) and every level leaves
 # as f2g_multi launches of up to 48 operations each.
 BATCH = None
-EAGER_REBUILD = opt("eager_rebuild", True)
+EAGER_REBUILD = opt("eager_rebuild", True)    # (a tunable because tests flip it)
 _RECIPES: dict = {}          # id(root parameter) -> {chain key: [weakref(root), chain, used]}
 _REPLAYING = False
 
@@ -447,7 +447,7 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
     padded to whole K slabs): what bench.py's FLOP count uses; the launch itself ignores them.
     split_k: 0 = let the library decide (forms 0/1: split-K onto a zeroed output when the tile
     grid would leave most of the last wave of CUs idle), 1 = off, > 1 = as given."""
-    if form == 1 and LEAN_DGRAD:
+    if form == 1:
         # data gradient C[r,n] = sum_k A[r,k] W[k,n] as a forward GEMM against the cached transpose
         # W^T [n][k]: same products in the same order, and the lean forward kernel applies
         src = getattr(Bm, "_src", None)
@@ -493,7 +493,7 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
         # (>= 4096 rows per block with the general rule's factor), its blocks are dealt in rounds of 512
         tiles = ((A.cols + 127) // 128) * ((Bm.cols + 127) // 128)
         split_k = split_for(A.rows, tiles)
-        if WGRAD_SPLIT512 and form == 2 and GEMM_PRECISION == 0 and atomic:
+        if form == 2 and GEMM_PRECISION == 0 and atomic:
             # (the library's own dispatch rule, asked with the descriptor as it would be launched)
             d.split_k, d.precision = split_k, 0
             if L.lib.f2g_gemm_wgrad_lean(C.byref(d)):
@@ -507,7 +507,7 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
                 (Bm.rows >= X6F_MIN_N and ((A.rows + 127) // 128) * ((Bm.rows + 127) // 128) >= X6F_MIN_TILES)
                 or (A.rows >= X6F_TALL_ROWS and Bm.rows >= 128)):
             in_kernel = True      # (mid-length reductions on well-filled grids: see X6F)
-        if X6F == 2 and X6N and 128 <= A.cols < X6_MIN_K and A.rows >= X6F_TALL_ROWS and Bm.rows == 32:
+        if X6F == 2 and 128 <= A.cols < X6_MIN_K and A.rows >= X6F_TALL_ROWS and Bm.rows == 32:
             in_kernel = True      # (tall GEMMs with 32 output columns: gemm_x6n_kernel)
         if X6F == 2 and X6_MIN_K <= A.cols < X6_NOPASS_K and A.P0 == 1 and A.P1 == 1 and not _is_const(A._keep[0]):
             in_kernel = True      # (a plain activation matrix has no producer-written image: no image pass)
@@ -535,7 +535,7 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
                 if how:
                     if not in_kernel:   # (else gemm_x6f_kernel reads the fp32 operands and splits them itself)
                         d.A, d.B = _x3_operand(A), _x3_operand(Bm)
-                    elif X6F_WIMG and Bm.P0 == 1 and Bm.P1 == 1 and _is_const(Bm._keep[0]):
+                    elif Bm.P0 == 1 and Bm.P1 == 1 and _is_const(Bm._keep[0]):
                         # the WEIGHT operand as its cached image: every row tile used to split the same weight
                         # slab again (M / 128 times); only the activation is split in the kernel.  Whole 32-row
                         # groups: the FRAGMENT-MAJOR image, read straight into MFMA registers (gemm_x6g_kernel)
@@ -543,7 +543,7 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
                     d.precision = 3
             if d.precision != 3:
                 d.E.x3_out = None
-        if form == 2 and X6_WGRAD and atomic and A.split == 0 and Bm.split == 0 and A.lrelu_src is None \
+        if form == 2 and atomic and A.split == 0 and Bm.split == 0 and A.lrelu_src is None \
                 and A.rows >= X6_MIN_K and L.lib.f2g_gemm_lean_ok(C.byref(d)):
             d.precision = 3       # weight gradient: gemm_leanw6_kernel splits the fp32 operands itself
         if x3_out:
@@ -551,9 +551,9 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
                 out._f2g_x3 = out._f2g_x3_buf
             else:
                 out._f2g_x3_bad = True
-    if ((GEMM_PRECISION == 1 and form in (0, 2)) or (GEMM_PRECISION == 2 and form == 0)) and LEAN_SPLIT:
+    if (GEMM_PRECISION == 1 and form in (0, 2)) or (GEMM_PRECISION == 2 and form == 0):
         ok = L.lib.f2g_gemm_lean_ok(C.byref(d))
-        if GEMM_PRECISION == 2 and (ok & 2) and (A.split == 2 or BF16_IMAGES):
+        if GEMM_PRECISION == 2 and (ok & 2):
             # plain bf16 over TRUE bf16 tensors (64-element slabs): activations written as bf16 by
             # their producers (or converted here), weights from the derived-weight cache
             d.A, d.B = _bf16_operand(A), _bf16_operand(Bm)
@@ -597,14 +597,9 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
 
 import os as _os
 
-# column sums of precision-3 epilogues through partial rows instead of atomics (gemm() above)
+# column sums of precision-3 epilogues through partial rows instead of atomics (gemm() above; tests flip it)
 COLSUM_PARTS = opt("colsum_parts", True)
 COLSUM_PARTS_MIN_ROWS = 2048
-
-LEAN_DGRAD = opt("lean_dgrad", True)
-LEAN_SPLIT = opt("lean_split", True)
-CONV32_SPLIT = opt("conv32_split", True)   # split-bf16 direct MRD convs
-
 
 def split3(img, src, src_off_bytes: int, ld: int, rows: int, K: int):
     """f2g_split_bf16x3: img (bf16, rows * K * 3) = three-piece image of the (rows, K) fp32 matrix at
@@ -686,9 +681,6 @@ class split_sharing:
         return img
 
 
-BF16_IMAGES = opt("bf16_images", True)   # precision 2: true bf16 operands
-
-
 def to_bf16(t):
     """bf16 copy (round to nearest even) of a contiguous fp32 tensor through f2g_to_bf16."""
     out = torch.empty(t.shape, device=t.device, dtype=torch.bfloat16)
@@ -727,7 +719,7 @@ def _bf16_operand(o: Operand) -> Operand:
     return n
 
 
-WGRAD_SPLIT512 = opt("wgrad_split512", True)
+# (the numeric thresholds below stay tunables: tests lower them to reach the kernels on small shapes)
 X6_MIN_ROWS = opt("x6_min_rows", 1024)
 # measured in the step (profiles/r03_x6_step.txt): the six-product kernel beats the fp32 lean kernel from
 # reductions of ~2000 on (184 against 131 TFLOP/s at K = 5120, 137 : 121 at 2048) and loses below ~1200
@@ -802,7 +794,7 @@ def x3_reserve(t, halo=None):
     """Storage for the three-piece image of the contiguous fp32 buffer `t` that the GEMMs writing `t`
     fill in their epilogues (gemm(x3_out=True)); halo = (S, Hp, C, top, bottom): those rows of every
     sequence are zero in `t` and are zeroed in the image too.  No-op outside the bf16x6 mode."""
-    if GEMM_PRECISION != 3 or X6F == 1 or not X3_PRODUCERS or t.numel() % 32 or not t.is_contiguous():
+    if GEMM_PRECISION != 3 or X6F == 1 or t.numel() % 32 or not t.is_contiguous():
         return t
     img = torch.empty(t.numel() * 3, device=t.device, dtype=torch.bfloat16)
     if halo is not None:
@@ -814,15 +806,14 @@ def x3_reserve(t, halo=None):
     return t
 
 
-X3_PRODUCERS = opt("x3_producers", True)
 X3_CHECK = opt("x3_check", False)       # (debug: compare every producer-written image with a fresh split)
-X6_WGRAD = opt("x6_wgrad", True)
 # gemm_x6f_kernel (the forward kernel over the fp32 operands, pieces made inside the kernel): 0 never,
 # 1 instead of the image kernel everywhere, 2 (default) where it was measured faster than both the image
 # kernel and the exact-fp32 lean kernel -- reductions of 640 <= K < X6_MIN_K with >= 512 output columns
 # and a tile grid that fills the chip (113920 x 512 x 640: 131 against 114 / 115 TFLOP/s;
 # 12032 x 512 x 1536: 109 : 111 : 95; 6016 x 2304 x 768: 103 : 109 : 96 -- profiles/r03_x6_step.txt),
 # or very tall GEMMs from 128 columns on (113920 x 128 x 1024: 129 against 98; 24064 x 384 x 1152 loses: 88 : 95)
+# (tests flip it)
 X6F = opt("x6f", 2)
 # (round 5: with the wide epilogue -- x6_epilogue.h -- the in-kernel-split kernel also wins on the generator's
 # short reductions: K >= 384, >= 384 columns, >= 180 tiles; same-box step 183.4 -> 178.2 ms, profiles/r05_x6_rules.txt)
@@ -830,16 +821,14 @@ X6F = opt("x6f", 2)
 # TFLOP/s per launch, same-box step 164.24 -> 163.51 ms over three interleaved pairs)
 X6F_MIN_K = opt("x6f_min_k", 160)
 X6F_MIN_N = opt("x6f_min_n", 384)
-# (round 6) tall GEMMs with 32 output columns -- the data gradients that land on the 32-channel MPD map -- on the
-# 128 x 32 instance of the in-kernel-split kernel (gemm_x6n_kernel) instead of the generic fp32 kernel
-X6N = opt("x6n", True)
 X6F_TALL_ROWS = opt("x6f_tall_rows", 50000)     # (round 5: the G-step halves of the MPD layer-3 data gradients too)
 X6F_MIN_TILES = opt("x6f_min_tiles", 180)
 # long reductions over a PLAIN activation matrix (the generator's K = 2304 GEMMs): below this K the in-kernel
 # split instead of an image pass (f2g_split_bf16x3: 10 bytes per element) in front of the image kernel
 X6_NOPASS_K = opt("x6_nopass_k", 4096)
-X6F_WIMG = opt("x6f_wimg", True)     # in-kernel-split kernel: weights from their cached image
-X6G = opt("x6g", True)               # ... in MFMA fragment order, straight into registers (gemm_x6g_kernel)
+# in-kernel-split kernel: weights from their cached image in MFMA fragment order, straight into registers
+# (gemm_x6g_kernel; tests turn it off to reach the row-major image path)
+X6G = opt("x6g", True)
 
 
 def _x3_window_ok(o: Operand) -> bool:
@@ -854,16 +843,11 @@ def operand_formats_ok(Cc: int, Hh: int) -> int:
     """Can the producers of a ConvNeXt block write its GEMM operands directly in the format the
     lean kernels consume?  2: bf16 tensors (precision 2: plain-bf16 inference), 1: split-bf16
     images (precision 1), 0: no (fp32 tensors, converted per GEMM where a lean kernel applies)."""
-    if not LEAN_SPLIT or not L.get_option("lean") or not OPERAND_PRODUCERS:
-        return 0
-    if GEMM_PRECISION == 2 and BF16_IMAGES and Cc % 64 == 0 and Hh % 64 == 0 and Cc > 64:
+    if GEMM_PRECISION == 2 and Cc % 64 == 0 and Hh % 64 == 0 and Cc > 64:
         return 2
     if GEMM_PRECISION == 1 and Cc % 128 == 0 and Hh % 128 == 0:
         return 1
     return 0
-
-
-OPERAND_PRODUCERS = opt("operand_producers", True)
 
 
 def _is_const(t) -> bool:
@@ -908,7 +892,7 @@ def _split_operand(o: Operand) -> Operand:
     return n
 
 
-CONV32_X6 = opt("conv32_x6", True)    # bf16x6 mode: fp32-class direct MRD convs
+CONV32_X6 = opt("conv32_x6", True)    # bf16x6 mode: fp32-class direct MRD convs (bench.py reads it)
 
 
 def x3_image(t2d):
@@ -927,7 +911,7 @@ def conv32_s2_fwd(x, S: int, H: int, Win: int, Wout: int, w_packed, bias, slope:
     d = L.Conv32Desc()
     d.x, d.x_seq, d.x_line = ptr(x), H * Win * 32, Win * 32
     d.S, d.H, d.Win, d.Wout = S, H, Win, Wout
-    if GEMM_PRECISION == 1 and CONV32_SPLIT:
+    if GEMM_PRECISION == 1:
         w_packed = derived(w_packed, "split", split_bf16)
         d.precision = 1
         d._keep = w_packed
@@ -946,7 +930,6 @@ def conv32_s2_fwd(x, S: int, H: int, Win: int, Wout: int, w_packed, bias, slope:
     return y
 
 
-CONV33_X6 = opt("conv33_x6", True)    # bf16x6 mode: direct (3, 3) band layer
 CONV33_MAX_W = 112     # one image row + its border must fit the kernel's 352 staged pixels: 3 * (W + 2) <= 352
 
 
@@ -1008,7 +991,7 @@ def conv32_s2_dgrad(g, S: int, H: int, Win: int, Wout: int, wT, gx, g_seq=None, 
     d.x_line = g_line if g_line is not None else Wout * 32
     d.x_seq = g_seq if g_seq is not None else H * d.x_line
     d.S, d.H, d.Win, d.Wout = S, H, Win, Wout
-    if GEMM_PRECISION == 1 and CONV32_SPLIT:
+    if GEMM_PRECISION == 1:
         wT = derived(wT, "split", split_bf16)
         d.precision = 1
         d._keep = wT
@@ -1040,7 +1023,7 @@ def conv32_s2_wgrad(x, g, S: int, H: int, Win: int, Wout: int, gw):
     d.S, d.H, d.Win, d.Wout = S, H, Win, Wout
     d.w, d.bias, d.lrelu_slope = None, None, 0.0
     d.y, d.y_seq, d.y_line = ptr(g), H * Wout * 32, Wout * 32
-    if GEMM_PRECISION == 1 and CONV32_SPLIT:
+    if GEMM_PRECISION == 1:
         d.precision = 1
     elif GEMM_PRECISION == 3 and CONV32_X6:
         d.precision = 3
@@ -1257,7 +1240,7 @@ _SIDE_STREAMS: dict = {}
 # F2G_OPTS="lane_cap_mpd=3,lane_cap_mrd=2": at most that many streams behind the lanes of a pool (lane i ->
 # stream i % cap; a measurement aid: how much concurrency the step wants)
 _LANE_CAP = {pool: opt("lane_cap_" + pool, 0) for pool in ("branch", "disc", "mpd", "mrd", "mel", "condpath",
-                                                           "timepath", "band")}
+                                                           "timepath")}
 _LANE_CAP = {k: v for k, v in _LANE_CAP.items() if v > 0}
 
 
@@ -1367,13 +1350,10 @@ def wgrad(dY, M: int, ldy: int, X: Operand, g_out, ldg: Optional[int] = None, ou
 
 
 # ------------------------------------------------------------------ fused pointwise MLP (bf16)
-FUSED_MLP = opt("fused_mlp", True)
-
-
 def fused_mlp_applies(Cc: int, Hh: int) -> bool:
     """pwconv1 -> PReLU -> pwconv2 (+ residual) as ONE kernel with the hidden activation on chip
     (csrc/fusedmlp.hip): plain-bf16 inference, C in {384, 512, 768}."""
-    return FUSED_MLP and GEMM_PRECISION == 2 and bool(L.lib.f2g_fused_mlp_ok(Cc, Hh))
+    return GEMM_PRECISION == 2 and bool(L.lib.f2g_fused_mlp_ok(Cc, Hh))
 
 
 def mlp_pack(w1, w2):
@@ -1459,8 +1439,8 @@ def fused_block_multi(entries):
     return [e["out"] for e in entries]
 
 
-FUSED_BLOCK = opt("fused_block", True)
-# all Fourier branches' blocks of a layer in one launch (bf16 inference; 0: one launch per branch and lane)
+# all Fourier branches' blocks of a layer in one launch (bf16 inference; 0: one launch per branch and lane;
+# tests flip it)
 FUSED_MULTI = opt("fused_multi", True)
 
 
@@ -1750,9 +1730,6 @@ def zeros_many(shapes, device):
 
 
 # ------------------------------------------------------------------ first MPD layer (1 -> 32 channels)
-MPD0_DIRECT = opt("mpd0_direct", True)
-
-
 def _mpd0_desc(x, S, H, Hout, halo, w=None, bias=None, slope=0.0, y=None, x_off=0, y_off=0):
     d = L.Mpd0Desc()
     d.x = None if x is None else ptr(x) + 4 * x_off
@@ -1829,9 +1806,9 @@ def mpdpost_wgrad(y, S, H, halo, g, gw):
 
 
 # ------------------------------------------------------------------ LDS-butterfly FFT (n_fft >= 1024)
-USE_FFT = opt("fft", True)
+USE_FFT = opt("fft", True)     # (the test uses the DFT-GEMM path as its reference)
 # transforms below FFT_MIN stay on the DFT GEMM (the 32- / 64-point mel-reconstruction scales: a
-# handful of MFMAs per frame).  F2G_FFT_MIN=1024 restores round 2's split (LDS FFT for n_fft >= 1024 only).
+# handful of MFMAs per frame).  F2G_OPTS=fft_min=1024 restores round 2's split (LDS FFT for n_fft >= 1024 only).
 FFT_MIN = opt("fft_min", 128)
 _FFT_TABLES = {}
 
@@ -1857,7 +1834,7 @@ def _spec_flags(spec, interleaved: bool) -> int:
     return (1 if interleaved else 0) | (2 if spec.dtype == torch.bfloat16 else 0)
 
 
-FFT_REFLECT = opt("fft_reflect", True)   # center / reflect padding inside the FFT kernel
+FFT_REFLECT = opt("fft_reflect", True)   # center / reflect padding inside the FFT kernel (tests flip it)
 
 
 def stft_fft(x, n_fft: int, hop: int, F: int, spec, interleaved: bool = False, zero_pad: bool = False):

@@ -40,10 +40,9 @@ const char* f2g_last_error(void);
 /* Library options: every tunable of the dispatch (which kernel family may take a launch, tile rules, the
  * bit-reproducible mode) is an int in one table, initialised once -- built-in defaults, then
  * F2G_OPTS="name=value,..." and F2G_DETERMINISTIC from the environment -- and changed afterwards only through
- * this setter; nothing reads the environment on a launch path.  Names: lean, lean_tall, lean_tap, lean_wgrad,
- * x6_tap, x6_wide, x6p, w6t, deterministic, streamk, conv2ch_v2, conv32_v2, conv32_wgrad_v2, mlp_rt, mlp_split,
- * multi_rt384, multi_rt512, streamk_min (meanings: csrc/common.h).  Unknown name: F2G_EINVAL.  Not thread safe against
- * concurrent launches. */
+ * this setter; nothing reads the environment on a launch path.  Names (any letter case): lean_tall, lean_wgrad, x6p,
+ * deterministic, streamk, mlp_rt, mlp_split, multi_rt384, multi_rt512, streamk_min (meanings: csrc/common.h).
+ * Unknown name: F2G_EINVAL.  Not thread safe against concurrent launches. */
 int f2g_set_option(const char* name, int32_t value);
 int f2g_get_option(const char* name, int32_t* value);
 

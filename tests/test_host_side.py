@@ -439,27 +439,43 @@ def test_weight_gradient_split_rule():
         assert s2 == 1 or rows // s2 >= 4096, (rows, tiles, s2)                          # never below the kernel's rule
 
 
-def test_library_options_and_python_tunables(monkeypatch):
-    """Round 6: one options table in the library (f2g_set_option / f2g_get_option; nothing reads the environment
-    on a launch path) and one override variable for the Python tunables (F2G_OPTS, flow2gan_amd/_opts.py)."""
+def test_surviving_options_retired_names_and_unknown_name_warning(monkeypatch):
+    """One options table in the library (f2g_set_option / f2g_get_option; nothing reads the environment on a
+    launch path) and one override variable for the Python tunables (F2G_OPTS, flow2gan_amd/_opts.py).  Only the
+    surviving switches are options: the retired ones raise, and an F2G_OPTS name neither side knows warns."""
+    import warnings
     from flow2gan_amd import _lib, _opts
-    names = ("lean", "lean_tall", "lean_tap", "lean_wgrad", "x6_tap", "x6_wide", "x6p", "w6t", "deterministic",
-             "streamk", "conv2ch_v2", "conv32_v2", "conv32_wgrad_v2", "mlp_rt", "mlp_split", "multi_rt384",
+    names = ("lean_tall", "lean_wgrad", "x6p", "deterministic", "streamk", "mlp_rt", "mlp_split", "multi_rt384",
              "multi_rt512", "streamk_min")
     for n in names:
         v = _lib.get_option(n)
         assert _lib.set_option(n, v + 5) == v and _lib.get_option(n) == v + 5
         assert _lib.set_option(n, v) == v + 5 and _lib.get_option(n) == v
+        assert _lib.get_option(n.upper()) == v           # (names match in any letter case, as in F2G_OPTS)
     with pytest.raises(_lib.F2GError):
         _lib.set_option("no_such_option", 1)
-    with pytest.raises(_lib.F2GError):
-        _lib.get_option("x6pr")            # (a removed kernel's switch is not an option any more)
+    retired = ("x6pr", "lean", "lean_tap", "x6_tap", "x6_wide", "w6t", "conv2ch_v2", "conv32_v2", "conv32_wgrad_v2")
+    for n in retired:                      # (a retired switch is not an option any more)
+        with pytest.raises(_lib.F2GError):
+            _lib.get_option(n)
     assert _lib.lib.f2g_set_option(None, 1) != 0
     # Python side: typed like the default, unknown names ignored, booleans from 0 / 1
-    monkeypatch.setattr(_opts, "_OPTS", _opts._parse("x6f_min_k=160, fuse_lrelu=3,disc_lanes=0,  x6p=2,junk"))
-    assert _opts.opt("x6f_min_k", 384) == 160 and _opts.opt("fuse_lrelu", 0) == 3
-    assert _opts.opt("disc_lanes", True) is False and _opts.opt("spec_pad", True) is True
+    monkeypatch.setattr(_opts, "_OPTS", _opts._parse("x6f_min_k=160, fft_min=3,fused_multi=0,  x6p=2,junk"))
+    assert _opts.opt("x6f_min_k", 384) == 160 and _opts.opt("fft_min", 0) == 3
+    assert _opts.opt("fused_multi", True) is False and _opts.opt("x6g", True) is True
     assert _opts.opt("x6_min_k", 2048) == 2048
+    # names neither side knows draw one warning (the package checks F2G_OPTS this way when it is imported);
+    # every surviving name is known to one side
+    python_side = ("conv32_x6", "fft", "fft_reflect", "fused_multi", "eager_rebuild", "time_ahead", "colsum_parts",
+                   "x6f", "x6g", "x3_check", "multi_cap", "lane_cap_disc", "x6_min_k", "x6_min_rows", "x6_nopass_k",
+                   "x6f_min_k", "x6f_min_n", "x6f_min_tiles", "x6f_tall_rows", "fft_min")
+    monkeypatch.setattr(_opts, "_OPTS", _opts._parse("direct_conv=0,x6p=2"))
+    with pytest.warns(UserWarning, match="direct_conv"):
+        assert _opts.warn_unknown(_lib.has_option) == ["direct_conv"]
+    monkeypatch.setattr(_opts, "_OPTS", _opts._parse(",".join(n + "=1" for n in python_side + names)))
+    with warnings.catch_warnings():
+        warnings.simplefilter("error")
+        assert _opts.warn_unknown(_lib.has_option) == []
     # no per-feature environment switch is left in the package (the kept ones are listed in _opts.py's docstring)
     import glob
     kept = {"F2G_GEMM", "F2G_STREAMS", "F2G_DETERMINISTIC", "F2G_WEIGHT_CACHE", "F2G_LIB_PATH", "F2G_DRYRUN",

@@ -20,14 +20,13 @@ python tools/streaming_latency.py 100 > $O/streaming.txt 2>/dev/null
 # bf16x6 mode: per-shape table, variants
 F2G_GEMM_REPORT=60 python bench.py --full --gemm bf16x6 --steps 3 --warmup 2 --no-cpu-baseline --no-fast-mode 2> $O/x6_shapes.txt > $O/x6_bench_roofline.json
 F2G_X6_MIN_K=32 F2G_GEMM_REPORT=60 python bench.py --full --gemm bf16x6 --steps 3 --warmup 2 --no-cpu-baseline --no-fast-mode 2> $O/x6_shapes_all.txt > /dev/null
-( for env in "" "F2G_CONV32_X6=0" "F2G_X6_TAP8=0" "F2G_X6_WGRAD=0"; do
+( for env in "" "F2G_CONV32_X6=0" "F2G_X6_TAP8=0"; do
     echo "# $env python bench.py --gemm bf16x6 --steps 8 --warmup 3 --no-cpu-baseline --no-fast-mode --no-roofline"
     env $env python bench.py --gemm bf16x6 --steps 8 --warmup 3 --no-cpu-baseline --no-fast-mode --no-roofline 2>/dev/null | tail -1 | cut -c1-260
   done
-  for env in "" "F2G_CONV32_WGRAD_V2=0" "F2G_CONV2CH_V2=0" "F2G_BAND_LANES=1"; do
-    echo "# $env python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-fast-mode --no-roofline   (exact fp32, same box)"
-    env $env python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-fast-mode --no-roofline 2>/dev/null | tail -1 | cut -c1-260
-  done ) > $O/x6_step_variants.txt
+  echo "# python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-fast-mode --no-roofline   (exact fp32, same box)"
+  python bench.py --steps 8 --warmup 3 --no-cpu-baseline --no-fast-mode --no-roofline 2>/dev/null | tail -1 | cut -c1-260
+) > $O/x6_step_variants.txt
 python tools/x6_gemm_bench.py > $O/x6_gemm_bench.txt 2>/dev/null
 # direct MRD convs: exact fp32 and fp32 class
 ( for m in fp32 bf16x6; do echo "## MODE=$m"; MODE=$m python tools/conv32_probe.py 2>&1 | grep -v amdgpu.ids; done ) > $O/conv32_probe.txt

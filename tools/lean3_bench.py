@@ -38,12 +38,7 @@ for R, K, N in shapes:
     Ws = ops._split_operand(ops.mat(W))
     t2 = timeit(lambda: ops.gemm(As, Ws, out, split_k=1))
     t3 = timeit(lambda: ops.split_bf16(A))
-    os.environ["X"] = "1"
-    ops.LEAN_SPLIT = False
-    t4 = timeit(lambda: ops.gemm(ops.mat(A), ops.mat(W), out, split_k=1))
-    ops.LEAN_SPLIT = True
     print(f"R={R:6d} K={K:5d} N={N:5d} fp32 {fl/t0/1e12:6.1f} TF ({t0*1e6:6.0f} us) | split+lean3 "
           f"{fl/t1/1e12:6.1f} TF ({t1*1e6:6.0f} us, path {path}) | lean3 alone {fl/t2/1e12:6.1f} TF "
-          f"({t2*1e6:6.0f} us) | split pass {t3*1e6:5.0f} us = {8.0*R*K/t3/1e9:6.0f} GB/s | generic b3 "
-          f"{fl/t4/1e12:6.1f} TF", flush=True)
+          f"({t2*1e6:6.0f} us) | split pass {t3*1e6:5.0f} us = {8.0*R*K/t3/1e9:6.0f} GB/s", flush=True)
 ops.set_gemm_precision("fp32")
