@@ -21,6 +21,7 @@
 //     bytes), both conflict-free for ds_read_b128 (pitch = 4 dwords mod 64).
 // Algorithmic traffic per block: z tile + residual in, output tile out, the weight stream
 // (12 C^2 bytes) from L2; FLOPs 12 C^2 per row.
+#include <stdio.h>
 #include <stdlib.h>
 
 #include "common.h"
@@ -487,6 +488,10 @@ void fused_mlp_kernel(const f2g_fused_mlp_desc d, const f2g_dwnorm_fwd_desc P, i
 // longest-processing-time-first list scheduling: the long tiles start first and the short ones
 // fill the CUs as they free up.
 constexpr int MULTI_MAX = 4;
+// what the last fused launch ran (f2g_fused_last_launch): 0 f2g_fused_mlp, 1 f2g_fused_block, 2 the multi launch;
+// rows / 32 per tile of each entry (in the caller's order) and the hidden-dimension parts of a single launch
+int g_fused_kind = -1, g_fused_n = 0, g_fused_parts = 0;
+int g_fused_rt[MULTI_MAX];
 struct fused_multi_args {
   f2g_fused_mlp_desc d[MULTI_MAX];
   f2g_dwnorm_fwd_desc P[MULTI_MAX];
@@ -582,6 +587,7 @@ int launch_fused(const f2g_fused_mlp_desc& d, hipStream_t st, const f2g_dwnorm_f
   }
   f2g_dwnorm_fwd_desc P{};
   if (dw) P = *dw;
+  g_fused_kind = DW ? 1 : 0, g_fused_n = 1, g_fused_rt[0] = RT, g_fused_parts = J;
   hipLaunchKernelGGL((fused_mlp_kernel<RT, NT, DW>), dim3(tiles, J), dim3(256), smem, st, d, P, spb);
   return f2g_check_launch();
 }
@@ -714,12 +720,14 @@ extern "C" int f2g_fused_block_multi(const f2g_dwnorm_fwd_desc* wp, const f2g_fu
     a.cum[k] = total;
     const int BM = bm_of(mp[i].C);
     a.rt[k] = BM / 32;
+    g_fused_rt[i] = BM / 32;
     total += (mp[i].rows + BM - 1) / BM;
     const size_t sm = (size_t)BM * (mp[i].C * 2 + 16) + (size_t)BM * PP;
     smem = sm > smem ? sm : smem;
   }
   for (int k = n; k <= MULTI_MAX; ++k) a.cum[k] = total;
   a.n = n;
+  g_fused_kind = 2, g_fused_n = n, g_fused_parts = 1;
   if (total == 0) return F2G_OK;
   static bool attr_done = false;
   if (!attr_done) {
@@ -729,4 +737,17 @@ extern "C" int f2g_fused_block_multi(const f2g_dwnorm_fwd_desc* wp, const f2g_fu
   }
   hipLaunchKernelGGL(fused_block_multi_kernel, dim3(total), dim3(256), smem, (hipStream_t)stream, a);
   return f2g_check_launch();
+}
+
+// "fused_mlp<rt=2,parts=3>", "fused_block<rt=4,parts=1>" or "fused_block_multi<rt=4,2,3,2>" (rows / 32 per tile of
+// each entry, in the order they were handed over); "" before the first launch
+extern "C" const char* f2g_fused_last_launch(void) {
+  static char buf[96];
+  static const char* const kinds[3] = {"fused_mlp", "fused_block", "fused_block_multi"};
+  if (g_fused_kind < 0) return "";
+  int n = snprintf(buf, sizeof(buf), "%s<rt=", kinds[g_fused_kind]);
+  for (int i = 0; i < g_fused_n; ++i) n += snprintf(buf + n, sizeof(buf) - n, i ? ",%d" : "%d", g_fused_rt[i]);
+  if (g_fused_kind < 2) n += snprintf(buf + n, sizeof(buf) - n, ",parts=%d", g_fused_parts);
+  snprintf(buf + n, sizeof(buf) - n, ">");
+  return buf;
 }

@@ -21,6 +21,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdio.h>
+#include <string.h>
 
 #include "common.h"
 #include "x6_epilogue.h"
@@ -28,6 +30,8 @@
 namespace {
 
 int g_last_path = 0;   // kernel family of the last dispatch (f2g_gemm_last_path)
+const char* g_last_kernel = "";   // instance of the last dispatch (f2g_gemm_last_kernel): a literal of this file,
+int g_last_split = 1;             // narrow.hip or gemm_x6p.hip, with the K split of a generic launch
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
@@ -766,8 +770,30 @@ int launch(const f2g_gemm_desc& d, int M, int N, int K, int split, hipStream_t s
   return f2g_check_launch();
 }
 
+// name of a generic route (f2g_gemm_last_kernel): form (F0 forward, F1 data gradient, F2 weight gradient) and
+// the loader modes of A and B
+template <bool AKM, bool BKM, int AMODE, int BMODE>
+const char* generic_name() {
+  if (AKM) {
+    if (AMODE == PF && BMODE == PF) return "generic<F2,PF,PF>";
+    if (AMODE == PF && BMODE == GF) return "generic<F2,PF,GF>";
+    if (AMODE == GF && BMODE == GF) return "generic<F2,GF,GF>";
+    return "generic<F2,SL,SL>";
+  }
+  if (BKM) {
+    if (AMODE == PF) return "generic<F1,PF,PF>";
+    if (AMODE == GF) return "generic<F1,GF,PF>";
+    return "generic<F1,SL,SL>";
+  }
+  if (AMODE == PF) return "generic<F0,PF,PF>";
+  if (AMODE == GF) return "generic<F0,GF,PF>";
+  if (AMODE == GR) return "generic<F0,GR,PF>";
+  return "generic<F0,SL,SL>";
+}
+
 template <bool AKM, bool BKM, int AMODE, int BMODE>
 int dispatch_tile(const f2g_gemm_desc& d, int M, int N, int K, int split, hipStream_t st) {
+  f2g_note_kernel(generic_name<AKM, BKM, AMODE, BMODE>(), split);
   // split-bf16 core: fast loader modes only; SL operands (small GEMMs) stay on exact fp32
   // (the reflect-padded STFT framing stays exact: small spectral bins are differences of large
   // terms, and the log-mel / spectral losses take their logarithm)
@@ -1036,7 +1062,8 @@ void gemm_lean_kernel(const f2g_gemm_desc d, int M, int N, int K, int kchunk, in
 #pragma unroll
     for (int ni = 0; ni < 2; ++ni) {
       const int col = n0 + (wn * 2 + ni) * 32 + li;
-      const float b = (d.E.bias && first && col < N) ? d.E.bias[col] : 0.f;
+      // (a scaled result takes its bias in the epilogue: v = acc * scale + bias, as the generic kernels)
+      const float b = (d.E.bias && first && col < N && (EP != 3 || d.E.scale == 0.f)) ? d.E.bias[col] : 0.f;
 #pragma unroll
       for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
@@ -1564,7 +1591,7 @@ void gemm_lean_kernel(const f2g_gemm_desc d, int M, int N, int K, int kchunk, in
       }
     } else {
       f2g_epilogue E2 = E;
-      E2.bias = nullptr;   // already in the accumulators
+      if (E.scale == 0.f) E2.bias = nullptr;   // already in the accumulators
       if (partial) { E2.atomic = 1; E2.accumulate = 0; }
       gemm_epilogue<2, 2>(E2, acc, M, N, m0, n0, wm, wn, li_e, h_e, first);
     }
@@ -1701,6 +1728,26 @@ int launch_lean(const f2g_gemm_desc& d, int M, int N, int K, int split, int upb,
     attr_done = true;
   }
   g_last_path = upb > 0 ? 2 : 1;
+  {
+    static const char* const flat[4][4] = {
+        {"lean<sk=0,ep=0,pm=0>", "lean<sk=0,ep=0,pm=1>", "lean<sk=0,ep=0,pm=2>", "lean<sk=0,ep=0,pm=3>"},
+        {"lean<sk=0,ep=1,pm=0>", "lean<sk=0,ep=1,pm=1>", "lean<sk=0,ep=1,pm=2>", "lean<sk=0,ep=1,pm=3>"},
+        {"lean<sk=0,ep=2,pm=0>", "lean<sk=0,ep=2,pm=1>", "lean<sk=0,ep=2,pm=2>", "lean<sk=0,ep=2,pm=3>"},
+        {"lean<sk=0,ep=3,pm=0>", "lean<sk=0,ep=3,pm=1>", "lean<sk=0,ep=3,pm=2>", "lean<sk=0,ep=3,pm=3>"}};
+    static const char* const sk[4] = {"lean<sk=1,ep=3,pm=0>", "lean<sk=1,ep=3,pm=1>", "lean<sk=1,ep=3,pm=2>",
+                                      "lean<sk=1,ep=3,pm=3>"};
+    static const char* const tl[4][2] = {{"lean_tall<ep=0,pm=1>", "lean_tall<ep=0,pm=3>"},
+                                         {"lean_tall<ep=1,pm=1>", "lean_tall<ep=1,pm=3>"},
+                                         {"lean_tall<ep=2,pm=1>", "lean_tall<ep=2,pm=3>"},
+                                         {"lean_tall<ep=3,pm=1>", "lean_tall<ep=3,pm=3>"}};
+    static const char* const tp[2] = {"lean_tap<ep=2>", "lean_tap<ep=3>"};
+    // (the same selection as the launches below)
+    const char* name = tap && (ep == 2 || ep == 3) ? tp[ep - 2]
+                       : tall                      ? tl[ep][pm == 1 ? 0 : 1]
+                       : upb > 0                   ? sk[pm]
+                                                   : flat[ep][pm];
+    f2g_note_kernel(name, split);
+  }
 #define F2G_LEAN(SKV, EPV)                                                                        \
   do {                                                                                            \
     if (pm == 1)                                                                                  \
@@ -2383,6 +2430,7 @@ int launch_leanw(const f2g_gemm_desc& d, int M, int N, int K, int split, hipStre
     attr_done = true;
   }
   g_last_path = 1;
+  f2g_note_kernel(host_plain(d.B) ? "leanw<bwin=0>" : "leanw<bwin=1>", split);
   if (host_plain(d.B))
     hipLaunchKernelGGL(gemm_leanw_kernel<false>, grid, dim3(256), smem, st, d, M, N, K, kchunk);
   else
@@ -2404,6 +2452,7 @@ int launch_leanw3(const f2g_gemm_desc& d, int M, int N, int K, int split, hipStr
     attr_done = true;
   }
   g_last_path = 1;
+  f2g_note_kernel(host_plain(d.B) ? "leanw3<bwin=0>" : "leanw3<bwin=1>", split);
   if (host_plain(d.B))
     hipLaunchKernelGGL(gemm_leanw3_kernel<false>, grid, dim3(256), smem, st, d, M, N, K, kchunk);
   else
@@ -2429,6 +2478,7 @@ int launch_leanw6(const f2g_gemm_desc& d, int M, int N, int K, int split, hipStr
     attr_done = true;
   }
   g_last_path = 4;
+  f2g_note_kernel(host_plain(d.B) ? "leanw6<bwin=0>" : "leanw6<bwin=1>", split);
   if (host_plain(d.B))
     hipLaunchKernelGGL(gemm_leanw6_kernel<false>, grid, dim3(256), smem, st, d, M, N, K, kchunk);
   else
@@ -3213,6 +3263,7 @@ static int launch_x6(const f2g_gemm_desc& d, hipStream_t st) {
   }
   R.bytes = (unsigned)(x6_a_extent(d.A) * 6);
   dim3 grid((M + 127) / 128, (N + 127) / 128);
+  f2g_note_kernel("x6", 1);
   hipLaunchKernelGGL(gemm_x6_kernel, grid, dim3(256), smem, st, d, M, N, K, R, x6_wide(d));
   g_last_path = 4;
   return f2g_check_launch();
@@ -3251,6 +3302,7 @@ static int launch_x6f(const f2g_gemm_desc& d, hipStream_t st) {
   }
   if (N <= 32 && d.B.split == 3 && !d.E.x3_out) {     // thin outputs: 128 x 32 tiles (gemm_x6n_kernel)
     constexpr size_t smem_n = (128 + 32) * 208;
+    f2g_note_kernel("x6n", 1);
     hipLaunchKernelGGL(gemm_x6n_kernel, dim3((M + 127) / 128), dim3(256), smem_n, st, d, M, N, K, R);
     g_last_path = 5;      // (its own family in the benchmark's tables: a different kernel on 128 x 32 tiles)
     return f2g_check_launch();
@@ -3258,10 +3310,12 @@ static int launch_x6f(const f2g_gemm_desc& d, hipStream_t st) {
   dim3 grid((M + 127) / 128, (N + 127) / 128);
   if (d.B.split == 4) {
     constexpr size_t smem_g = 4 * x6e::ESZ > 128 * 208 ? 4 * x6e::ESZ : 128 * 208;
+    f2g_note_kernel("x6g", 1);
     hipLaunchKernelGGL(gemm_x6g_kernel, grid, dim3(256), smem_g, st, d, M, N, K, R, x6_wide(d));
     g_last_path = 4;
     return f2g_check_launch();
   }
+  f2g_note_kernel(d.B.split == 3 ? "x6f<wimg=1>" : "x6f<wimg=0>", 1);
   if (d.B.split == 3) hipLaunchKernelGGL(gemm_x6f_kernel<true>, grid, dim3(256), smem, st, d, M, N, K, R, x6_wide(d));
   else hipLaunchKernelGGL(gemm_x6f_kernel<false>, grid, dim3(256), smem, st, d, M, N, K, R, x6_wide(d));
   g_last_path = 4;
@@ -3310,6 +3364,20 @@ extern "C" int f2g_split_bf16x3(void* dst, const float* src, int64_t ld, int32_t
 }
 
 extern "C" int f2g_gemm_last_path(void) { return g_last_path; }
+
+void f2g_note_kernel(const char* name, int split) {
+  g_last_kernel = name;
+  g_last_split = split;
+}
+
+extern "C" const char* f2g_gemm_last_kernel(void) {
+  static char buf[64];
+  if (g_last_split > 1 && strncmp(g_last_kernel, "generic<", 8) == 0)
+    snprintf(buf, sizeof(buf), "%s split=%d", g_last_kernel, g_last_split);
+  else
+    snprintf(buf, sizeof(buf), "%s", g_last_kernel);
+  return buf;
+}
 
 // 1 if f2g_gemm would run this form-2 descriptor (exact fp32, E.atomic, split_k as set) on the K-major lean
 // weight-gradient kernel -- two blocks per CU, so the host deals its blocks in rounds of 512 (ops.split_for)
@@ -3389,6 +3457,7 @@ extern "C" int f2g_split_bf16(float* dst, const float* src, int64_t n, f2g_strea
 
 extern "C" int f2g_gemm(const f2g_gemm_desc* dp, f2g_stream_t stream) {
   if (!dp || !dp->A.base || !dp->B.base || !dp->E.C) return F2G_EINVAL;
+  f2g_note_kernel("", 1);
   const f2g_gemm_desc& d = *dp;
   hipStream_t st = (hipStream_t)stream;
   int split = d.split_k > 0 ? d.split_k : 1;

@@ -542,6 +542,7 @@ int f2g_launch_x6p(const f2g_gemm_desc& d, int taps, long long a_extent, hipStre
   R.P0 = d.A.P0, R.HpIn = (int)(d.A.seq_stride / d.A.unit), R.offpos = -d.A.pad0, R.C32 = d.A.unit / 32;
   R.bytes = (unsigned)(a_extent * 6);
   dim3 grid((M + 255) / 256, (N + 127) / 128);
+  f2g_note_kernel(taps == 5 ? "x6p<taps=5>" : "x6p<taps=2>", 1);
   if (taps == 5) hipLaunchKernelGGL(gemm_x6p_kernel<5>, grid, dim3(512), smem, st, d, M, N, K, R);
   else hipLaunchKernelGGL(gemm_x6p_kernel<2>, grid, dim3(512), smem, st, d, M, N, K, R);
   return f2g_check_launch();
@@ -592,6 +593,7 @@ int f2g_launch_leanw6t(const f2g_gemm_desc& d, int split, hipStream_t st) {
     const int spb = (nseq + best - 1) / best, zs = (nseq + spb - 1) / spb;
     const long long xrows = (long long)nseq * (d.B.seq_stride / Cin);
     dim3 grid(M / 128, Cin / 128, zs);
+    f2g_note_kernel("leanw6s<step=3>", split);
     hipLaunchKernelGGL((gemm_leanw6s_kernel<5, 3>), grid, dim3(512), smem3, st, d, nseq, spb, xrows);
     return f2g_check_launch();
   }
@@ -620,6 +622,7 @@ int f2g_launch_leanw6t(const f2g_gemm_desc& d, int split, hipStream_t st) {
   zs = (K + kchunk - 1) / kchunk;
   const long long xrows = (long long)(d.B.rows / d.B.P0) * d.B.P0;
   dim3 grid(M / 128, Cin / 128, zs);
+  f2g_note_kernel("leanw6t<step=1>", split);
   hipLaunchKernelGGL(gemm_leanw6t_kernel<5>, grid, dim3(512), smem, st, d, K, kchunk, xrows);
   return f2g_check_launch();
 }

@@ -227,6 +227,11 @@ int32_t f2g_gemm_colsum_part_rows(const f2g_gemm_desc* d);
  * 0 generic MFMA kernels, 1 lean kernel, 2 lean kernel in stream-K mode, 3 narrow VALU kernels,
  * 4 the precision-3 kernels, 5 the precision-3 kernel for <= 32 output columns (gemm_x6n_kernel). */
 int f2g_gemm_last_path(void);
+/* Kernel instance the last f2g_gemm call launched (tests and diagnostics, not thread safe; "" when it
+ * launched nothing), e.g. "lean<sk=1,ep=3,pm=0>" (lean kernel: stream-K, epilogue instance, operand mode),
+ * "lean_tall<ep=2,pm=1>", "lean_tap<ep=3>", "narrow_wgrad4<4>", "x6f<wimg=1>" or "generic<F1,GF,PF> split=3"
+ * (generic MFMA tiles: form, loader modes of A and B, and the K split when > 1). */
+const char* f2g_gemm_last_kernel(void);
 
 /* ------------------------------------------------------------------------------------------
  * Fused depthwise-conv(k=7) + BiasNorm + cond add + time scale  (modules.py:473-485, A.4):
@@ -786,6 +791,11 @@ int f2g_fused_block(const f2g_dwnorm_fwd_desc* dw, const f2g_fused_mlp_desc* mlp
  * calls (row by row the same arithmetic; tile heights, hence kernel instances, may differ). */
 int f2g_fused_block_multi(const f2g_dwnorm_fwd_desc* dw, const f2g_fused_mlp_desc* mlp, int32_t n,
                           f2g_stream_t stream);
+/* What the last of the three fused launches above ran (tests and diagnostics, not thread safe; "" before the
+ * first): "fused_mlp<rt=R,parts=J>" / "fused_block<rt=R,parts=J>" (rows / 32 per tile, blocks per row tile
+ * along the hidden dimension) or "fused_block_multi<rt=R0,R1,...>" (rows / 32 per tile of each entry, in the
+ * order handed over). */
+const char* f2g_fused_last_launch(void);
 
 #ifdef __cplusplus
 }
