@@ -9,8 +9,9 @@
 
 int f2g_check_launch();
 // records the kernel instance f2g_gemm launches (f2g_gemm_last_kernel): `name` must be a string literal (the
-// suite lists them from the sources); `split` > 1 is appended to the names of the generic routes
-void f2g_note_kernel(const char* name, int split);
+// suite lists them from the sources); `split` > 1 is appended to the names of the generic routes; `path` is the
+// instance's kernel family (f2g_gemm_last_path)
+void f2g_note_kernel(const char* name, int split, int path);
 // Library options (capi.hip): every tunable the dispatch looks at is one int of a table that is initialised
 // ONCE -- defaults, then `F2G_OPTS="name=value,..."` from the environment -- and changed afterwards only through
 // f2g_set_option (tests, lab tools).  No getenv on a launch path.  The table's names (lower case, matched without

@@ -2,7 +2,7 @@
 // discriminators.py:171-181: Conv2d(32, 32, (3, 9), stride (1, 2), padding (1, 4))) on the bf16 matrix
 // pipe: f2g_conv32_desc.precision = 3.  Every fp32 value is three bf16 pieces x = p0 + p1 + p2 and a
 // product the six v_mfma_f32_32x32x16_bf16 with i + j <= 2, fp32 accumulation, smallest terms first
-// (error <= ~2^-23 per product: the class of fp32 rounding -- gemm.hip, gemm_x6_kernel).  The matrix
+// (error <= ~2^-23 per product: the class of fp32 rounding -- gemm_x6.hip, gemm_x6_kernel).  The matrix
 // pipe is 2.7x less busy per product than with v_mfma_f32_32x32x2_f32 (12 MFMAs of 32 cycles per tap and
 // wave instead of 16 of 64).
 //

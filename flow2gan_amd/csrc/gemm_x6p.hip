@@ -21,17 +21,13 @@
 //    patch (32 rows at a time) into 8-column row segments: bias / leaky ReLU / the leaky-ReLU backward mask of
 //    the layer below (+ feature-matching term) with 16-byte loads, 16-byte stores of the fp32 map AND of its
 //    image pieces from the same registers, column sums (the bias gradient) reduced over the wave's rows
-//    before the atomics; one division per ROW (x6_epilogue.h, shared with gemm.hip's six-product kernels).
+//    before the atomics; one division per ROW (x6_epilogue.h, shared with gemm_x6.hip's six-product kernels).
 #include <stdlib.h>
 
-#include "common.h"
+#include "gemm_common.h"
 #include "x6_epilogue.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int PITCH = 208;                 // bytes of a staged position / weight row: 3 x 64 + 16 (52 dwords)
 constexpr int LH = 160;                    // staged positions of a group's 128 rows (host check)
@@ -43,22 +39,6 @@ struct x6p_tap {
   int P0, HpIn, offpos, C32;
   unsigned bytes;
 };
-
-__device__ __forceinline__ void lds_barrier() {
-  // LDS traffic of this wave done, then the block barrier; outstanding global loads keep flying
-  asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-}
-
-__device__ __forceinline__ void tile_of_block(int BM, int BN, int& m0, int& n0) {
-  const int tiles_n = gridDim.y, tiles_m = gridDim.x;
-  const int nblk = tiles_m * tiles_n;
-  int bid = blockIdx.y * tiles_m + blockIdx.x;
-  const int q = nblk >> 3, rem = nblk & 7, xcd = bid & 7, idx = bid >> 3;
-  bid = (xcd < rem ? xcd * (q + 1) : rem * (q + 1) + (xcd - rem) * q) + idx;
-  const int tm = bid / tiles_n, tn = bid - tm * tiles_n;
-  m0 = tm * BM;
-  n0 = tn * BN;
-}
 
 template <int TAPS>
 __global__ __launch_bounds__(512, 1) void gemm_x6p_kernel(const f2g_gemm_desc d, int M, int N, int K,
@@ -202,19 +182,6 @@ __global__ __launch_bounds__(512, 1) void gemm_x6p_kernel(const f2g_gemm_desc d,
 // windows -- was measured no faster than two free-running 128 x 128 blocks in round 5, 188 : 190 and 147 : 149
 // TFLOP/s equivalent, and removed in round 6.)
 
-// three bf16 pieces of four floats (common.h: f2g_split3_pair, round to nearest even at every step)
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void split3x4(const u32x4& v, u32x2& p0, u32x2& p1, u32x2& p2) {
-  // (by value first: __builtin_bit_cast applied to a vector-element expression reads element 0)
-  const unsigned u0 = v.x, u1 = v.y, u2 = v.z, u3 = v.w;
-  unsigned a0, a1, a2, b0, b1, b2;
-  f2g_split3_pair(__uint_as_float(u0), __uint_as_float(u1), a0, a1, a2);
-  f2g_split3_pair(__uint_as_float(u2), __uint_as_float(u3), b0, b1, b2);
-  p0 = u32x2{a0, b0};
-  p1 = u32x2{a1, b1};
-  p2 = u32x2{a2, b2};
-}
-
 // ---- tap-walking weight gradient of a stride-1 conv layer over halo maps (round 5) ----------------------
 // gw[co][t][ci] += sum_r g[r][co] * x[r + t - pad][ci]  (the 1024-channel MPD layer: t = 0..4; reference
 // discriminators.py:65-76 backward).  gemm_leanw6_kernel gives every (tap, 128 ci) column tile its own block:
@@ -225,16 +192,6 @@ __device__ __forceinline__ void split3x4(const u32x4& v, u32x2& p0, u32x2& p1, u
 // staged map rows by shifting the transposing fragment reads (ds_read_b64_tr_b16) one row down.  8 waves =
 // (co half) x (ci quarter), 2 x TAPS accumulator tiles each; 120 MFMAs per wave and slab behind 15 LDS stores
 // per thread (the old kernel: 48 behind 24).
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-__device__ __forceinline__ bf16x8 tr_frag(const unsigned char* p) {
-  typedef s16x4 __attribute__((address_space(3))) * lds_p;
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p + 4 * 256));
-  const s16x8 v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(bf16x8, v);
-}
-
 template <int TAPS>
 __global__ __launch_bounds__(512, 1) void gemm_leanw6t_kernel(const f2g_gemm_desc d, int K, int kchunk,
                                                               long long xrows) {
@@ -515,7 +472,7 @@ __global__ __launch_bounds__(512, 1) void gemm_leanw6s_kernel(const f2g_gemm_des
 
 }  // namespace
 
-// d: a precision-3 descriptor that passed gemm.hip's x6_tap_ok(d, taps) (stride-1 windows of `taps` positions
+// d: a precision-3 descriptor that passed gemm_x6.hip's x6_tap_ok(d, taps) (stride-1 windows of `taps` positions
 // over a halo-map image, <= 160 staged positions per 128 rows).  0 = not taken.
 int f2g_x6p_ok(const f2g_gemm_desc& d, int taps) {
   const int mode = f2g_opt(F2G_OPT_X6P);    // 0 off, 1 (default) chip-filling grids, 2 whatever the grid
@@ -530,19 +487,12 @@ int f2g_launch_x6p(const f2g_gemm_desc& d, int taps, long long a_extent, hipStre
   const int M = d.A.rows, N = d.B.rows, K = d.A.cols;
   constexpr size_t smem = (size_t)OPERA + 2 * OPERB;
   static_assert(8 * ESZ <= (int)smem, "epilogue patches fit under the main loop's buffers");
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x6p_kernel<5>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_x6p_kernel<2>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_done = true;
-  }
+  dyn_lds_once<gemm_x6p_kernel<5>, gemm_x6p_kernel<2>>((int)smem);
   x6p_tap R;
   R.P0 = d.A.P0, R.HpIn = (int)(d.A.seq_stride / d.A.unit), R.offpos = -d.A.pad0, R.C32 = d.A.unit / 32;
   R.bytes = (unsigned)(a_extent * 6);
   dim3 grid((M + 255) / 256, (N + 127) / 128);
-  f2g_note_kernel(taps == 5 ? "x6p<taps=5>" : "x6p<taps=2>", 1);
+  f2g_note_kernel(taps == 5 ? "x6p<taps=5>" : "x6p<taps=2>", 1, 4);
   if (taps == 5) hipLaunchKernelGGL(gemm_x6p_kernel<5>, grid, dim3(512), smem, st, d, M, N, K, R);
   else hipLaunchKernelGGL(gemm_x6p_kernel<2>, grid, dim3(512), smem, st, d, M, N, K, R);
   return f2g_check_launch();
@@ -573,12 +523,7 @@ int f2g_launch_leanw6t(const f2g_gemm_desc& d, int split, hipStream_t st) {
   constexpr int TAPS = 5;
   if (d.B.step0 == 3) {     // strided layer: whole sequences per block, slabs of 16 gradient rows
     constexpr size_t smem3 = (size_t)2 * (3 * 16 * 256 + 3 * (15 * 3 + TAPS) * 256);
-    static bool attr3 = false;
-    if (!attr3) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_leanw6s_kernel<5, 3>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3);
-      attr3 = true;
-    }
+    dyn_lds_once<gemm_leanw6s_kernel<5, 3>>((int)smem3);
     const int nseq = K / d.B.P0, tiles = (M / 128) * (Cin / 128);
     // blocks = tiles x sequence chunks: the chunk count whose block total fills rounds of 256 best
     int best = 1;
@@ -593,17 +538,12 @@ int f2g_launch_leanw6t(const f2g_gemm_desc& d, int split, hipStream_t st) {
     const int spb = (nseq + best - 1) / best, zs = (nseq + spb - 1) / spb;
     const long long xrows = (long long)nseq * (d.B.seq_stride / Cin);
     dim3 grid(M / 128, Cin / 128, zs);
-    f2g_note_kernel("leanw6s<step=3>", split);
+    f2g_note_kernel("leanw6s<step=3>", split, 4);
     hipLaunchKernelGGL((gemm_leanw6s_kernel<5, 3>), grid, dim3(512), smem3, st, d, nseq, spb, xrows);
     return f2g_check_launch();
   }
   constexpr size_t smem = (size_t)2 * (3 * 32 * 256 + 3 * (32 + TAPS - 1) * 256);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_leanw6t_kernel<5>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_done = true;
-  }
+  dyn_lds_once<gemm_leanw6t_kernel<5>>((int)smem);
   // one block per CU: split the rows so that tiles x chunks fill rounds of 256 blocks
   const int tiles = (M / 128) * (Cin / 128);
   int zs = split;
@@ -622,7 +562,7 @@ int f2g_launch_leanw6t(const f2g_gemm_desc& d, int split, hipStream_t st) {
   zs = (K + kchunk - 1) / kchunk;
   const long long xrows = (long long)(d.B.rows / d.B.P0) * d.B.P0;
   dim3 grid(M / 128, Cin / 128, zs);
-  f2g_note_kernel("leanw6t<step=1>", split);
+  f2g_note_kernel("leanw6t<step=1>", split, 4);
   hipLaunchKernelGGL(gemm_leanw6t_kernel<5>, grid, dim3(512), smem, st, d, K, kchunk, xrows);
   return f2g_check_launch();
 }

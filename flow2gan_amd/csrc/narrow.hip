@@ -260,7 +260,7 @@ int f2g_gemm_narrow(const f2g_gemm_desc& d, hipStream_t st) {
     if (N > 4 || !plainish(d.B) || M <= 0 || (size_t)N * ((K + 3) & ~3) * 4 > 60000) return 0;
     const size_t smem = (size_t)N * ((K + 3) & ~3) * sizeof(float);
     dim3 grid((M + 4 * ROWS_PER_WAVE - 1) / (4 * ROWS_PER_WAVE));
-    f2g_note_kernel(f1 ? "narrow_rows<form=1>" : "narrow_rows<form=0>", 1);
+    f2g_note_kernel(f1 ? "narrow_rows<form=1>" : "narrow_rows<form=0>", 1, 3);
     if (f1) hipLaunchKernelGGL(narrow_rows_kernel<true>, grid, dim3(256), smem, st, d, M, N, K);
     else hipLaunchKernelGGL(narrow_rows_kernel<false>, grid, dim3(256), smem, st, d, M, N, K);
     int rc = f2g_check_launch();
@@ -273,7 +273,7 @@ int f2g_gemm_narrow(const f2g_gemm_desc& d, hipStream_t st) {
     if (rows_per < 64) rows_per = 64;
     if (rows_per > 512) rows_per = 512;
     dim3 grid((R + rows_per - 1) / rows_per);
-    f2g_note_kernel((N & 3) == 0 && N <= 4096 ? (M == 1 ? "narrow_wgrad4<1>" : "narrow_wgrad4<4>") : "narrow_wgrad", 1);
+    f2g_note_kernel((N & 3) == 0 && N <= 4096 ? (M == 1 ? "narrow_wgrad4<1>" : "narrow_wgrad4<4>") : "narrow_wgrad", 1, 3);
     if ((N & 3) == 0 && N <= 4096 && M == 1)
       hipLaunchKernelGGL(narrow_wgrad4_kernel<1>, grid, dim3(256), 0, st, d, M, N, R, rows_per);
     else if ((N & 3) == 0 && N <= 4096)

@@ -1,4 +1,4 @@
-// Wide epilogue of the fp32-class (six-product) GEMM kernels (gemm.hip: gemm_x6 / x6t / x6f; gemm_x6p.hip).
+// Wide epilogue of the fp32-class (six-product) GEMM kernels (gemm_x6.hip: gemm_x6 / x6f / x6g; gemm_x6p.hip).
 //
 // The generic epilogue (gemm_epilogue) stores 4 bytes per lane and instruction straight from the MFMA
 // layout, behind one integer division per ELEMENT for the row map, and the result's three-piece image was

@@ -258,7 +258,7 @@ def x6_ok(ops, d):
 
 
 def expect(acc, mag, *, bias=None, res=None, gamma=None, aux=None, alpha_n=None, lrelu=0.0, scale=0.0, c0=None):
-    """the generic epilogue's arithmetic (gemm.hip: gemm_epilogue) in float64: (out, its scale, colsum, its
+    """the generic epilogue's arithmetic (gemm_common.h: gemm_epilogue) in float64: (out, its scale, colsum, its
     scale, colsum_alpha)"""
     s = scale if scale else 1.0
     v, m = acc * s, mag * abs(s)
@@ -303,7 +303,7 @@ def products(A, B, form, bf16, b=None, r0=0, r1=None):
     return a @ bt, a.abs() @ bt.abs()
 
 
-EPI = {   # epilogue instances of the lean kernel (selection: gemm.hip launch_lean, "epilogue instance")
+EPI = {   # epilogue instances of the lean kernel (selection: gemm_lean.hip f2g_launch_lean, "epilogue instance")
     0: dict(bias=True, res=True, lrelu=0.1),
     1: dict(bias=True, aux=True, colsum=True),
     2: dict(bias=True, colsum=True, lrelu=0.2, rowmap=True),
@@ -463,7 +463,7 @@ def test_lean_tall_rule(ops, lib_option):
 
 # ------------------------------------------------------------------ stream-K
 def stream_k_rule(M, N, K, mode, streamk, streamk_min):
-    """units per block, or 0 (gemm.hip: lean_stream_k; true bf16 operands count 64-element slabs)"""
+    """units per block, or 0 (gemm_lean.hip: f2g_lean_stream_k; true bf16 operands count 64-element slabs)"""
     if streamk == 0:
         return 0
     tiles = -(-M // 128) * -(-N // 128)
@@ -992,7 +992,7 @@ def test_fused_block_multi_tile_options(ops, rt384, rt512, lib_option):
 # ------------------------------------------------------------------ ledger
 def kernel_literals():
     """every kernel name f2g_gemm_last_kernel can report: the string literals handed to f2g_note_kernel (directly
-    or through the name tables of launch_lean / generic_name)"""
+    or through the name tables of f2g_launch_lean / generic_name)"""
     names = set()
     for fn in os.listdir(os.path.join(ROOT, "flow2gan_amd", "csrc")):
         if not fn.endswith((".hip", ".h")) or fn == "capi.hip":      # (capi.hip: the option table's names)

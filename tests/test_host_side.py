@@ -517,3 +517,26 @@ def test_weight_batch_levels_operations_by_their_data_dependencies():
               1 << 19, **one)
     assert time.perf_counter() - t0 < 0.5
     assert {o[0] for o in b.ops} == {0, 1}
+
+
+def test_makefile_builds_and_digests_every_source():
+    """csrc/Makefile: every .hip is in SRCS and exists, and every header is both a prerequisite of the objects and
+    part of the f2g_version() digest (its rule's prerequisites and its `cat`) -- a source left out of the digest
+    builds and runs, only counters recorded with one build could then be attributed to another"""
+    csrc = os.path.join(ROOT, "flow2gan_amd", "csrc")
+    mk = open(os.path.join(csrc, "Makefile")).read()
+    srcs = re.search(r"^SRCS\s*=\s*(.+)$", mk, re.M).group(1).split()
+    hips = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
+    headers = sorted(f for f in os.listdir(csrc) if f.endswith(".h") and f != "version_gen.h")
+    assert hips and headers
+    assert sorted(srcs) == hips, (sorted(set(hips) - set(srcs)), sorted(set(srcs) - set(hips)))
+    assert len(set(srcs)) == len(srcs), srcs
+    obj_prereqs = re.search(r"^%\.o:\s*(.+)$", mk, re.M).group(1).split()
+    digest = re.search(r"^version_gen\.h:\s*(.+)\n\t(.+)$", mk, re.M)
+    digest_prereqs = digest.group(1).split()
+    digest_cat = re.search(r"\(cat\s+([^;]+);", digest.group(2)).group(1).split()
+    for where, names in (("object rule", obj_prereqs), ("digest prerequisites", digest_prereqs),
+                         ("digest cat", digest_cat)):
+        missing = [h for h in headers if h not in names]
+        assert not missing, (where, missing)
+    assert "$(SRCS)" in digest_prereqs and "$(SRCS)" in digest_cat
