@@ -227,6 +227,7 @@ _SIGS = {
     "f2g_sadam_stats": [_P, _P, _I, _P, _I],
     "f2g_sadam_prepare": [_P, C.POINTER(SadamGroup), _P, _P, _P, _P],
     "f2g_lrelu_bwd_colsum": [_P, _P, _P, _F, _P, _F, _I, _I, _L, _P],
+    "f2g_lrelu_bwd_add": [_P, _P, _L, _I, _I, _I, _I, _L, _L, _L, _P, _L, _L, _L, _L, _F, _P],
     "f2g_zero_halo": [_P, _I, _I, _I, _I, _I],
     "f2g_sadam_update": [_P, _P, _I, _P],
     "f2g_mlp_pack": [_P, _P, _L, _P, _L, _I, _I],

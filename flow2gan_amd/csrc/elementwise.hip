@@ -573,6 +573,79 @@ __global__ __launch_bounds__(256) void lrelu_bwd_cs_kernel(float* g, const float
   }
 }
 
+// Leaky-ReLU backward of a channels-last map in place with a caller's gradient of the SAME map landed first,
+// g[pos, c] = (g[pos, c] + u[item, c, pos]) * lrelu'(y[pos, c]), (+ column sums of the result): the upstream u
+// arrives in the reference's (B, C, H, W) convention -- channel slow, a position axis fast -- with arbitrary
+// element strides.  A block walks `tiles_per` tiles of 32 positions x 32 channels of one item; positions are
+// q = slow * nf + fast over two position axes, each with its own stride on either side.
+// TILE (the upstream's fast position axis has stride 1): the 32 x 32 upstream tile is read position-fastest and
+// turned through LDS (row stride 33 words), so that both sides are coalesced; the channels-last side moves as
+// float4: thread = (float4 channel group c4, position).  !TILE: every thread gathers its four upstream values.
+template <bool TILE>
+__global__ __launch_bounds__(256) void lrelu_bwd_add_kernel(float* g, const float* y_act, int xb, int ns, int nf,
+                                                            int C, long long gs0, long long gs_s, long long gs_f,
+                                                            const float* u, long long us0, long long us_s,
+                                                            long long us_f, long long us_c, float slope,
+                                                            int tiles_per, float* colsum) {
+  __shared__ float tile[32][33];
+  __shared__ float4 red[256];
+  const int b = blockIdx.x / xb, xt = blockIdx.x - b * xb;
+  const int c0 = blockIdx.y * 32;
+  const int Q = ns * nf;
+  const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;  // upstream side: 32 positions x 8 channel rows
+  const int c4 = threadIdx.x & 7, pl = threadIdx.x >> 3;   // channels-last side: 8 float4 groups x 32 positions
+  const int c = c0 + 4 * c4;
+  const float* ub = u + (long long)b * us0;
+  float* gb = g + (long long)b * gs0;
+  const float* yb = y_act + (long long)b * gs0;
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int t = 0; t < tiles_per; ++t) {
+    const int q0 = (xt * tiles_per + t) * 32;
+    if (q0 >= Q) break;  // (uniform over the block)
+    if (TILE) {
+      __syncthreads();  // the previous tile has been consumed
+      const int q = q0 + tx;
+      const int qs = q / nf, qf = q - qs * nf;
+      const long long uo = (long long)qs * us_s + (long long)qf * us_f;
+#pragma unroll
+      for (int i = ty; i < 32; i += 8)
+        tile[i][tx] = (q < Q && c0 + i < C) ? ub[uo + (long long)(c0 + i) * us_c] : 0.f;
+      __syncthreads();
+    }
+    const int q = q0 + pl;
+    if (q < Q && c < C) {
+      const int qs = q / nf, qf = q - qs * nf;
+      float4 uv;
+      if (TILE) {
+        uv = make_float4(tile[4 * c4][pl], tile[4 * c4 + 1][pl], tile[4 * c4 + 2][pl], tile[4 * c4 + 3][pl]);
+      } else {
+        const float* up = ub + (long long)qs * us_s + (long long)qf * us_f + (long long)c * us_c;
+        uv = make_float4(up[0], up[us_c], up[2 * us_c], up[3 * us_c]);
+      }
+      const long long off = (long long)qs * gs_s + (long long)qf * gs_f + c;
+      const float4 y = *reinterpret_cast<const float4*>(yb + off);
+      float4 gv = *reinterpret_cast<const float4*>(gb + off);
+      gv.x = (gv.x + uv.x) * (y.x > 0.f ? 1.f : slope);
+      gv.y = (gv.y + uv.y) * (y.y > 0.f ? 1.f : slope);
+      gv.z = (gv.z + uv.z) * (y.z > 0.f ? 1.f : slope);
+      gv.w = (gv.w + uv.w) * (y.w > 0.f ? 1.f : slope);
+      *reinterpret_cast<float4*>(gb + off) = gv;
+      s.x += gv.x; s.y += gv.y; s.z += gv.z; s.w += gv.w;
+    }
+  }
+  if (!colsum) return;
+  red[threadIdx.x] = s;
+  __syncthreads();
+  if (pl == 0 && c < C) {
+    for (int i = 1; i < 32; ++i) {
+      const float4 r = red[(i << 3) + c4];
+      s.x += r.x; s.y += r.y; s.z += r.z; s.w += r.w;
+    }
+    atomicAdd(colsum + c, s.x); atomicAdd(colsum + c + 1, s.y);
+    atomicAdd(colsum + c + 2, s.z); atomicAdd(colsum + c + 3, s.w);
+  }
+}
+
 // rows [0, lo) and [rows_per_seq - hi, rows_per_seq) of every sequence := 0 (float4 lanes)
 __global__ __launch_bounds__(256) void zero_halo_kernel(float* buf, int nseq, int rows_per_seq,
                                                         int C4, int lo, int hi) {
@@ -607,6 +680,38 @@ extern "C" int f2g_lrelu_bwd_colsum(float* g, const float* y_act, const float* f
   dim3 grid((C4 + CS - 1) / CS, (rows + rows_per - 1) / rows_per);
   hipLaunchKernelGGL(lrelu_bwd_cs_kernel, grid, dim3(256), 0, ST, g, y_act, f_real, w, wdev, slope,
                      rows, C4, (long long)(ld / 4), rows_per, cs_log2, colsum);
+  return f2g_check_launch();
+}
+
+extern "C" int f2g_lrelu_bwd_add(float* g, const float* y_act, int64_t off, int32_t n0, int32_t n1, int32_t n2,
+                                 int32_t C, int64_t gs0, int64_t gs1, int64_t gs2, const float* u, int64_t us0,
+                                 int64_t us1, int64_t us2, int64_t usc, float slope, float* colsum,
+                                 f2g_stream_t stream) {
+  if (!g || !y_act || !u || (C & 3) || ((off | gs0 | gs1 | gs2) & 3)) return F2G_EINVAL;
+  if ((((uintptr_t)g) | ((uintptr_t)y_act)) & 15) return F2G_EINVAL;
+  if (n0 <= 0 || n1 <= 0 || n2 <= 0 || C <= 0) return F2G_OK;
+  if ((int64_t)n1 * n2 > 0x7fffffff - 64) return F2G_EINVAL;
+  // the kernel's fast position axis is the one the upstream is contiguous along (axis 2 when neither is)
+  const bool swap = us2 != 1 && us1 == 1;
+  const bool tile = swap || us2 == 1;
+  const int ns = swap ? n2 : n1, nf = swap ? n1 : n2;
+  const long long gs_s = swap ? gs2 : gs1, gs_f = swap ? gs1 : gs2;
+  const long long us_s = swap ? us2 : us1, us_f = swap ? us1 : us2;
+  const int nqt = (int)(((int64_t)ns * nf + 31) / 32), cty = (C + 31) / 32;
+  // up to 8 tiles (256 positions) per block and column-sum atomic, fewer while the grid is small
+  int tiles_per = 8;
+  while (tiles_per > 1 && (int64_t)n0 * ((nqt + tiles_per - 1) / tiles_per) * cty < 1024) tiles_per >>= 1;
+  const int xb = (nqt + tiles_per - 1) / tiles_per;
+  if ((int64_t)n0 * xb > 0x7fffffff) return F2G_EINVAL;
+  dim3 grid((unsigned)(n0 * xb), cty);
+  if (tile)
+    hipLaunchKernelGGL(lrelu_bwd_add_kernel<true>, grid, dim3(256), 0, ST, g + off, y_act + off, xb, ns, nf, C,
+                       (long long)gs0, gs_s, gs_f, u, (long long)us0, us_s, us_f, (long long)usc, slope, tiles_per,
+                       colsum);
+  else
+    hipLaunchKernelGGL(lrelu_bwd_add_kernel<false>, grid, dim3(256), 0, ST, g + off, y_act + off, xb, ns, nf, C,
+                       (long long)gs0, gs_s, gs_f, u, (long long)us0, us_s, us_f, (long long)usc, slope, tiles_per,
+                       colsum);
   return f2g_check_launch();
 }
 

@@ -2,9 +2,10 @@
 (reference flow2gan/models/discriminators.py).  Weight-norm is disabled in the reference
 (discriminators.py:13-15), so plain Conv2d parameters are what a checkpoint holds.
 
-Training runs through the fused loss nodes in flow2gan_amd/fused_disc.py; `forward(y, y_hat)`
-keeps the reference's return convention (scores / feature maps in (B, C, H, W)) for inspection
-and parity tests, computed on the same HIP kernels without autograd.
+GAN.forward trains through the fused loss nodes in flow2gan_amd/fused_disc.py.  `forward(y, y_hat)` keeps
+the reference's return convention (scores / feature maps in (B, C, H, W)) on the same HIP kernels WITH
+autograd (leaf.DiscPFn / DiscRFn): a loss the caller builds from the returned scores and maps gives
+gradients for the discriminator parameters and for the input audio.
 """
 from __future__ import annotations
 
@@ -15,7 +16,7 @@ from torch import nn
 from torch.nn import Conv2d
 
 from .. import fused_disc as FD
-from .. import ops
+from .. import leaf
 from .modules import _Window
 
 
@@ -45,22 +46,10 @@ class DiscriminatorP(nn.Module):
             p += [c.weight, c.bias]
         return p + [self.conv_post.weight, self.conv_post.bias]
 
-    @torch.no_grad()
     def forward(self, x: torch.Tensor, cond_embedding_id: Optional[torch.Tensor] = None):
         """x (B, T) -> (score (B, H*p), fmap list of (B, C, H, p))."""
         _no_embeddings(cond_embedding_id)
-        B = x.shape[0]
-        st = FD._mpd_forward_one(x.contiguous(), self.period, self._params())
-        p = self.period
-        fmap = []
-        for l in range(2, 6):
-            y = st["acts"][l]
-            H, Cc = st["hs"][l], y.shape[1]
-            fmap.append(FD.unhalo(y, B * p, H).reshape(B, p, H, Cc).permute(0, 3, 2, 1))
-        H5 = st["hs"][5]
-        sc = st["scores"].view(B, p, H5, 1).permute(0, 3, 2, 1)
-        fmap.append(sc)
-        return torch.flatten(sc, 1, -1), fmap
+        return leaf.discriminator_p_forward(self, x)
 
 
 def _no_embeddings(v) -> None:
@@ -131,26 +120,10 @@ class DiscriminatorR(nn.Module):
                 p += [c.weight, c.bias]
         return p + [self.conv_post.weight, self.conv_post.bias]
 
-    @torch.no_grad()
     def forward(self, x: torch.Tensor, cond_embedding_id: Optional[torch.Tensor] = None):
         """x (B, T) -> (score (B, 1, frames, freq), fmap list of (B, C, frames, freq))."""
         _no_embeddings(cond_embedding_id)
-        B = x.shape[0]
-        st = FD._mrd_forward_one(x.contiguous(), self.window_length, self._params())
-        Ft, Wcat, C = st["Ft"], st["Wcat"], FD.MRD_CH
-        cat = st["cat"].view(B, Ft, Wcat, C)
-        fmap = []
-        foff = 0
-        for bi in range(5):
-            ws = st["widths"][bi]
-            for l in range(1, 4):
-                y = st["acts"][bi][l]
-                fmap.append(y.view(B, Ft, ws[l + 1], C).permute(0, 3, 1, 2))
-            fmap.append(cat[:, :, foff:foff + ws[5]].permute(0, 3, 1, 2))
-            foff += ws[5]
-        sc = st["scores"].view(B, Ft, Wcat, 1).permute(0, 3, 1, 2)
-        fmap.append(sc)
-        return sc, fmap
+        return leaf.discriminator_r_forward(self, x)
 
 
 class MultiResolutionDiscriminator(_MultiD):

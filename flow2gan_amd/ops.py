@@ -1712,6 +1712,19 @@ def lrelu_bwd_colsum(g, y_act, f_real, w, slope, rows, Cc, ld, colsum, wdev=None
         call(*args)
 
 
+def lrelu_bwd_add(g, y_act, dims, g_strides, Cc, u, u_strides, slope, colsum=None, g_off=0):
+    """In place on the channels-last map g: g = (g + u) * lrelu'(y_act) (+ column sums of the result), u being
+    a gradient of the same map in the caller's layout.  dims = the three position extents; g_strides their float
+    strides in g / y_act (both start g_off floats in; channels contiguous); u_strides = u's element strides for
+    the three position axes and the channel -- any tensor autograd hands over (expanded, permuted) goes as it is."""
+    n0, n1, n2 = dims
+    gs0, gs1, gs2 = g_strides
+    us0, us1, us2, usc = u_strides
+    call("f2g_lrelu_bwd_add", ptr(g), ptr(y_act), g_off, n0, n1, n2, Cc, gs0, gs1, gs2,
+         ptr(u), us0, us1, us2, usc, float(slope), ptr(colsum))
+    return g
+
+
 def zeros_many(shapes, device):
     """Several zero-initialised tensors carved from ONE zeroed allocation (one fill launch instead
     of one per tensor); every piece starts on a 64-float boundary."""

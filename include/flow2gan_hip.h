@@ -456,6 +456,17 @@ int f2g_lrelu_bwd(float* g, const float* y_act, const float* f_real, float w, co
 int f2g_lrelu_bwd_colsum(float* g, const float* y_act, const float* f_real, float w,
                          const float* wdev, float slope, int32_t rows, int32_t C, int64_t ld,
                          float* colsum, f2g_stream_t stream);
+/* Leaky-ReLU backward in place on a channels-last map with a caller's gradient of that map landed first: the
+ * discriminators hand every feature map out in (B, C, H, W) (discriminators.py:92-96, 203-207), so the gradient of a
+ * loss built on one arrives channel-slow / position-fast while the maps live position-slow / channel-fast:
+ *   g[pos, c] = (g[pos, c] + u[pos, c]) * (y_act[pos, c] > 0 ? 1 : slope),  colsum[c] += sum_pos g[pos, c].
+ * g, y_act: element (i0, i1, i2, c) at off + i0*gs0 + i1*gs1 + i2*gs2 + c floats (C, off and the strides multiples
+ * of 4, both pointers 16-byte aligned; positions outside the three extents are never touched).  u: element at
+ * i0*us0 + i1*us1 + i2*us2 + c*usc, any strides (0 and negative included).  When us1 or us2 is 1 the upstream is
+ * turned through LDS tiles and both sides are coalesced; other patterns take a gather path.  colsum may be NULL. */
+int f2g_lrelu_bwd_add(float* g, const float* y_act, int64_t off, int32_t n0, int32_t n1, int32_t n2, int32_t C,
+                      int64_t gs0, int64_t gs1, int64_t gs2, const float* u, int64_t us0, int64_t us1,
+                      int64_t us2, int64_t usc, float slope, float* colsum, f2g_stream_t stream);
 /* Batched real FFT of STFT frames through LDS butterflies (fft.hip; modules.py:69-78 torch.stft,
  * modules.py:106-115 torch.istft) for n_fft = 64..4096 (power of two).  rows =
  * items * F frames; frame m of an item is the n_fft samples x[item*x_stride + m*hop + n] of the
