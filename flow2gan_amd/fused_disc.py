@@ -18,7 +18,7 @@ from typing import List
 import torch
 
 from . import ops
-from .fused import filterbank_spec, filterbank_spec_bwd
+from .fused import deliver_grads, filterbank_spec, filterbank_spec_bwd, sink_register
 from .models.modules import dft_matrices
 from .ops import gemm, mat, win1d, win2d
 
@@ -177,6 +177,146 @@ def _conv1d_dgrad(g_pre, S, Hout, Cout, w, stride, pad, Hin, mask=None, fm=None,
     return gx
 
 
+class MPDFusedLanding:
+    """Landing policy of the fused loss nodes.  Every data gradient applies the leaky-ReLU backward of the layer it
+    lands on (mask by that layer's activation, in the G-step plus the feature-matching term from the real half)
+    and leaves the column sums = the bias gradient of the conv that produced that layer -- in the producer's
+    epilogue or as a separate pass.  Sx sequences from sequence roff on take part in backward."""
+
+    def __init__(self, st, Sx: int, roff: int, g1, train_disc: bool):
+        self.acts, self.hs, self.Sx, self.roff, self.g1, self.train_disc = st["acts"], st["hs"], Sx, roff, g1, train_disc
+
+    def __call__(self, l_out, producer, cs):
+        y, Sx, g1 = self.acts[l_out], self.Sx, self.g1
+        Hp_, C_ = self.hs[l_out] + 2 * HALO, y.shape[1]
+        mk = (y, self.roff * Hp_ * C_, SLOPE)
+        fk = None
+        if (not self.train_disc) and l_out >= 2:     # fmaps: conv layers 1..4 (acts[2..5])
+            fk = (y, 0, 1.0 / (Sx * self.hs[l_out] * C_), g1)
+        # conv_post's data gradient (round 5): the stream kernel applies the mask / feature-matching term / bias
+        # sums itself and leaves the image the fp32-class data gradient of the 1024-channel layer reads next.
+        # (below it fused only in bf16x6 mode where the data gradient runs on the six-product kernel -- the
+        # 1024-channel layers, K >= 2048 --: that kernel has the generic epilogue anyway, and the
+        # image it leaves for the next data gradient must be of the final map.  Elsewhere the
+        # separate pass won: on the stage-2 step separate passes 257.5 ms, fused into every MPD
+        # epilogue 258.6 -- the HBM-bound pass overlaps with other lanes' MFMA work, while masking in
+        # the epilogue holds an MFMA wave's registers and LDS idle)
+        if l_out == 5 or (ops.GEMM_PRECISION == 3 and l_out in (3, 4)):
+            return producer(mk, fk, cs)
+        gm = producer(None, None, None)
+        gm._f2g_x3_bad = True      # (changed in place below: no producer-written image of it)
+        n_ = Sx * Hp_ * C_
+        if self.train_disc:
+            ops.lrelu_bwd_colsum(gm, y, None, 0.0, SLOPE, Sx * Hp_, C_, C_, cs, y_off=mk[1])
+        elif fk is not None:
+            ops.lrelu_bwd(gm, y, y, fk[2], SLOPE, 1, n_, n_, wdev=g1, y_off=mk[1], r_off=0)
+        else:
+            ops.lrelu_bwd(gm, y, None, 0.0, SLOPE, 1, n_, n_, y_off=mk[1])
+        return gm
+
+
+class MPDUpstreamLanding:
+    """Landing policy of the autograd node (leaf.DiscPFn): the data gradient is produced unfused, then one pass adds
+    the caller's gradient of the map it lands on (ups[l_out]: (B, C, H, p), any strides; None: no such gradient)
+    and applies that map's leaky-ReLU backward; the column sums are the bias gradient of conv layer l_out - 1."""
+
+    def __init__(self, st, B: int, ups: dict):
+        self.acts, self.hs, self.S, self.p, self.B, self.ups = st["acts"], st["hs"], st["S"], st["p"], B, ups
+
+    def __call__(self, l_out, producer, cs):
+        gm = producer(None, None, None)
+        gm._f2g_x3_bad = True      # (changed in place below: no producer-written image of it)
+        y, Hl, p = self.acts[l_out], self.hs[l_out], self.p
+        Hp_, C_ = Hl + 2 * HALO, y.shape[1]
+        u = self.ups.get(l_out)
+        if u is not None:
+            ub, uc, uh, uw = u.stride()                  # (B, C, H, p)
+            ops.lrelu_bwd_add(gm, y, (self.B, p, Hl), (p * Hp_ * C_, Hp_ * C_, C_), C_, u, (ub, uw, uh, uc),
+                              SLOPE, colsum=cs, g_off=HALO * C_)
+        elif cs is not None:
+            ops.lrelu_bwd_colsum(gm, y, None, 0.0, SLOPE, self.S * Hp_, C_, C_, cs)
+        else:
+            n_ = self.S * Hp_ * C_
+            ops.lrelu_bwd(gm, y, None, 0.0, SLOPE, 1, n_, n_)
+        return gm
+
+
+def _mpd_backward_one(st, prm: list, gs, seqs, need_w: bool, need_x: bool, land, top: int = 4):
+    """The backward walk of one period discriminator, shared by MPDLossFn and leaf.DiscPFn.
+    st: the state of _mpd_forward_one; prm: its 12 parameters; gs: gradient of the score map (S*H5, 1), or None
+    to start from zeros on acts[top + 1] (the layers above the highest map with a gradient get none);
+    seqs = (Sx, roff): the sequences whose data gradients are computed and the first of them (weight gradients
+    reduce over all S); land(l_out, producer, cs): the landing policy -- runs producer(mask, fm, colsum) -> the
+    gradient map landing on acts[l_out] and applies that map's leaky-ReLU backward, cs = the bias-gradient
+    accumulator of the conv that produced acts[l_out] (None without need_w).
+    Returns (gradient of the folded image (Sx*H0, 1) or None, the 12 parameter gradients)."""
+    acts, hs, S = st["acts"], st["hs"], st["S"]
+    Sx, roff = seqs
+    dev = acts[0].device
+    grads_p = [None] * 12
+    unpack = []     # (re-laid at the end of the period: ONE f2g_multi launch)
+    zbuf = None
+    if need_w:
+        # every weight / bias gradient accumulator of this sub-discriminator: one fill
+        zshapes = [(1, 3 * 1024), (1,)]
+        for l in range(5):
+            zshapes += [(MPD_CH[l + 1], 5 * MPD_CH[l]), (MPD_CH[l + 1],)]
+        zbuf = ops.zeros_many(zshapes, dev)
+
+    def bias_acc(l_out):
+        return zbuf[2 * l_out + 1] if need_w else None     # of the conv whose output is acts[l_out]
+
+    if gs is not None:
+        # conv_post (1024 -> 1, 3 taps, stride 1)
+        H5, wpost = hs[5], prm[10]
+        if need_w:
+            ops.mpdpost_wgrad(acts[5], S, H5, HALO, gs, zbuf[0])
+            unpack.append((10, zbuf[0], wpost.shape))
+            ops.colsum(zbuf[1], gs, S * H5, 1)
+            grads_p[11] = zbuf[1]
+        # (an image of the map is reserved only where the landing rides in the kernel: a separate pass changes the
+        # map in place before the next GEMM reads it)
+        g = land(5, lambda mk, fk, ck: ops.mpdpost_dgrad(
+            gs, Sx, H5, HALO, ops.derived(wpost, "pack", pack_conv_weight),
+            _halo_rows(Sx, H5, 1024, dev, x3=mk is not None), g_off=roff * H5, mask=mk, fm=fk, colsum=ck), bias_acc(5))
+        top = 4
+    else:
+        g = land(top + 1, lambda mk, fk, ck: ops.zeros(Sx * (hs[top + 1] + 2 * HALO), MPD_CH[top + 1], device=dev),
+                 bias_acc(top + 1))
+    for l in reversed(range(top + 1)):
+        w = prm[2 * l]
+        Cin, Cout, stv = MPD_CH[l], MPD_CH[l + 1], MPD_STRIDE[l]
+        Hin, Hout = hs[l], hs[l + 1]
+        Hp = Hout + 2 * HALO
+        # g: gradient of layer l's PRE-activation (S or Sx sequences, halo layout);
+        # (split-bf16 mode) one image of it serves the weight gradient and every stride
+        # residue of the data gradient, the forward image of acts[l] the weight gradient
+        with ops.split_sharing(g), (st["shares"][l] or ops.split_sharing()):
+            if need_w:
+                grads_p[2 * l + 1] = zbuf[2 + 2 * l + 1]
+                # reduction over ALL rows of the padded gradient map (its halo rows are 0, so
+                # the windows they pair with -- partly outside the input -- contribute nothing)
+                gwp = zbuf[2 + 2 * l]
+                if l == 0:
+                    ops.mpd0_wgrad(acts[0], S, Hin, Hout, HALO, g, gwp)
+                else:
+                    X = win1d(acts[l], S, Hin + 2 * HALO, Cin, Hp, stv, HALO * stv, 5,
+                              unbounded=True)   # g's halo rows are zero
+                    ops.wgrad(g, Cout, Cout, X, gwp)
+                unpack.append((2 * l, gwp, w.shape))
+            if l > 0:
+                g = land(l, lambda mk, fk, ck: _conv1d_dgrad(g, Sx, Hout, Cout, w, stv, 2, Hin, mask=mk, fm=fk,
+                                                             colsum=ck), bias_acc(l))
+            elif need_x:
+                gx0 = ops.empty(Sx * Hin, 1, device=dev)
+                g = ops.mpd0_dgrad(g, Sx, Hin, Hout, HALO, w.reshape(Cout, 5), gx0)
+    if need_w:
+        with ops.weight_batch():
+            for slot_, gwp_, shape_ in unpack:
+                grads_p[slot_] = unpack_conv_grad(gwp_, shape_)
+    return (g if need_x else None), grads_p
+
+
 class MPDLossFn(torch.autograd.Function):
     """(real, fake) -> (loss0, loss1): D-step (hinge_D, 0); G-step (hinge_G, feature matching)."""
 
@@ -215,7 +355,6 @@ class MPDLossFn(torch.autograd.Function):
         ctx.meta = (B, T, train_disc, tuple(periods))
         # D-step: each period discriminator's gradients are handed to an armed exchange as soon as
         # its launch lane has finished its backward (dist._Sink)
-        from .fused import sink_register
         ctx.tickets = [sink_register(list(params[12 * i: 12 * i + 12])) if train_disc else None
                        for i in range(len(periods))]
         return losses[0], losses[1]
@@ -234,119 +373,27 @@ class MPDLossFn(torch.autograd.Function):
           with lanes.lane(i):
             prm = list(params[12 * i: 12 * i + 12])
             st = ctx.saved[i]
-            acts, hs, sc, S = st["acts"], st["hs"], st["scores"], st["S"]
-            H5 = hs[5]
+            sc, S = st["scores"], st["S"]
+            H5 = st["hs"][5]
             nh = (S // 2) * H5
-            wpost = prm[10]
+            gs = ops.empty(S * H5, 1, device=dev)
             if train_disc:
-                gs = ops.empty(S * H5, 1, device=dev)
                 ops.hinge_loss(None, gs, sc, nh, -1.0, 1.0 / nh, wdev=g0)
                 ops.hinge_loss(None, gs, sc, nh, +1.0, 1.0 / nh, wdev=g0, s_off=nh)
                 Sx, roff = S, 0            # sequences taking part in backward, row offset (seqs)
-            else:
-                gs = ops.empty(S * H5, 1, device=dev)  # only the fake half is used
+            else:                          # only the fake half is used
                 ops.hinge_loss(None, gs, sc, nh, -1.0, 1.0 / nh, wdev=g0, s_off=nh)
                 ops.lrelu_bwd(gs, sc, sc, 1.0 / nh, 1.0, 1, nh, nh, wdev=g1, g_off=nh, y_off=nh,
                               r_off=0)
                 Sx, roff = S // 2, S // 2
-            grads_p = [None] * 12
-            # conv_post (1024 -> 1, 3 taps, stride 1)
-            y5 = acts[5]
-            if train_disc:
-                # every weight / bias gradient accumulator of this sub-discriminator: one fill
-                zshapes = [(1, 3 * 1024), (1,)]
-                for l in range(5):
-                    zshapes += [(MPD_CH[l + 1], 5 * MPD_CH[l]), (MPD_CH[l + 1],)]
-                zbuf = ops.zeros_many(zshapes, dev)
-                gwp = zbuf[0]
-                ops.mpdpost_wgrad(y5, S, H5, HALO, gs, gwp)
-                unpack = [(10, gwp, wpost.shape)]     # (re-laid at the end of the period: ONE f2g_multi launch)
-                gb = zbuf[1]
-                ops.colsum(gb, gs, S * H5, 1)
-                grads_p[11] = gb
-            # Every data gradient applies the leaky-ReLU backward of the layer it lands on in its own
-            # epilogue (mask by that layer's activation, in the G-step plus the feature-matching
-            # term) and leaves the column sums = the bias gradient of the conv that produced it:
-            # the maps are not re-read by a separate pass.
-            def below(l_out):
-                """(mask, fm, colsum) for a gradient that lands on acts[l_out] (l_out = 1..5)."""
-                y = acts[l_out]
-                Hp_, C_ = hs[l_out] + 2 * HALO, y.shape[1]
-                yo = roff * Hp_ * C_
-                fm_ = None
-                if (not train_disc) and l_out >= 2:     # fmaps: conv layers 1..4 (acts[2..5])
-                    fm_ = (y, 0, 1.0 / (Sx * hs[l_out] * C_), g1)
-                cs_ = zbuf[2 + 2 * (l_out - 1) + 1] if train_disc else None
-                return (y, yo, SLOPE), fm_, cs_
-
-            def land(gmap, l_out, producer):
-                """Run `producer(mask, fm, colsum)` -> gradient map landing on acts[l_out], with its
-                leaky-ReLU backward fused or as a separate pass."""
-                mk, fk, ck = below(l_out)
-                # (fused only in bf16x6 mode where the data gradient runs on the six-product kernel -- the
-                # 1024-channel layers, K >= 2048 --: that kernel has the generic epilogue anyway, and the
-                # image it leaves for the next data gradient must be of the final map.  Elsewhere the
-                # separate pass won: on the stage-2 step separate passes 257.5 ms, fused into every MPD
-                # epilogue 258.6 -- the HBM-bound pass overlaps with other lanes' MFMA work, while masking in
-                # the epilogue holds an MFMA wave's registers and LDS idle)
-                if ops.GEMM_PRECISION == 3 and l_out in (3, 4):
-                    return producer(mk, fk, ck)
-                gm = producer(None, None, None)
-                gm._f2g_x3_bad = True      # (changed in place below: no producer-written image of it)
-                y = acts[l_out]
-                Hp_, C_ = hs[l_out] + 2 * HALO, y.shape[1]
-                n_ = Sx * Hp_ * C_
-                if train_disc:
-                    ops.lrelu_bwd_colsum(gm, y, None, 0.0, SLOPE, Sx * Hp_, C_, C_, ck, y_off=mk[1])
-                elif fk is not None:
-                    ops.lrelu_bwd(gm, y, y, fk[2], SLOPE, 1, n_, n_, wdev=g1, y_off=mk[1], r_off=0)
-                else:
-                    ops.lrelu_bwd(gm, y, None, 0.0, SLOPE, 1, n_, n_, y_off=mk[1])
-                return gm
-
-            # conv_post's data gradient (round 5): the stream kernel applies the mask / feature-matching term /
-            # bias sums itself and leaves the image the fp32-class data gradient of the 1024-channel layer reads next
-            mk, fk, ck = below(5)
-            g = ops.mpdpost_dgrad(gs, Sx, H5, HALO, ops.derived(wpost, "pack", pack_conv_weight),
-                                  _halo_rows(Sx, H5, 1024, dev, x3=True), g_off=roff * H5, mask=mk, fm=fk, colsum=ck)
-            for l in reversed(range(5)):
-                w = prm[2 * l]
-                Cin, Cout, stv = MPD_CH[l], MPD_CH[l + 1], MPD_STRIDE[l]
-                Hin, Hout = hs[l], hs[l + 1]
-                Hp = Hout + 2 * HALO
-                # g: gradient of layer l's PRE-activation (S or Sx sequences, halo layout);
-                # (split-bf16 mode) one image of it serves the weight gradient and every stride
-                # residue of the data gradient, the forward image of acts[l] the weight gradient
-                with ops.split_sharing(g), (st["shares"][l] or ops.split_sharing()):
-                    if train_disc:
-                        grads_p[2 * l + 1] = zbuf[2 + 2 * l + 1]
-                        # reduction over ALL rows of the padded gradient map (its halo rows are 0, so
-                        # the windows they pair with -- partly outside the input -- contribute nothing)
-                        gwp = zbuf[2 + 2 * l]
-                        if l == 0:
-                            ops.mpd0_wgrad(acts[0], S, Hin, Hout, HALO, g, gwp)
-                        else:
-                            X = win1d(acts[l], S, Hin + 2 * HALO, Cin, Hp, stv, HALO * stv, 5,
-                                      unbounded=True)   # g's halo rows are zero
-                            ops.wgrad(g, Cout, Cout, X, gwp)
-                        unpack.append((2 * l, gwp, w.shape))
-                    if l > 0:
-                        g = land(None, l, lambda mk, fk, ck, g=g, w=w, Hout=Hout, Cout=Cout, stv=stv, Hin=Hin:
-                                 _conv1d_dgrad(g, Sx, Hout, Cout, w, stv, 2, Hin, mask=mk, fm=fk, colsum=ck))
-                    elif not train_disc:
-                        gx0 = ops.empty(Sx * Hin, 1, device=dev)
-                        g = ops.mpd0_dgrad(g, Sx, Hin, Hout, HALO, w.reshape(Cout, 5), gx0)
+            g, grads_p = _mpd_backward_one(st, prm, gs, (Sx, roff), train_disc, not train_disc,
+                                           MPDFusedLanding(st, Sx, roff, g1, train_disc))
             if not train_disc:
                 # g: (B*p*H0, 1) gradient of the folded image of the generated half
                 lanes.chain_enter()  # g_fake is accumulated period after period
-                ops.period_fold_bwd(g_fake, g, B, T, p, hs[0], True)
+                ops.period_fold_bwd(g_fake, g, B, T, p, st["hs"][0], True)
                 lanes.chain_leave()
-            if train_disc:
-                with ops.weight_batch():
-                    for slot_, gwp_, shape_ in unpack:
-                        grads_p[slot_] = unpack_conv_grad(gwp_, shape_)
-            from .fused import deliver_grads
-            pgrads += deliver_grads(ctx.tickets[i], list(params[12 * i: 12 * i + 12]), grads_p)
+            pgrads += deliver_grads(ctx.tickets[i], prm, grads_p)
         lanes.join()
         ctx.saved = None
         return tuple([None, g_fake, None, None] + pgrads)
@@ -524,6 +571,248 @@ def _conv2d_dgrad(g_pre, S, H, Wout, Cout, w, sw, Win, gx, *, g_line=None, g_seq
     return gx
 
 
+def _mrd_foffs(st) -> list:
+    """First column of every band's layer-4 map in the concatenated map."""
+    foffs, foff = [], 0
+    for ws in st["widths"]:
+        foffs.append(foff)
+        foff += ws[5]
+    return foffs
+
+
+class MRDFusedLanding:
+    """Landing policy of the fused loss nodes: the gradient that lands on a band map gets that map's leaky-ReLU
+    backward (+ feature matching against the real half for the maps the reference lists, band layers 1..4) and
+    leaves the bias-gradient column sums, in the producer's epilogue or as a separate pass.  Sx sequences from
+    sequence soff on take part in backward."""
+    fused = True     # the walk keeps the loss nodes' launch order (see _mrd_backward_one)
+
+    def __init__(self, st, Sx: int, soff: int, g1, train_disc: bool):
+        self.st, self.Sx, self.soff, self.g1, self.train_disc = st, Sx, soff, g1, train_disc
+        self.foffs = _mrd_foffs(st)
+
+    def __call__(self, bi, l_out, producer, cs):
+        st, Sx, soff, g1, train_disc = self.st, self.Sx, self.soff, self.g1, self.train_disc
+        Ft, C = st["Ft"], MRD_CH
+        Wl = st["widths"][bi][l_out + 1]
+        if l_out == 4:
+            # layer 4's output is a strided slice of cat / gcat; its bias sums are taken by the walk
+            gcat, cat, ldc, foff = producer(None, None, None), st["cat"], st["Wcat"] * C, self.foffs[bi]
+            y_off = soff * Ft * ldc + foff * C
+            if train_disc:
+                ops.lrelu_bwd(gcat, cat, None, 0.0, SLOPE, Sx * Ft, Wl * C, ldc, g_off=foff * C, y_off=y_off)
+            else:
+                ops.lrelu_bwd(gcat, cat, cat, 1.0 / (Sx * Ft * Wl * C), SLOPE, Sx * Ft, Wl * C, ldc,
+                              wdev=g1, g_off=foff * C, y_off=y_off, r_off=foff * C)
+            return gcat
+        yb = st["acts"][bi][l_out]
+        nb_ = Sx * Ft * Wl * C
+        mk = (yb, soff * Ft * Wl * C, SLOPE)
+        fmk = (yb, 0, 1.0 / nb_, g1) if ((not train_disc) and l_out >= 1) else None
+        # (round 5) D-step on the direct fp32-class kernels: their data gradients request the
+        # mask of a tile BEFORE its MFMAs, so the fused leaky-ReLU backward (+ bias-gradient
+        # column sums) costs no exposed round trip and saves a pass over the map
+        if (train_disc and ops.GEMM_PRECISION == 3 and ops.CONV32_X6
+                and (l_out < 3 or Wl <= ops.CONV33_MAX_W)):
+            return producer(mk, fmk, cs)
+        gx = producer(None, None, None)
+        if train_disc:
+            ops.lrelu_bwd_colsum(gx, yb, None, 0.0, SLOPE, Sx * Ft * Wl, C, C, cs, y_off=mk[1])
+        elif fmk is not None:
+            ops.lrelu_bwd(gx, yb, yb, fmk[2], SLOPE, 1, nb_, nb_, wdev=g1, y_off=mk[1], r_off=0)
+        else:
+            ops.lrelu_bwd(gx, yb, None, 0.0, SLOPE, 1, nb_, nb_, y_off=mk[1])
+        return gx
+
+
+class MRDUpstreamLanding:
+    """Landing policy of the autograd node (leaf.DiscRFn): the data gradient is produced unfused, then one pass adds
+    the caller's gradient of the map it lands on (g_maps[4 * bi + l_out - 1]: (B, C, Ft, W), any strides; None: no
+    such gradient) and applies that map's leaky-ReLU backward; the column sums are the bias gradient of layer l_out."""
+    fused = False
+
+    def __init__(self, st, S: int, g_maps):
+        self.st, self.S, self.g_maps = st, S, g_maps
+        self.foffs = _mrd_foffs(st)
+
+    def __call__(self, bi, l_out, producer, cs):
+        st, S = self.st, self.S
+        Ft, C = st["Ft"], MRD_CH
+        Wl = st["widths"][bi][l_out + 1]
+        gm = producer(None, None, None)
+        u = self.g_maps[4 * bi + l_out - 1] if l_out >= 1 else None
+        if l_out == 4:     # layer 4's output is a strided slice of cat / gcat
+            y, line, off = st["cat"], st["Wcat"] * C, self.foffs[bi] * C
+        else:
+            y, line, off = st["acts"][bi][l_out], Wl * C, 0
+        if u is not None:
+            ub, uc, uf, uw = u.stride()                  # (B, C, Ft, W)
+            ops.lrelu_bwd_add(gm, y, (S, Ft, Wl), (Ft * line, line, C), C, u, (ub, uf, uw, uc), SLOPE,
+                              colsum=cs, g_off=off)
+        elif l_out == 4:
+            ops.lrelu_bwd(gm, y, None, 0.0, SLOPE, S * Ft, Wl * C, line, g_off=off, y_off=off)
+            if cs is not None:
+                ops.colsum_strided(cs, gm, S * Ft, Wl, C, line, off)
+        elif cs is not None:
+            ops.lrelu_bwd_colsum(gm, y, None, 0.0, SLOPE, S * Ft * Wl, C, C, cs)
+        else:
+            nb_ = S * Ft * Wl * C
+            ops.lrelu_bwd(gm, y, None, 0.0, SLOPE, 1, nb_, nb_)
+        return gm
+
+
+def _mrd_backward_one(st, prm: list, x, win: int, gs, seqs, need_w: bool, need_x: bool, land, tops=None):
+    """The backward walk of one STFT-band discriminator, shared by MRDLossFn and leaf.DiscRFn.
+    st: the state of _mrd_forward_one over the audio x (S, T) at window `win`; prm: its 52 parameters; gs: gradient
+    of the score map (S*Ft*Wcat, 1), or None with tops[bi] = the highest layer of band bi whose output has a
+    gradient (None: the band has none; the layers above get none); seqs = (Sx, soff): the sequences whose data
+    gradients are computed and the first of them (weight gradients reduce over all S); land(bi, l_out, producer,
+    cs): the landing policy -- runs producer(mask, fm, colsum) -> the gradient map landing on the output of band
+    layer l_out and applies that map's leaky-ReLU backward, cs = the bias-gradient accumulator of that layer
+    (None without need_w).  The fused nodes' launch order is fixed, and where the two callers' bookkeeping
+    differs `land.fused` keeps each one's own: conv_post's two accumulators (two fills / one), and layer 4's bias
+    sums (after its weight gradient / at landing time, where the upstream pass already produces them).
+    Returns (gradient of x's rows soff .. soff + Sx or None, the 52 parameter gradients)."""
+    Ft, Wcat, nb, ldp, hop = st["Ft"], st["Wcat"], st["nb"], st["ldp"], st["hop"]
+    cat, packed = st["cat"], st["packed"]
+    S, T = x.shape
+    Sx, soff = seqs
+    dev = cat.device
+    C = MRD_CH
+    direct = ops.GEMM_PRECISION in (0, 1, 3)
+    grads_w = [None] * N_MRD_PARAMS
+    unpack = []     # (re-laid at the end of the window: ONE f2g_multi launch)
+    gcat = None
+    if gs is not None:
+        wpost = prm[50]
+        if need_w:
+            if land.fused:
+                gwp = ops.zeros(1, 9 * C, device=dev)
+            else:
+                gwp, gb = ops.zeros_many([(1, 9 * C), (1,)], dev)
+            if direct:
+                ops.convpost_wgrad(cat, S, Ft, Wcat, gs, gwp)
+            else:
+                ops.wgrad(gs, 1, 1, win2d(cat, S, Ft, Wcat, C, Wcat, 3, 3, 1, 1, 1), gwp)
+            unpack.append((50, gwp, wpost.shape))
+            if land.fused:
+                gb = ops.zeros(1, device=dev)
+            ops.colsum(gb, gs, S * Ft * Wcat, 1)
+            grads_w[51] = gb
+        # gradient of the concatenated layer-4 maps (only the sequences in backward)
+        gcat = ops.empty(Sx * Ft * Wcat, C, device=dev)
+        if direct:
+            ops.convpost_dgrad(gs, Sx, Ft, Wcat, ops.derived(wpost, "pack", pack_conv_weight),
+                               gcat, g_off=soff * Ft * Wcat)
+        else:
+            _conv2d_dgrad(gs, Sx, Ft, Wcat, 1, wpost, 1, Wcat, gcat, g_off=soff * Ft * Wcat)
+        tops = [4] * len(st["bands"])
+    elif 4 in tops:
+        gcat = ops.zeros(Sx * Ft * Wcat, C, device=dev)
+    g_packed = None
+    if need_x:
+        # (a band without any gradient writes nothing: its bins stay zero)
+        g_packed = ops.empty(Sx * Ft, ldp, device=dev) if gs is not None else ops.zeros(Sx * Ft, ldp, device=dev)
+    ldc = Wcat * C
+    foffs = _mrd_foffs(st)
+
+    def accumulators():   # every accumulator of a band's five layers from one zeroed allocation
+        return ops.zeros_many([(C,)] * 5 + [(C, 3 * kw_ * (2 if l_ == 0 else C))
+                                            for l_, (kw_, _sw) in enumerate(MRD_LAYERS)], dev)
+
+    for bi, (lo, hi) in enumerate(st["bands"]):
+        foff, ws, top = foffs[bi], st["widths"][bi], tops[bi]
+        if top is None:
+            continue
+        W4 = ws[5]
+        gbs = [None] * 5
+        if need_w and not land.fused:
+            zs = accumulators()
+            gbs, gwps = zs[:5], zs[5:]
+        g = None
+        if top == 4:
+            land(bi, 4, lambda mk, fk, ck: gcat, gbs[4])
+        else:
+            g = land(bi, top, lambda mk, fk, ck: ops.zeros(Sx * Ft * ws[top + 1], C, device=dev), gbs[top])
+        if need_w and land.fused:
+            zs = accumulators()
+            gbs, gwps = zs[:5], zs[5:]
+        for l in reversed(range(top + 1)):
+            kw, sw = MRD_LAYERS[l]
+            w = prm[(bi * 5 + l) * 2]
+            Cin = 2 if l == 0 else C
+            Win, Wout = ws[l], ws[l + 1]
+            # (for l < 4, g already is the gradient of layer l's PRE-activation: the landing of the data
+            # gradient that produced it applied this layer's leaky-ReLU backward)
+            # operands describing this layer's pre-activation gradient image
+            if l == 4:
+                dy_line, dy_seq, dy_off, dy_t = ldc, Ft * ldc, foff * C, gcat
+            else:
+                dy_line, dy_seq, dy_off, dy_t = None, None, 0, g
+            if need_w:
+                x_in = packed if l == 0 else st["acts"][bi][l - 1]
+                if l == 0:
+                    X = win2d(x_in, S, Ft, Win, Cin, Wout, 3, kw, sw, 1, kw // 2,
+                              line_stride=ldp, seq_stride=Ft * ldp, offset=lo * 2)
+                else:
+                    X = win2d(x_in, S, Ft, Win, Cin, Wout, 3, kw, sw, 1, kw // 2)
+                gwp = gwps[l]
+                if l == 4:
+                    dY = win1d(gcat, S * Ft, Wcat, C, W4, 1, -foff, 1)
+                else:
+                    dY = mat(g, S * Ft * Wout, C)
+                tiles = ((3 * kw * Cin + 255) // 256)
+                if l == 0 and direct:
+                    ops.conv2ch_wgrad(packed, Ft * ldp, ldp, lo * 2, S, Ft, Win, g, gwp)
+                elif l in (1, 2, 3) and direct:
+                    ops.conv32_s2_wgrad(x_in, g, S, Ft, Win, Wout, gwp)
+                elif (l == 4 and ops.GEMM_PRECISION == 3
+                      and Wout <= ops.CONV33_MAX_W):
+                    # (round 6) the (3, 3) layer's weight gradient as a direct fp32-class kernel over the
+                    # band's slice of the concatenated gradient map (31 TFLOP/s as an implicit GEMM)
+                    ops.conv33_wgrad(x_in, gcat, S, Ft, Wout, gwp, g_off=foff * C, g_line=ldc, g_seq=Ft * ldc)
+                else:
+                    gemm(dY, X, gwp, form=2, atomic=True,
+                         split_k=ops.split_for(X.rows, tiles))
+                unpack.append(((bi * 5 + l) * 2, gwp, w.shape))
+                if l == 4 and land.fused:
+                    ops.colsum_strided(gbs[4], gcat, S * Ft, W4, C, ldc, foff * C)
+                grads_w[(bi * 5 + l) * 2 + 1] = gbs[l]
+            if l > 0:
+                # lands on acts[bi][l-1]
+                gx = ops.empty(Sx * Ft * Win, Cin, device=dev)
+                g = land(bi, l - 1, lambda mk, fk, ck: _conv2d_dgrad(
+                    dy_t, Sx, Ft, Wout, C, w, sw, Win, gx, g_line=dy_line, g_seq=dy_seq, g_off=dy_off,
+                    mask=mk, fm=fk, colsum=ck), gbs[l - 1])
+            elif need_x and direct:
+                def build_c2t(t):
+                    out = ops.empty(27, 2, C, device=t.device)   # [tap][ci][co]
+                    ops.permute4(out, t, (27, 2, C, 1), (1, 27, 2 * 27, 0))
+                    return out
+                ops.conv2ch_dgrad(g, Sx, Ft, Win, ops.derived(w, "c2t", build_c2t), g_packed,
+                                  Ft * ldp, ldp, lo * 2)
+            elif need_x:
+                _conv2d_dgrad(dy_t, Sx, Ft, Wout, C, w, sw, Win, g_packed, g_line=dy_line,
+                              g_seq=dy_seq, g_off=dy_off, x_line=ldp, x_off=lo * 2)
+    g_x = None
+    if need_x:
+        # the packed spectrogram's gradient back to audio: STFT adjoint, overlap-add, peak normalisation
+        gfr = ops.empty(Sx * Ft, win, device=dev)
+        if ops.fft_applies(win):
+            ops.stft_fft_adjoint(g_packed, win, Ft, gfr, interleaved=True)
+        else:
+            gemm(mat(g_packed, Sx * Ft, 2 * nb), mat(dft_interleaved(win, dev)), gfr, form=1)
+        gxn = ops.empty(Sx, T, device=dev)
+        ops.frames_fold(gfr, gxn, Sx, Ft, win, hop, T, False)
+        g_x = ops.empty(Sx, T, device=dev)
+        ops.peaknorm_bwd(g_x, gxn, x, st["stats"], Sx, T, row_off=soff)
+    if need_w:
+        with ops.weight_batch():
+            for slot_, gwp_, shape_ in unpack:
+                grads_w[slot_] = unpack_conv_grad(gwp_, shape_)
+    return g_x, grads_w
+
+
 class MRDLossFn(torch.autograd.Function):
     """(real, fake) -> (loss0, loss1) as MPDLossFn, for the STFT-band discriminators."""
 
@@ -582,18 +871,15 @@ class MRDLossFn(torch.autograd.Function):
         g1 = g1.reshape(1).contiguous()
         pgrads: List = []
         g_fake = None if train_disc else ops.zeros(B, T, device=dev)
-        C = MRD_CH
         lanes = ops.Lanes(dev, len(fft_sizes), "mrd")
         for i, win in enumerate(fft_sizes):
           with lanes.lane(i):
             prm = list(params[N_MRD_PARAMS * i: N_MRD_PARAMS * (i + 1)])
             st = ctx.saved[i]
-            Ft, Wcat, nb, ldp, hop = st["Ft"], st["Wcat"], st["nb"], st["ldp"], st["hop"]
-            sc, cat, packed = st["scores"], st["cat"], st["packed"]
+            sc = st["scores"]
             S = 2 * B
-            nh = B * Ft * Wcat
-            grads_w = [None] * N_MRD_PARAMS
-            gs = ops.empty(S * Ft * Wcat, 1, device=dev)
+            nh = B * st["Ft"] * st["Wcat"]
+            gs = ops.empty(S * st["Ft"] * st["Wcat"], 1, device=dev)
             if train_disc:
                 ops.hinge_loss(None, gs, sc, nh, -1.0, 1.0 / nh, wdev=g0)
                 ops.hinge_loss(None, gs, sc, nh, +1.0, 1.0 / nh, wdev=g0, s_off=nh)
@@ -602,169 +888,17 @@ class MRDLossFn(torch.autograd.Function):
                 ops.hinge_loss(None, gs, sc, nh, -1.0, 1.0 / nh, wdev=g0, s_off=nh)
                 ops.lrelu_bwd(gs, sc, sc, 1.0 / nh, 1.0, 1, nh, nh, wdev=g1, g_off=nh, y_off=nh,
                               r_off=0)
-                Sx, soff = B, B   # sequences in backward, first sequence
-            wpost = prm[50]
-            if train_disc:
-                gwp = ops.zeros(1, 9 * C, device=dev)
-                if ops.GEMM_PRECISION in (0, 1, 3):
-                    ops.convpost_wgrad(cat, S, Ft, Wcat, gs, gwp)
-                else:
-                    ops.wgrad(gs, 1, 1, win2d(cat, S, Ft, Wcat, C, Wcat, 3, 3, 1, 1, 1), gwp)
-                unpack = [(50, gwp, wpost.shape)]     # (re-laid at the end of the window: ONE f2g_multi launch)
-                gb = ops.zeros(1, device=dev)
-                ops.colsum(gb, gs, S * Ft * Wcat, 1)
-                grads_w[51] = gb
-            # gradient of the concatenated layer-4 maps (only the sequences in backward)
-            gcat = ops.empty(Sx * Ft * Wcat, C, device=dev)
-            if ops.GEMM_PRECISION in (0, 1, 3):
-                ops.convpost_dgrad(gs, Sx, Ft, Wcat, ops.derived(wpost, "pack", pack_conv_weight),
-                                   gcat, g_off=soff * Ft * Wcat)
-            else:
-                _conv2d_dgrad(gs, Sx, Ft, Wcat, 1, wpost, 1, Wcat, gcat, g_off=soff * Ft * Wcat)
-            g_packed = None
+                Sx, soff = B, B   # sequences in backward, first sequence (x2 = [real; fake])
+            gx2, grads_w = _mrd_backward_one(st, prm, ctx.x2, win, gs, (Sx, soff), train_disc, not train_disc,
+                                             MRDFusedLanding(st, Sx, soff, g1, train_disc))
             if not train_disc:
-                g_packed = ops.empty(B * Ft, ldp, device=dev)
-            ldc = Wcat * C
-            foffs, foff = [], 0
-            for bi in range(len(st["bands"])):
-                foffs.append(foff)
-                foff += st["widths"][bi][5]
-            for bi, (lo, hi) in enumerate(st["bands"]):
-                foff = foffs[bi]
-                ws = st["widths"][bi]
-                # ---- layer 4 (its output is a strided slice of cat / gcat)
-                W4 = ws[5]
-                cols = W4 * C
-                y_off = soff * Ft * ldc + foff * C
-                if train_disc:
-                    ops.lrelu_bwd(gcat, cat, None, 0.0, SLOPE, Sx * Ft, cols, ldc, g_off=foff * C,
-                                  y_off=y_off)
-                else:
-                    ops.lrelu_bwd(gcat, cat, cat, 1.0 / (B * Ft * cols), SLOPE, Sx * Ft, cols, ldc,
-                                  wdev=g1, g_off=foff * C, y_off=y_off, r_off=foff * C)
-                g = None
-                # bias-gradient accumulators of the band (layers 0..3 get theirs as column sums from
-                # the data-gradient epilogue that lands on their output)
-                if train_disc:   # every accumulator of the band's five layers from one zeroed allocation
-                    zs = ops.zeros_many([(C,)] * 5 + [(C, 3 * kw_ * (2 if l_ == 0 else C))
-                                                      for l_, (kw_, _sw) in enumerate(MRD_LAYERS)], dev)
-                    gbs, gb4, gwps = zs[:4], zs[4], zs[5:]
-                else:
-                    gbs = [None] * 4
-                for l in reversed(range(5)):
-                    kw, sw = MRD_LAYERS[l]
-                    w = prm[(bi * 5 + l) * 2]
-                    Cin = 2 if l == 0 else C
-                    Win, Wout = ws[l], ws[l + 1]
-                    # (for l < 4, g already is the gradient of layer l's PRE-activation: the data
-                    # gradient that produced it applied this layer's leaky-ReLU backward)
-                    # operands describing this layer's pre-activation gradient image
-                    if l == 4:
-                        dy_line, dy_seq, dy_off, dy_t = ldc, Ft * ldc, foff * C, gcat
-                    else:
-                        dy_line, dy_seq, dy_off, dy_t = None, None, 0, g
-                    if train_disc:
-                        x_in = packed if l == 0 else st["acts"][bi][l - 1]
-                        if l == 0:
-                            X = win2d(x_in, S, Ft, Win, Cin, Wout, 3, kw, sw, 1, kw // 2,
-                                      line_stride=ldp, seq_stride=Ft * ldp, offset=lo * 2)
-                        else:
-                            X = win2d(x_in, S, Ft, Win, Cin, Wout, 3, kw, sw, 1, kw // 2)
-                        gwp = gwps[l]
-                        if l == 4:
-                            dY = win1d(gcat, S * Ft, Wcat, C, W4, 1, -foff, 1)
-                        else:
-                            dY = mat(g, S * Ft * Wout, C)
-                        tiles = ((3 * kw * Cin + 255) // 256)
-                        if l == 0 and ops.GEMM_PRECISION in (0, 1, 3):
-                            ops.conv2ch_wgrad(packed, Ft * ldp, ldp, lo * 2, S, Ft, Win, g, gwp)
-                        elif l in (1, 2, 3) and ops.GEMM_PRECISION in (0, 1, 3):
-                            ops.conv32_s2_wgrad(x_in, g, S, Ft, Win, Wout, gwp)
-                        elif (l == 4 and ops.GEMM_PRECISION == 3
-                              and Wout <= ops.CONV33_MAX_W):
-                            # (round 6) the (3, 3) layer's weight gradient as a direct fp32-class kernel over the
-                            # band's slice of the concatenated gradient map (31 TFLOP/s as an implicit GEMM)
-                            ops.conv33_wgrad(x_in, gcat, S, Ft, Wout, gwp, g_off=foff * C, g_line=ldc, g_seq=Ft * ldc)
-                        else:
-                            gemm(dY, X, gwp, form=2, atomic=True,
-                                 split_k=ops.split_for(X.rows, tiles))
-                        unpack.append(((bi * 5 + l) * 2, gwp, w.shape))
-                        if l == 4:
-                            gb = gb4
-                            _colsum_strided(gb, gcat, S * Ft, W4, C, ldc, foff * C)
-                        else:
-                            gb = gbs[l]
-                        grads_w[(bi * 5 + l) * 2 + 1] = gb
-                    if l > 0:
-                        # lands on acts[bi][l-1]: its leaky-ReLU backward (+ feature matching for the
-                        # maps the reference lists, band layers 1..4) rides in this epilogue
-                        yb = st["acts"][bi][l - 1]
-                        nb_ = Sx * Ft * Win * C
-                        mk = (yb, soff * Ft * Win * C, SLOPE)
-                        fmk = (yb, 0, 1.0 / nb_, g1) if ((not train_disc) and l - 1 >= 1) else None
-                        gx = ops.empty(Sx * Ft * Win, Cin, device=dev)
-                        # (round 5) D-step on the direct fp32-class kernels: their data gradients request the
-                        # mask of a tile BEFORE its MFMAs, so the fused leaky-ReLU backward (+ bias-gradient
-                        # column sums) costs no exposed round trip and saves a pass over the map
-                        fuse_d = (train_disc and ops.GEMM_PRECISION == 3 and ops.CONV32_X6
-                                  and (l < 4 or Win <= ops.CONV33_MAX_W))
-                        if fuse_d:
-                            _conv2d_dgrad(dy_t, Sx, Ft, Wout, C, w, sw, Win, gx, g_line=dy_line,
-                                          g_seq=dy_seq, g_off=dy_off, mask=mk, fm=fmk,
-                                          colsum=gbs[l - 1])
-                        else:
-                            _conv2d_dgrad(dy_t, Sx, Ft, Wout, C, w, sw, Win, gx, g_line=dy_line,
-                                          g_seq=dy_seq, g_off=dy_off)
-                            if train_disc:
-                                ops.lrelu_bwd_colsum(gx, yb, None, 0.0, SLOPE, Sx * Ft * Win, C, C,
-                                                     gbs[l - 1], y_off=mk[1])
-                            elif fmk is not None:
-                                ops.lrelu_bwd(gx, yb, yb, fmk[2], SLOPE, 1, nb_, nb_, wdev=g1,
-                                              y_off=mk[1], r_off=0)
-                            else:
-                                ops.lrelu_bwd(gx, yb, None, 0.0, SLOPE, 1, nb_, nb_, y_off=mk[1])
-                        g = gx
-                    elif not train_disc and ops.GEMM_PRECISION in (0, 1, 3):
-                        def build_c2t(t):
-                            out = ops.empty(27, 2, C, device=t.device)   # [tap][ci][co]
-                            ops.permute4(out, t, (27, 2, C, 1), (1, 27, 2 * 27, 0))
-                            return out
-                        ops.conv2ch_dgrad(g, Sx, Ft, Win, ops.derived(w, "c2t", build_c2t), g_packed,
-                                          Ft * ldp, ldp, lo * 2)
-                    elif not train_disc:
-                        _conv2d_dgrad(dy_t, Sx, Ft, Wout, C, w, sw, Win, g_packed, g_line=dy_line,
-                                      g_seq=dy_seq, g_off=dy_off, x_line=ldp, x_off=lo * 2)
-            if not train_disc:
-                gfr = ops.empty(B * Ft, win, device=dev)
-                if ops.fft_applies(win):
-                    ops.stft_fft_adjoint(g_packed, win, Ft, gfr, interleaved=True)
-                else:
-                    gemm(mat(g_packed, B * Ft, 2 * nb), mat(dft_interleaved(win, dev)), gfr, form=1)
-                gxn = ops.empty(B, T, device=dev)
-                ops.frames_fold(gfr, gxn, B, Ft, win, hop, T, False)
-                gx2 = ops.empty(B, T, device=dev)
-                # x2 = [real; fake]: the generated half starts at row B
-                ops.call("f2g_peaknorm_bwd", ops.ptr(gx2), ops.ptr(gxn),
-                         ops.ptr(ctx.x2) + 4 * B * T, ops.ptr(st["stats"]) + 4 * 3 * B, B, T)
                 lanes.chain_enter()  # g_fake is accumulated resolution after resolution
                 ops.axpby_rows(g_fake, g_fake, gx2, sa=1.0, sb=1.0)
                 lanes.chain_leave()
-            if train_disc:
-                with ops.weight_batch():
-                    for slot_, gwp_, shape_ in unpack:
-                        grads_w[slot_] = unpack_conv_grad(gwp_, shape_)
             pgrads += grads_w
         lanes.join()
         ctx.saved = None
         return tuple([None, g_fake, None, None] + pgrads)
-
-
-def _colsum_strided(out, a, nrows, W, C, ld, off):
-    """out[c] += sum over (row, w) of a[row*ld + off + w*C + c]: column sums of the (nrows, W*C)
-    slice, then of the resulting (W, C) table."""
-    tmp = ops.zeros(W * C, device=a.device)
-    ops.call("f2g_colsum", ops.ptr(tmp), ops.ptr(a) + 4 * off, ld, None, 0, nrows, W * C)
-    ops.call("f2g_colsum", ops.ptr(out), ops.ptr(tmp), C, None, 0, W, C)
 
 
 # =====================================================================================

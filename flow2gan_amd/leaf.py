@@ -490,7 +490,8 @@ def cond_encoder_forward(enc, x, mask=None):
 # caller builds whatever loss it wants from the score and the feature maps, and the upstream gradient of every
 # map is landed on the channels-last data gradient by f2g_lrelu_bwd_add.  The fused training path
 # (fused_disc.MPDLossFn / MRDLossFn, which bake in the hinge / feature-matching losses) does not come through here;
-# these nodes use no launch lanes and hand their gradients to autograd like any other node.
+# these nodes use no launch lanes and hand their gradients to autograd like any other node.  The backward itself is
+# the fused nodes' walk (fused_disc._mpd_backward_one / _mrd_backward_one) under the upstream landing policy.
 class DiscPFn(GradAwareFunction):
     """DiscriminatorP.forward: x (B, T) -> (score map (B, 1, H5, p), fmap[0..3] (B, C, H, p))."""
 
@@ -518,93 +519,25 @@ class DiscPFn(GradAwareFunction):
         st, prm = ctx.saved, list(ctx.params)
         B, T, p = ctx.dims
         need_x, need_w = ctx.needs_input_grad[0], any(ctx.needs_input_grad[2:])
-        acts, hs, S = st["acts"], st["hs"], st["S"]
-        dev = acts[0].device
-        HALO, SLOPE, CH, STRIDE = FD.HALO, FD.SLOPE, FD.MPD_CH, FD.MPD_STRIDE
+        hs, S = st["hs"], st["S"]
+        dev = st["scores"].device
         ups = {l: g_maps[l - 2] for l in range(2, 6)}      # upstream of the map acts[l] (fmap[l - 2])
-        grads_p: List = [None] * 12
         ctx.saved = None
         if g_sc is None and all(u is None for u in g_maps):
-            return tuple([None, None] + grads_p)
-        unpack = []
-        if need_w:
-            # every weight / bias gradient accumulator of this sub-discriminator: one fill
-            zshapes = [(1, 3 * 1024), (1,)]
-            for l in range(5):
-                zshapes += [(CH[l + 1], 5 * CH[l]), (CH[l + 1],)]
-            zbuf = ops.zeros_many(zshapes, dev)
-
-        def land(gm, l_out):
-            """Leaky-ReLU backward of acts[l_out] on the gradient map that lands on it, the caller's gradient of
-            that map added first; the column sums are the bias gradient of conv layer l_out - 1."""
-            y = acts[l_out]
-            Hl, C_ = hs[l_out], y.shape[1]
-            Hp_ = Hl + 2 * HALO
-            cs = zbuf[2 + 2 * (l_out - 1) + 1] if need_w else None
-            u = ups.get(l_out)
-            if u is not None:
-                ub, uc, uh, uw = u.stride()                  # (B, C, H, p)
-                ops.lrelu_bwd_add(gm, y, (B, p, Hl), (p * Hp_ * C_, Hp_ * C_, C_), C_, u, (ub, uw, uh, uc),
-                                  SLOPE, colsum=cs, g_off=HALO * C_)
-            elif cs is not None:
-                ops.lrelu_bwd_colsum(gm, y, None, 0.0, SLOPE, S * Hp_, C_, C_, cs)
-            else:
-                n_ = S * Hp_ * C_
-                ops.lrelu_bwd(gm, y, None, 0.0, SLOPE, 1, n_, n_)
-            return gm
-
+            return tuple([None, None] + [None] * 12)
+        gs, top = None, 4
         if g_sc is not None:
-            # conv_post (1024 -> 1, 3 taps, stride 1; no activation: no mask on the score gradient)
-            H5 = hs[5]
-            wpost = prm[10]
-            gs = ops.empty(S * H5, 1, device=dev)
+            gs = ops.empty(S * hs[5], 1, device=dev)
             sb, _, sh, sw = g_sc.stride()                    # (B, 1, H5, p) -> (b, w, h) order
-            ops.permute4(gs, g_sc, (B, p, H5, 1), (sb, sw, sh, 0))
-            if need_w:
-                ops.mpdpost_wgrad(acts[5], S, H5, HALO, gs, zbuf[0])
-                unpack.append((10, zbuf[0], wpost.shape))
-                ops.colsum(zbuf[1], gs, S * H5, 1)
-                grads_p[11] = zbuf[1]
-            # (no image reserved for this map: it is changed in place by land() before the next GEMM reads it)
-            g = ops.mpdpost_dgrad(gs, S, H5, HALO, ops.derived(wpost, "pack", FD.pack_conv_weight),
-                                  FD._halo_rows(S, H5, 1024, dev))
-            top = 4
+            ops.permute4(gs, g_sc, (B, p, hs[5], 1), (sb, sw, sh, 0))
         else:
             # the layers above the highest map with a gradient get none: start from zeros on that map
             top = max(l for l in range(2, 6) if ups[l] is not None) - 1
-            g = ops.zeros(S * (hs[top + 1] + 2 * HALO), CH[top + 1], device=dev)
-        land(g, top + 1)
-        for l in reversed(range(top + 1)):
-            w = prm[2 * l]
-            Cin, Cout, stv = CH[l], CH[l + 1], STRIDE[l]
-            Hin, Hout = hs[l], hs[l + 1]
-            Hp = Hout + 2 * HALO
-            # g: gradient of layer l's PRE-activation (halo layout)
-            with ops.split_sharing(g), (st["shares"][l] or ops.split_sharing()):
-                if need_w:
-                    grads_p[2 * l + 1] = zbuf[2 + 2 * l + 1]
-                    gwp = zbuf[2 + 2 * l]
-                    if l == 0:
-                        ops.mpd0_wgrad(acts[0], S, Hin, Hout, HALO, g, gwp)
-                    else:
-                        X = ops.win1d(acts[l], S, Hin + 2 * HALO, Cin, Hp, stv, HALO * stv, 5,
-                                      unbounded=True)   # g's halo rows are zero
-                        ops.wgrad(g, Cout, Cout, X, gwp)
-                    unpack.append((2 * l, gwp, w.shape))
-                if l > 0:
-                    g = FD._conv1d_dgrad(g, S, Hout, Cout, w, stv, 2, Hin)
-                    g._f2g_x3_bad = True      # (changed in place below: no producer-written image of it)
-                    land(g, l)
-                elif need_x:
-                    g = ops.mpd0_dgrad(g, S, Hin, Hout, HALO, w.reshape(Cout, 5), ops.empty(S * Hin, 1, device=dev))
+        g, grads_p = FD._mpd_backward_one(st, prm, gs, (S, 0), need_w, need_x, FD.MPDUpstreamLanding(st, B, ups), top)
         g_x = None
         if need_x:
             g_x = ops.empty(B, T, device=dev)
             ops.period_fold_bwd(g_x, g, B, T, p, hs[0], False)
-        if need_w:
-            with ops.weight_batch():
-                for slot_, gwp_, shape_ in unpack:
-                    grads_p[slot_] = FD.unpack_conv_grad(gwp_, shape_)
         return tuple([g_x, None] + grads_p)
 
 
@@ -650,164 +583,22 @@ class DiscRFn(GradAwareFunction):
         prm = list(ctx.params)
         B, T, win = ctx.dims
         need_x, need_w = ctx.needs_input_grad[0], any(ctx.needs_input_grad[2:])
-        Ft, Wcat, nb, ldp, hop = st["Ft"], st["Wcat"], st["nb"], st["ldp"], st["hop"]
-        cat, packed = st["cat"], st["packed"]
-        dev = cat.device
-        C, SLOPE, LAYERS = FD.MRD_CH, FD.SLOPE, FD.MRD_LAYERS
-        direct = ops.GEMM_PRECISION in (0, 1, 3)
-        S = B
-        grads_w: List = [None] * FD.N_MRD_PARAMS
+        Ft, Wcat = st["Ft"], st["Wcat"]
         ctx.saved = None
         if g_sc is None and all(u is None for u in g_maps):
-            return tuple([None, None] + grads_w)
-        unpack = []
-        ldc = Wcat * C
-
-        def land(gm, y, Wl, u, cs, g_off=0, line=None):
-            """Leaky-ReLU backward of the map y (S, Ft, Wl, C; line stride `line` floats, starting g_off floats
-            in) on the gradient gm of the same layout, the caller's gradient u (B, C, Ft, Wl) added first."""
-            line = Wl * C if line is None else line
-            ub, uc, uf, uw = u.stride()
-            ops.lrelu_bwd_add(gm, y, (S, Ft, Wl), (Ft * line, line, C), C, u, (ub, uf, uw, uc), SLOPE,
-                              colsum=cs, g_off=g_off)
-
-        gcat = None
-        if g_sc is not None:
-            wpost = prm[50]
-            if g_sc.is_contiguous() and g_sc.data_ptr() % 16 == 0:
-                gs = g_sc.view(S * Ft * Wcat, 1)            # already in (b, ft, w) order
-            else:
-                gs = ops.empty(S * Ft * Wcat, 1, device=dev)
-                sb, _, sf, sw = g_sc.stride()
-                ops.permute4(gs, g_sc, (B, Ft, Wcat, 1), (sb, sf, sw, 0))
-            if need_w:
-                gwp, gb = ops.zeros_many([(1, 9 * C), (1,)], dev)
-                if direct:
-                    ops.convpost_wgrad(cat, S, Ft, Wcat, gs, gwp)
-                else:
-                    ops.wgrad(gs, 1, 1, ops.win2d(cat, S, Ft, Wcat, C, Wcat, 3, 3, 1, 1, 1), gwp)
-                unpack.append((50, gwp, wpost.shape))
-                ops.colsum(gb, gs, S * Ft * Wcat, 1)
-                grads_w[51] = gb
-            gcat = ops.empty(S * Ft * Wcat, C, device=dev)
-            if direct:
-                ops.convpost_dgrad(gs, S, Ft, Wcat, ops.derived(wpost, "pack", FD.pack_conv_weight), gcat)
-            else:
-                FD._conv2d_dgrad(gs, S, Ft, Wcat, 1, wpost, 1, Wcat, gcat)
-        elif any(g_maps[4 * bi + 3] is not None for bi in range(5)):
-            gcat = ops.zeros(S * Ft * Wcat, C, device=dev)
-        g_packed = None
-        if need_x:
-            # (a band without any gradient writes nothing: its bins stay zero)
-            g_packed = ops.empty(B * Ft, ldp, device=dev) if g_sc is not None else ops.zeros(B * Ft, ldp, device=dev)
-        foffs, foff = [], 0
-        for bi in range(len(st["bands"])):
-            foffs.append(foff)
-            foff += st["widths"][bi][5]
-        for bi, (lo, hi) in enumerate(st["bands"]):
-            foff = foffs[bi]
-            ws = st["widths"][bi]
-            ub_ = g_maps[4 * bi: 4 * bi + 4]           # upstreams of the outputs of band layers 1..4
-            if g_sc is not None or ub_[3] is not None:
-                top = 4
-            else:
-                # the layers above the highest map with a gradient get none
-                tops = [j + 1 for j in range(3) if ub_[j] is not None]
-                if not tops:
-                    continue
-                top = max(tops)
-            if need_w:   # every accumulator of the band's five layers from one zeroed allocation
-                zs = ops.zeros_many([(C,)] * 5 + [(C, 3 * kw_ * (2 if l_ == 0 else C))
-                                                  for l_, (kw_, _sw) in enumerate(LAYERS)], dev)
-                gbs, gwps = zs[:5], zs[5:]
-            else:
-                gbs = [None] * 5
-            W4 = ws[5]
-            g = None
-            if top == 4:
-                # layer 4's output is a strided slice of cat / gcat
-                if ub_[3] is not None:
-                    land(gcat, cat, W4, ub_[3], gbs[4], g_off=foff * C, line=ldc)
-                else:
-                    ops.lrelu_bwd(gcat, cat, None, 0.0, SLOPE, S * Ft, W4 * C, ldc, g_off=foff * C, y_off=foff * C)
-                    if need_w:
-                        FD._colsum_strided(gbs[4], gcat, S * Ft, W4, C, ldc, foff * C)
-            else:
-                g = ops.zeros(S * Ft * ws[top + 1], C, device=dev)
-                land(g, st["acts"][bi][top], ws[top + 1], ub_[top - 1], gbs[top])
-            for l in reversed(range(top + 1)):
-                kw, sw = LAYERS[l]
-                w = prm[(bi * 5 + l) * 2]
-                Cin = 2 if l == 0 else C
-                Win, Wout = ws[l], ws[l + 1]
-                # g (gcat's slice for l = 4): the gradient of layer l's PRE-activation
-                if l == 4:
-                    dy_line, dy_seq, dy_off, dy_t = ldc, Ft * ldc, foff * C, gcat
-                else:
-                    dy_line, dy_seq, dy_off, dy_t = None, None, 0, g
-                if need_w:
-                    x_in = packed if l == 0 else st["acts"][bi][l - 1]
-                    gwp = gwps[l]
-                    if l == 0 and direct:
-                        ops.conv2ch_wgrad(packed, Ft * ldp, ldp, lo * 2, S, Ft, Win, g, gwp)
-                    elif l in (1, 2, 3) and direct:
-                        ops.conv32_s2_wgrad(x_in, g, S, Ft, Win, Wout, gwp)
-                    elif l == 4 and ops.GEMM_PRECISION == 3 and Wout <= ops.CONV33_MAX_W:
-                        ops.conv33_wgrad(x_in, gcat, S, Ft, Wout, gwp, g_off=foff * C, g_line=ldc, g_seq=Ft * ldc)
-                    else:
-                        if l == 0:
-                            X = ops.win2d(x_in, S, Ft, Win, Cin, Wout, 3, kw, sw, 1, kw // 2,
-                                          line_stride=ldp, seq_stride=Ft * ldp, offset=lo * 2)
-                        else:
-                            X = ops.win2d(x_in, S, Ft, Win, Cin, Wout, 3, kw, sw, 1, kw // 2)
-                        if l == 4:
-                            dY = ops.win1d(gcat, S * Ft, Wcat, C, W4, 1, -foff, 1)
-                        else:
-                            dY = mat(g, S * Ft * Wout, C)
-                        gemm(dY, X, gwp, form=2, atomic=True,
-                             split_k=ops.split_for(X.rows, (3 * kw * Cin + 255) // 256))
-                    unpack.append(((bi * 5 + l) * 2, gwp, w.shape))
-                    grads_w[(bi * 5 + l) * 2 + 1] = gbs[l]
-                if l > 0:
-                    # lands on acts[bi][l - 1] (a feature map for l - 1 >= 1)
-                    yb = st["acts"][bi][l - 1]
-                    gx = ops.empty(S * Ft * Win, Cin, device=dev)
-                    FD._conv2d_dgrad(dy_t, S, Ft, Wout, C, w, sw, Win, gx, g_line=dy_line, g_seq=dy_seq,
-                                     g_off=dy_off)
-                    u = ub_[l - 2] if l >= 2 else None
-                    if u is not None:
-                        land(gx, yb, Win, u, gbs[l - 1])
-                    elif need_w:
-                        ops.lrelu_bwd_colsum(gx, yb, None, 0.0, SLOPE, S * Ft * Win, C, C, gbs[l - 1])
-                    else:
-                        nb_ = S * Ft * Win * C
-                        ops.lrelu_bwd(gx, yb, None, 0.0, SLOPE, 1, nb_, nb_)
-                    g = gx
-                elif need_x and direct:
-                    def build_c2t(t):
-                        out = ops.empty(27, 2, C, device=t.device)   # [tap][ci][co]
-                        ops.permute4(out, t, (27, 2, C, 1), (1, 27, 2 * 27, 0))
-                        return out
-                    ops.conv2ch_dgrad(g, S, Ft, Win, ops.derived(w, "c2t", build_c2t), g_packed,
-                                      Ft * ldp, ldp, lo * 2)
-                elif need_x:
-                    FD._conv2d_dgrad(dy_t, S, Ft, Wout, C, w, sw, Win, g_packed, g_line=dy_line,
-                                     g_seq=dy_seq, g_off=dy_off, x_line=ldp, x_off=lo * 2)
-        g_x = None
-        if need_x:
-            gfr = ops.empty(B * Ft, win, device=dev)
-            if ops.fft_applies(win):
-                ops.stft_fft_adjoint(g_packed, win, Ft, gfr, interleaved=True)
-            else:
-                gemm(mat(g_packed, B * Ft, 2 * nb), mat(FD.dft_interleaved(win, dev)), gfr, form=1)
-            gxn = ops.empty(B, T, device=dev)
-            ops.frames_fold(gfr, gxn, B, Ft, win, hop, T, False)
-            g_x = ops.empty(B, T, device=dev)
-            ops.peaknorm_bwd(g_x, gxn, x, st["stats"], B, T)
-        if need_w:
-            with ops.weight_batch():
-                for slot_, gwp_, shape_ in unpack:
-                    grads_w[slot_] = FD.unpack_conv_grad(gwp_, shape_)
+            return tuple([None, None] + [None] * FD.N_MRD_PARAMS)
+        gs, tops = None, None
+        if g_sc is None:
+            # per band the highest of layers 1..4 whose output has a gradient: the layers above it get none
+            tops = [max((j + 1 for j in range(4) if g_maps[4 * bi + j] is not None), default=None) for bi in range(5)]
+        elif g_sc.is_contiguous() and g_sc.data_ptr() % 16 == 0:
+            gs = g_sc.view(B * Ft * Wcat, 1)            # already in (b, ft, w) order
+        else:
+            gs = ops.empty(B * Ft * Wcat, 1, device=x.device)
+            sb, _, sf, sw = g_sc.stride()
+            ops.permute4(gs, g_sc, (B, Ft, Wcat, 1), (sb, sf, sw, 0))
+        g_x, grads_w = FD._mrd_backward_one(st, prm, x, win, gs, (B, 0), need_w, need_x,
+                                            FD.MRDUpstreamLanding(st, B, g_maps), tops)
         return tuple([g_x, None] + grads_w)
 
 

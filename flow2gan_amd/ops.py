@@ -1608,6 +1608,14 @@ def colsum(out, a, rows, cols, b=None, out_offset=0):
     return out
 
 
+def colsum_strided(out, a, nrows, W, Cc, ld, off):
+    """out[c] += sum over (row, w) of a[row*ld + off + w*Cc + c]: column sums of the (nrows, W*Cc)
+    slice, then of the resulting (W, Cc) table."""
+    tmp = zeros(W * Cc, device=a.device)
+    call("f2g_colsum", ptr(tmp), ptr(a) + 4 * off, ld, None, 0, nrows, W * Cc)
+    call("f2g_colsum", ptr(out), ptr(tmp), Cc, None, 0, W, Cc)
+
+
 def bct_to_rows(out, x, B, Cc, F):
     call("f2g_bct_to_rows", ptr(out), out.stride(0), ptr(x), B, Cc, F)
     return out
@@ -1689,8 +1697,9 @@ def peaknorm_fwd(y, stats, x, rows, T):
     call("f2g_peaknorm_fwd", ptr(y), ptr(stats), ptr(x), rows, T)
 
 
-def peaknorm_bwd(gx, gy, x, stats, rows, T):
-    call("f2g_peaknorm_bwd", ptr(gx), ptr(gy), ptr(x), ptr(stats), rows, T)
+def peaknorm_bwd(gx, gy, x, stats, rows, T, row_off=0):
+    """gx, gy: (rows, T); they belong to rows row_off .. row_off + rows of x and of its stats."""
+    call("f2g_peaknorm_bwd", ptr(gx), ptr(gy), ptr(x) + 4 * row_off * T, ptr(stats) + 4 * 3 * row_off, rows, T)
 
 
 def lrelu_bwd(g, y_act, f_real, w, slope, rows, cols, ld, wdev=None, g_off=0, y_off=0, r_off=0):
