@@ -27,6 +27,7 @@ class Operand(C.Structure):
         ("reflect", C.c_int32), ("split", C.c_int32),
         ("alpha", C.c_void_p), ("lrelu_src", C.c_void_p),
         ("lrelu_slope", C.c_float), ("unbounded", C.c_int32),
+        ("rscale", C.c_void_p),
     ]
 
 
@@ -236,13 +237,14 @@ _SIGS = {
     "f2g_fused_block_multi": [C.POINTER(DwnormFwd), C.POINTER(FusedMlpDesc), C.c_int32],
     "f2g_istft_ola_multi": [C.POINTER(OlaMultiDesc), _P, _I, _I, _F, _I],
     "f2g_split_bf16x3": [_P, _P, _L, _I, _I],
+    "f2g_split_f16x2": [_P, _P, _P, _L, _I, _I],
     "f2g_multi": [C.POINTER(MultiDesc)],
 }
 EXPORTS = sorted(list(_SIGS) + ["f2g_version", "f2g_last_error", "f2g_gemm_last_path", "f2g_gemm_last_kernel",
                                  "f2g_fused_last_launch",
                                  "f2g_gemm_lean_ok", "f2g_gemm_wgrad_lean", "f2g_fused_mlp_ok",
                                  "f2g_dwnorm_bwd_workspace", "f2g_split_bf16x3_bytes", "f2g_gemm_x6_ok",
-                                 "f2g_gemm_colsum_part_rows", "f2g_set_option", "f2g_get_option",
+                                 "f2g_gemm_colsum_part_rows", "f2g_gemm_f16_ok", "f2g_set_option", "f2g_get_option",
                                  "f2g_dwconv_bwd_workspace", "f2g_sadam_chunk_elems"])
 
 
@@ -272,6 +274,8 @@ def _load():
     lib.f2g_split_bf16x3_bytes.restype = C.c_int64
     lib.f2g_gemm_x6_ok.argtypes = [C.POINTER(GemmDesc)]
     lib.f2g_gemm_x6_ok.restype = C.c_int
+    lib.f2g_gemm_f16_ok.argtypes = [C.POINTER(GemmDesc)]
+    lib.f2g_gemm_f16_ok.restype = C.c_int
     lib.f2g_gemm_colsum_part_rows.argtypes = [C.POINTER(GemmDesc)]
     lib.f2g_gemm_colsum_part_rows.restype = C.c_int32
     lib.f2g_fused_mlp_ok.argtypes = [C.c_int32, C.c_int32]

@@ -897,6 +897,11 @@ extern "C" int f2g_gemm(const f2g_gemm_desc* dp, f2g_stream_t stream) {
                   "(f2g_gemm_colsum_part_rows(d) == 0 for this descriptor)");
     return F2G_EINVAL;
   }
+  if (d.precision == 4) return f2g_gemm_h3(d, st);   // fp16x3: its own kernel or F2G_EINVAL
+  if (d.A.split == 5 || d.B.split == 5) {
+    f2g_set_error("f2g_gemm: f2g_split_f16x2 images (split = 5) belong to precision 4");
+    return F2G_EINVAL;
+  }
   if (d.precision == 3 && d.form == 2) {
     // fp32-class weight gradient: fp32 operands, split into three pieces inside the kernel
     if (d.A.split || d.B.split || d.A.rows != d.B.rows || !f2g_leanw_ok(d) || d.E.x3_out ||

@@ -1,5 +1,5 @@
 // What more than one of the GEMM translation units needs (gemm.hip, gemm_lean.hip, gemm_wgrad.hip, gemm_x6.hip,
-// gemm_x6p.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
+// gemm_x6p.hip, gemm_f16.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
 // three-piece split, the LDS barrier, the lab switches, and the host functions that cross those files.  Everything
 // defined here has internal linkage; no GEMM file includes another.
 #pragma once
@@ -18,6 +18,8 @@ bool f2g_leanw_fp32_takes(const f2g_gemm_desc& d, int split);
 int f2g_launch_leanw(const f2g_gemm_desc& d, int pieces, int split, hipStream_t st);
 // gemm_x6.hip: form 0 at precision 3 (checks the descriptor, picks the kernel, launches)
 int f2g_gemm_x6(const f2g_gemm_desc& d, hipStream_t st);
+// gemm_f16.hip: form 0 at precision 4 over f2g_split_f16x2 images (checks the descriptor, launches)
+int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st);
 
 // ---- lab switches (product builds: both 0) ---------------------------------------------------------------------
 // F2G_LABVAR (tools/micro/build_variants.sh; timing only): ablations of the bf16 lean K loop (gemm_lean.hip) --

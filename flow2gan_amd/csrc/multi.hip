@@ -7,6 +7,7 @@
 // one call must not depend on each other (the host batches by dependency level, flow2gan_amd/ops.py).
 // Element arithmetic is exactly that of the single-operation kernels (same rounding of the bf16 pieces).
 #include "common.h"
+#include "split_f16.h"
 
 namespace {
 
@@ -108,6 +109,14 @@ __device__ __forceinline__ void run_split3g(const f2g_multi_entry& e, long long 
   }
 }
 
+// F2G_MULTI_SPLIT_F16: f2g_split_f16x2 -- one wave per row, the entry's blocks share its rows; the row is read twice
+// (split_f16.h: the same image from 38 instead of 94 registers, which every other kind of this kernel would pay for in occupancy)
+__device__ __forceinline__ void run_split_f16(const f2g_multi_entry& e, long long b, long long nb) {
+  float* dst = reinterpret_cast<float*>(e.out);
+  f2g_split_f16x2_rows<false>(dst, dst + e.s[1], reinterpret_cast<const float*>(e.in), e.s[0], e.n[0], e.n[1],
+                       b * 4 + (threadIdx.x >> 6), nb * 4);
+}
+
 __global__ __launch_bounds__(256) void multi_kernel(const f2g_multi_desc d) {
   int i = 0;
   long long first = 0;
@@ -119,6 +128,7 @@ __global__ __launch_bounds__(256) void multi_kernel(const f2g_multi_desc d) {
     case F2G_MULTI_PERMUTE4: run_permute4(e, b, nb); break;
     case F2G_MULTI_COPY3: run_copy3(e, b, nb); break;
     case F2G_MULTI_SPLIT3: run_split3(e, b, nb); break;
+    case F2G_MULTI_SPLIT_F16: run_split_f16(e, b, nb); break;
     default: run_split3g(e, b, nb); break;
   }
 }
@@ -130,12 +140,16 @@ extern "C" int f2g_multi(const f2g_multi_desc* d, f2g_stream_t stream) {
   long long grid = 0;
   for (int i = 0; i < d->n; ++i) {
     const f2g_multi_entry& e = d->e[i];
-    if (!e.out || (e.kind != F2G_MULTI_FILL && !e.in) || e.blocks < 1 || e.kind < 0 || e.kind > F2G_MULTI_SPLIT3G)
+    if (!e.out || (e.kind != F2G_MULTI_FILL && !e.in) || e.blocks < 1 || e.kind < 0 || e.kind > F2G_MULTI_SPLIT_F16)
       return F2G_EINVAL;
     if (e.kind == F2G_MULTI_SPLIT3G && (e.n[0] & 31)) return F2G_EINVAL;
     if ((e.kind == F2G_MULTI_SPLIT3 || e.kind == F2G_MULTI_SPLIT3G) &&
         (e.n[1] < 32 || (e.n[1] % 32) || e.s[0] < e.n[1] || (e.s[0] & 3) || (((uintptr_t)e.in) & 15) ||
          (((uintptr_t)e.out) & 15)))
+      return F2G_EINVAL;
+    if (e.kind == F2G_MULTI_SPLIT_F16 &&
+        (e.n[0] < 0 || e.n[1] < 32 || (e.n[1] % 32) || e.n[1] > F2G_F16_MAX_K || e.s[0] < e.n[1] || (e.s[0] & 3) ||
+         e.s[1] <= 0 || (((uintptr_t)e.in) & 15) || (((uintptr_t)e.out) & 15)))
       return F2G_EINVAL;
     grid += e.blocks;
   }

@@ -200,7 +200,7 @@ MULTI_CAP = min(L.MULTI_MAX, max(1, opt("multi_cap", L.MULTI_MAX)))     # operat
 
 
 class WeightBatch:
-    """Records fill / permute4 / copy3 / split3 operations (ops.fill_, permute4, copy3, split3 while
+    """Records fill / permute4 / copy3 / split3 / fp16 image operations (ops.fill_, permute4, copy3, split3 while
     ops.BATCH is this object) and launches them as f2g_multi tables, dependency level by level."""
 
     MAX_BLOCKS = 512
@@ -447,6 +447,7 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
     padded to whole K slabs): what bench.py's FLOP count uses; the launch itself ignores them.
     split_k: 0 = let the library decide (forms 0/1: split-K onto a zeroed output when the tile
     grid would leave most of the last wave of CUs idle), 1 = off, > 1 = as given."""
+    global FP16X3_LAUNCHES
     if form == 1:
         # data gradient C[r,n] = sum_k A[r,k] W[k,n] as a forward GEMM against the cached transpose
         # W^T [n][k]: same products in the same order, and the lean forward kernel applies
@@ -500,7 +501,21 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
                 split_k = split_for(A.rows, tiles, True)
     d.split_k = split_k
     d.precision = GEMM_PRECISION
-    if GEMM_PRECISION == 3:
+    f16 = False
+    if GEMM_PRECISION == 3 and FP16X3 and form == 0 and A.split == 0 and Bm.split == 0 \
+            and A.cols >= FP16X3_MIN_K and Bm.rows >= FP16X3_MIN_N and split_k <= 1 and out.dtype == torch.float32:
+        # fp16x3: two plain matrices (a data gradient arrives here as form 0 over the cached transpose) as
+        # f2g_split_f16x2 images -- the weight's from the derived-weight cache, the activation's made here.  The
+        # library is asked first, with the descriptor as it will be launched; what it declines goes the bf16x6 way
+        d.precision = 4
+        if L.lib.f2g_gemm_f16_ok(C.byref(d)) == 2:
+            d.A, d.B = _f16_operand(A), _f16_operand(Bm)
+            f16 = True
+            FP16X3_LAUNCHES += 1
+    if GEMM_PRECISION == 3 and f16:
+        if x3_out:
+            out._f2g_x3_bad = True     # (no image from this kernel: the next consumer builds its own)
+    elif GEMM_PRECISION == 3:
         d.precision = 0       # (what does not qualify below runs on the exact fp32 MFMA)
         in_kernel = X6F == 1
         if X6F == 2 and X6F_MIN_K <= A.cols < X6_MIN_K and (
@@ -892,6 +907,33 @@ def _split_operand(o: Operand) -> Operand:
     return n
 
 
+def _f16_operand(o: Operand) -> Operand:
+    """Copy of a plain fp32 matrix operand over its two-piece fp16 image (f2g_split_f16x2: same addressing, the
+    reciprocal row scales behind the image in the same allocation): cached for weights and cached re-layouts of
+    weights (recorded into an open WeightBatch when a rebuild replays the chain), written here for activations."""
+    t = o._keep[0]
+    rows, K, ld = o.rows, o.cols, o.seq_stride
+    off = o.base - ptr(t)
+    soff = ((rows - 1) * ld + K + 3) // 4 * 4          # floats from the image to its scales
+
+    def build(tt):
+        buf = torch.empty(soff + rows, device=tt.device, dtype=torch.float32)
+        if BATCH is not None:
+            BATCH.add(5, ptr(buf), 4 * (soff + rows), ptr(tt) + off, 4 * ((rows - 1) * ld + K), (rows, K, 0, 0),
+                      (ld, soff, 0, 0), 256 * ((rows + 3) // 4), (buf, tt))
+        else:
+            call("f2g_split_f16x2", ptr(buf), ptr(buf) + 4 * soff, ptr(tt) + off, ld, rows, K)
+        return buf
+    buf = derived(t, ("f16x2", off, rows, K, ld), build) if _is_const(t) else build(t)
+    n = Operand()
+    C.memmove(C.byref(n), C.byref(o), C.sizeof(Operand))
+    n.base = ptr(buf)
+    n.rscale = ptr(buf) + 4 * soff
+    n.split = 5
+    n._keep = (buf,) + tuple(o._keep)
+    return n
+
+
 CONV32_X6 = opt("conv32_x6", True)    # bf16x6 mode: fp32-class direct MRD convs (bench.py reads it)
 
 
@@ -1162,7 +1204,7 @@ class GemmTimer:
         call("f2g_gemm", C.byref(d))
         e.record()
         self.records.append((s, e, flops))
-        self.paths.append(("generic", "lean", "lean-streamk", "narrow", "x6", "x6-thin")[L.lib.f2g_gemm_last_path()])
+        self.paths.append(("generic", "lean", "lean-streamk", "narrow", "x6", "x6-thin", "fp16x3")[L.lib.f2g_gemm_last_path()])
         if self.paths[-1] == "x6" and form == 0 and d.A.split == 3 and (L.lib.f2g_gemm_x6_ok(C.byref(d)) & 2):
             self.x6_tap = getattr(self, "x6_tap", 0) + 1      # (launches on the tap-walking instance)
         self.shapes.append((form, mm, nn, kk))
@@ -1213,20 +1255,39 @@ GEMM_TIMER = None
 # accumulate).  Selected with F2G_GEMM=fp32|bf16x3 (default fp32) or set_gemm_precision().
 import os as _os
 
-GEMM_PRECISION = {"bf16x3": 1, "split": 1, "1": 1, "bf16": 2, "2": 2, "bf16x6": 3, "3": 3}.get(
+GEMM_PRECISION = {"bf16x3": 1, "split": 1, "1": 1, "bf16": 2, "2": 2, "bf16x6": 3, "3": 3, "fp16x3": 3}.get(
     _os.environ.get("F2G_GEMM", "fp32").lower(), 0)
+# fp16x3 (F2G_GEMM=fp16x3 / set_gemm_precision("fp16x3")): the bf16x6 mode everywhere (GEMM_PRECISION == 3), except
+# that the forward-form GEMMs over two plain matrices -- the generator's pointwise convolutions and, through the
+# cached transposed weight, their data gradients -- run on gemm_h3_kernel (f2g_gemm_desc.precision 4): two scaled
+# fp16 pieces per operand, three MFMAs per product, error <= 3 * 2^-22 per product (gemm() below)
+FP16X3 = _os.environ.get("F2G_GEMM", "fp32").lower() == "fp16x3"
+# shortest reduction the fp16x3 kernel takes (where X6F_MIN_K starts; tests lower it to reach the kernel on small
+# shapes): profiles/fp16x3_gemm_shapes.txt has the launches it was measured on
+FP16X3_MIN_K = opt("fp16x3_min_k", 160)
+# fewest output columns: every activation pays an image pass (f2g_split_f16x2: 10 bytes of HBM traffic per element
+# against 4 for the in-kernel split of gemm_x6g_kernel) that only a wide output amortises.  Measured per launch,
+# image pass included, on one box (profiles/fp16x3_gemm_shapes.txt, first table: every shape on the new kernel):
+# K 768 -> N 2304 0.87-0.95 of the bf16x6 time forward, 0.96-1.06 as a data gradient (inside the spread); every
+# shape with N <= 1536 loses -- 1.02-1.16 at N 768, 1.04-1.62 at N 384 / 512 / 1152 / 1536 -- and so did the steps
+# (stage 1 34.7 against 31.1 ms).  Hence the rule: N >= 2048 (tests lower it).  Second table of the file, the rule
+# in place: 0 of 36 launches lose by more than their spread, stage 1 31.46 against 31.12 ms, stage 2 162.11 : 161.70
+FP16X3_MIN_N = opt("fp16x3_min_n", 2048)
+FP16X3_LAUNCHES = 0        # launches gemm_h3_kernel took (tests and tools)
 
 
 def set_gemm_precision(name: str) -> None:
-    global GEMM_PRECISION
-    if name not in ("fp32", "bf16x3", "bf16", "bf16x6"):
-        raise ValueError("precision must be 'fp32', 'bf16x3', 'bf16x6' or 'bf16'")
+    global GEMM_PRECISION, FP16X3
+    if name not in ("fp32", "bf16x3", "bf16", "bf16x6", "fp16x3"):
+        raise ValueError("precision must be 'fp32', 'bf16x3', 'bf16x6', 'fp16x3' or 'bf16'")
     # "bf16": plain bf16 operands, fp32 accumulate -- inference throughput mode (BASELINE config 2),
     # not a parity mode (waveform error ~1e-3 RMS instead of <= 1e-4)
     # "bf16x6": fp32-class -- three bf16 pieces per operand, six MFMAs per product (error ~2^-23 per
     # product, like fp32 rounding itself) for the plain-matrix forward / data-gradient GEMMs (the
     # generator's 1x1 convolutions and linears); everything else stays on the exact fp32 MFMA
-    GEMM_PRECISION = {"fp32": 0, "bf16x3": 1, "bf16": 2, "bf16x6": 3}[name]
+    # "fp16x3": bf16x6 with the plain-matrix forward-form GEMMs on two scaled fp16 pieces (FP16X3 above)
+    GEMM_PRECISION = {"fp32": 0, "bf16x3": 1, "bf16": 2, "bf16x6": 3, "fp16x3": 3}[name]
+    FP16X3 = name == "fp16x3"
 
 
 # ------------------------------------------------------------------ concurrent launch lanes

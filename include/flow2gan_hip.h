@@ -80,7 +80,9 @@ typedef struct {
    *    straight into the operand registers of v_mfma_f32_32x32x16_bf16 (gemm_x6g_kernel);
    * 1: `base` holds the split-bf16 image written by f2g_split_bf16 (same addressing);
    * 2: `base` is a TRUE bf16 tensor (f2g_to_bf16 or a bf16 producer): strides / offsets stay in
-   *    elements, the reduction needs whole 64-element slabs (precision 2, lean kernel only) */
+   *    elements, the reduction needs whole 64-element slabs (precision 2, lean kernel only);
+   * 5: `base` holds the two-piece fp16 image written by f2g_split_f16x2 (same addressing as the plain fp32
+   *    matrix it was made of) and `rscale` its reciprocal row scales (precision 4, form 0, plain matrices only) */
   int32_t split;
   const float* alpha;
   const float* lrelu_src;
@@ -90,6 +92,8 @@ typedef struct {
    * with is zero there -- the weight gradient of a conv whose gradient map carries zero halo rows.
    * Only the split-bf16 weight-gradient kernel looks at it. */
   int32_t unbounded;
+  /* split = 5 only: 1 / s per row of the operand (f2g_split_f16x2), `rows` floats; NULL otherwise */
+  const float* rscale;
 } f2g_operand;
 
 /* Epilogue of f2g_gemm: v = acc (+bias[n]) (+gamma[n]*res[r,n]); optional PReLU-derivative
@@ -172,7 +176,10 @@ typedef struct {
    * 3 = fp32-CLASS products on the bf16 pipe: three bf16 pieces per operand, six MFMAs per product.
    *     form 0: both operands as three-piece images (f2g_split_bf16x3 / E.x3_out of the producing
    *     GEMM; f2g_gemm_x6_ok); form 2: the fp32 operands themselves -- whatever f2g_gemm_lean_ok accepts
-   *     for form 2, with E.atomic when split_k > 1 -- split into pieces inside the kernel. */
+   *     for form 2, with E.atomic when split_k > 1 -- split into pieces inside the kernel;
+   * 4 = fp16x3: fp32-class products from TWO fp16 pieces per operand, three MFMAs per product (per-product error
+   *     <= 3 * 2^-22): form 0 over two plain matrices, both given as f2g_split_f16x2 images (f2g_operand.split = 5
+   *     with rscale).  A descriptor f2g_gemm_f16_ok does not answer with 1 is F2G_EINVAL, never run elsewhere. */
   int32_t precision;
   int32_t _pad3;
 } f2g_gemm_desc;
@@ -222,14 +229,33 @@ int f2g_gemm_x6_ok(const f2g_gemm_desc* d);
  * column sums (then leave colsum_part_ld at 0: atomics).  Ask with the descriptor exactly as it will be
  * launched (precision, operand formats); E.colsum / colsum_alpha / colsum_part_ld may still be unset. */
 int32_t f2g_gemm_colsum_part_rows(const f2g_gemm_desc* d);
+/* Two-piece fp16 image for precision 4 (fp16x3).  Every row of the (rows, K) row-major fp32 matrix src (row
+ * stride ld floats, K % 32 == 0, K <= 4096, both pointers 16-byte aligned) is scaled by the power of two
+ * s = 2^(14 - floor(log2 max|x|)) -- largest element in [2^14, 2^15); s = 1 for an all-zero row and for a row
+ * holding an inf or a NaN, whose values stay non-finite; the exponent clamped to +-126 so that s and 1 / s are
+ * normal -- and split: y = x s, hi = fp16(y) (nearest even), lo = fp16(2^11 (y - hi)), so y = hi + 2^-11 lo to
+ * 2^-22 |y|.  dst (same row stride; may be src) receives the image in the layout of f2g_split_bf16: every aligned
+ * group of four floats becomes its four hi halves followed by its four lo halves, the same 16 bytes at the same
+ * offset; nothing outside the rows' K columns is written.  rscale[r] = 1 / s of row r.  One pass over the matrix,
+ * one wave per row, the row's maximum by a fixed reduction order (no atomics: the image is reproducible).
+ * f2g_gemm with precision = 4 computes, for two such images, acc0 += hi_a hi_b, acc1 += hi_a lo_b + lo_a hi_b on
+ * v_mfma_f32_32x32x16_f16 and hands v = (acc0 + 2^-11 acc1) * rscale_a[row] * rscale_b[col] to the generic
+ * epilogue (bias, residual, leaky ReLU, PReLU with both outputs, PReLU backward with column sums, accumulate /
+ * atomic, row map, mask).  No x3_out, no colsum_part_ld, no bf16 output, no split-K.
+ * f2g_gemm_f16_ok(d) applies the tests of that dispatch without launching: 1 = f2g_gemm runs d as handed over,
+ * 2 = it would once both fp32 operands (split = 0) are replaced by their images, 0 = not at precision 4. */
+int f2g_split_f16x2(float* dst, float* rscale, const float* src, int64_t ld, int32_t rows, int32_t K,
+                    f2g_stream_t stream);
+int f2g_gemm_f16_ok(const f2g_gemm_desc* d);
 
 /* Kernel family the last f2g_gemm call dispatched to (benchmark diagnostics, not thread safe):
  * 0 generic MFMA kernels, 1 lean kernel, 2 lean kernel in stream-K mode, 3 narrow VALU kernels,
- * 4 the precision-3 kernels, 5 the precision-3 kernel for <= 32 output columns (gemm_x6n_kernel). */
+ * 4 the precision-3 kernels, 5 the precision-3 kernel for <= 32 output columns (gemm_x6n_kernel),
+ * 6 the fp16x3 kernel (precision 4). */
 int f2g_gemm_last_path(void);
 /* Kernel instance the last f2g_gemm call launched (tests and diagnostics, not thread safe; "" when it
  * launched nothing), e.g. "lean<sk=1,ep=3,pm=0>" (lean kernel: stream-K, epilogue instance, operand mode),
- * "lean_tall<ep=2,pm=1>", "lean_tap<ep=3>", "narrow_wgrad4<4>", "x6f<wimg=1>" or "generic<F1,GF,PF> split=3"
+ * "lean_tall<ep=2,pm=1>", "lean_tap<ep=3>", "narrow_wgrad4<4>", "x6f<wimg=1>", "h3<ep=all>" or "generic<F1,GF,PF> split=3"
  * (generic MFMA tiles: form, loader modes of A and B, and the K split when > 1). */
 const char* f2g_gemm_last_kernel(void);
 
@@ -527,8 +553,12 @@ int f2g_fill(float* x, float v, int64_t n, f2g_stream_t stream);
  *                          F2G_MULTI_SPLIT3   f2g_split_bf16x3         n = {rows, K}, s[0] = ld
  *                          F2G_MULTI_SPLIT3G  the same pieces in MFMA FRAGMENT order (f2g_operand.split = 4;
  *                                             rows % 32 == 0)                  n = {rows, K}, s[0] = ld
+ *                          F2G_MULTI_SPLIT_F16 f2g_split_f16x2 (image row stride = ld; K <= 4096; one wave per
+ *                                             row: blocks <= rows / 4 rounded up)    n = {rows, K}, s[0] = ld,
+ *                                             s[1] = offset in floats from `out` to the reciprocal row scales
  * `blocks` = blocks of 256 threads the entry gets (>= 1; its elements are walked grid-stride). */
-enum { F2G_MULTI_FILL = 0, F2G_MULTI_PERMUTE4 = 1, F2G_MULTI_COPY3 = 2, F2G_MULTI_SPLIT3 = 3, F2G_MULTI_SPLIT3G = 4 };
+enum { F2G_MULTI_FILL = 0, F2G_MULTI_PERMUTE4 = 1, F2G_MULTI_COPY3 = 2, F2G_MULTI_SPLIT3 = 3, F2G_MULTI_SPLIT3G = 4,
+       F2G_MULTI_SPLIT_F16 = 5 };
 #define F2G_MULTI_MAX 48
 typedef struct {
   void* out;
