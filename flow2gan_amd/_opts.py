@@ -12,7 +12,8 @@ shapes.  The comment at each declaration says which.
 The names (each declared in flow2gan_amd/ops.py unless noted): conv32_x6, fft, fft_reflect, fft_min, fused_multi,
 eager_rebuild, time_ahead (models/generator.py), colsum_parts, x6f, x6g, x3_check, multi_cap, lane_cap_<pool>,
 x6_min_k, x6_min_rows, x6_nopass_k, x6f_min_k, x6f_min_n, x6f_min_tiles, x6f_tall_rows, fp16x3_min_k, fp16x3_min_n
-(F2G_GEMM=fp16x3: the shortest reduction and the fewest output columns the fp16x3 GEMM kernel takes).
+(F2G_GEMM=fp16x3: the shortest reduction and the fewest output columns the fp16x3 GEMM kernel takes),
+fp16x3_wgrad_min_rows (the fewest reduction rows at which a weight gradient takes the fp16x3 weight-gradient kernel).
 
 Environment switches that remain on their own (user-facing, or needed before anything is imported):
 F2G_GEMM (arithmetic of the GEMMs), F2G_STREAMS (launch lanes), F2G_DETERMINISTIC (no splits on the library's

@@ -897,9 +897,9 @@ extern "C" int f2g_gemm(const f2g_gemm_desc* dp, f2g_stream_t stream) {
                   "(f2g_gemm_colsum_part_rows(d) == 0 for this descriptor)");
     return F2G_EINVAL;
   }
-  if (d.precision == 4) return f2g_gemm_h3(d, st);   // fp16x3: its own kernel or F2G_EINVAL
-  if (d.A.split == 5 || d.B.split == 5) {
-    f2g_set_error("f2g_gemm: f2g_split_f16x2 images (split = 5) belong to precision 4");
+  if (d.precision == 4) return f2g_gemm_h3(d, st);   // fp16x3: its own kernels or F2G_EINVAL
+  if (d.A.split == 5 || d.B.split == 5 || d.A.split == 6 || d.B.split == 6) {
+    f2g_set_error("f2g_gemm: f2g_split_f16x2 / f2g_split_f16x2_cols images (split = 5 / 6) belong to precision 4");
     return F2G_EINVAL;
   }
   if (d.precision == 3 && d.form == 2) {

@@ -18,7 +18,8 @@ bool f2g_leanw_fp32_takes(const f2g_gemm_desc& d, int split);
 int f2g_launch_leanw(const f2g_gemm_desc& d, int pieces, int split, hipStream_t st);
 // gemm_x6.hip: form 0 at precision 3 (checks the descriptor, picks the kernel, launches)
 int f2g_gemm_x6(const f2g_gemm_desc& d, hipStream_t st);
-// gemm_f16.hip: form 0 at precision 4 over f2g_split_f16x2 images (checks the descriptor, launches)
+// gemm_f16.hip: precision 4 -- form 0 over f2g_split_f16x2 images, form 2 over f2g_split_f16x2_cols images (checks
+// the descriptor, launches)
 int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st);
 
 // ---- lab switches (product builds: both 0) ---------------------------------------------------------------------

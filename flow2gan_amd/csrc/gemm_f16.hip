@@ -1,5 +1,6 @@
 // fp16x3: fp32-class products from TWO scaled fp16 pieces per operand, three MFMAs per product (gemm.hip has the
-// family, gemm_common.h what the GEMM files share).  f2g_split_f16x2 writes the operand images, gemm_h3_kernel reads them.
+// family, gemm_common.h what the GEMM files share).  f2g_split_f16x2 writes the operand images, gemm_h3_kernel reads them;
+// f2g_split_f16x2_cols writes the images of K-major operands (one scale per column), gemm_h3w_kernel reads those.
 #include <stddef.h>
 #include <stdint.h>
 
@@ -15,6 +16,71 @@ __global__ __launch_bounds__(256) void split_f16x2_kernel(float* dst, float* rsc
                                                           int rows, int K) {
   f2g_split_f16x2_rows<true>(dst, rscale, src, ld, rows, K, (long long)blockIdx.x * 4 + (threadIdx.x >> 6),
                        (long long)gridDim.x * 4);
+}
+
+// ---- the column image (K-major operands: the reduction of a weight gradient walks ROWS, so a scale that leaves
+// the sum is one per column) --------------------------------------------------------------------------------------
+// Both kernels: thread = (16-byte chunk blockIdx.x * 32 + (tid & 31) of a row, row blockIdx.y * 8 + (tid >> 5) and
+// every gridDim.y * 8 rows from there): 32 threads read 512 contiguous bytes of a row.
+// First pass: the columns' largest sign-less bit patterns -- per thread over its rows, per block through LDS, across
+// blocks by atomicMax into `work` (zeroed before; a maximum does not depend on the order: the image is reproducible).
+__global__ __launch_bounds__(256) void cols_amax_kernel(unsigned* work, const float* src, long long ld, int rows,
+                                                        int cols) {
+  __shared__ uint4 part[8][32];
+  const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5, c0 = (blockIdx.x * 32 + cl) * 4;
+  const long long step = (long long)gridDim.y * 8;
+  unsigned m[4] = {0u, 0u, 0u, 0u};
+  if (c0 < cols) {
+    const float* p = src + c0;
+#pragma unroll 4
+    for (long long r = (long long)blockIdx.y * 8 + rl; r < rows; r += step) {
+      const float4 v = *reinterpret_cast<const float4*>(p + r * ld);
+      const unsigned a[4] = {__float_as_uint(v.x), __float_as_uint(v.y), __float_as_uint(v.z), __float_as_uint(v.w)};
+#pragma unroll
+      for (int j = 0; j < 4; ++j) m[j] = m[j] > (a[j] & 0x7fffffffu) ? m[j] : (a[j] & 0x7fffffffu);
+    }
+  }
+  part[rl][cl] = make_uint4(m[0], m[1], m[2], m[3]);
+  __syncthreads();
+  if (rl != 0 || c0 >= cols) return;
+#pragma unroll
+  for (int q = 1; q < 8; ++q) {
+    const uint4 t = part[q][cl];
+    m[0] = m[0] > t.x ? m[0] : t.x;
+    m[1] = m[1] > t.y ? m[1] : t.y;
+    m[2] = m[2] > t.z ? m[2] : t.z;
+    m[3] = m[3] > t.w ? m[3] : t.w;
+  }
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+    if (m[j]) atomicMax(work + c0 + j, m[j]);
+}
+
+// Second pass: every thread scales and splits its chunks (split_f16.h: the row image's arithmetic with the scale of
+// each element's column) -- the same 16 bytes at the same offset, so dst may be src; rscale[c] = 1 / s.
+__global__ __launch_bounds__(256) void cols_split_kernel(float* dst, float* rscale, const unsigned* work,
+                                                         const float* src, long long ld, int rows, int cols) {
+  const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5, c0 = (blockIdx.x * 32 + cl) * 4;
+  if (c0 >= cols) return;
+  const long long step = (long long)gridDim.y * 8;
+  float s[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const int sexp = f2g_f16_scale_exp(work[c0 + j]);
+    s[j] = __uint_as_float((unsigned)(127 + sexp) << 23);
+    if (blockIdx.y == 0 && rl == 0) rscale[c0 + j] = __uint_as_float((unsigned)(127 - sexp) << 23);
+  }
+  const float4 s4 = make_float4(s[0], s[1], s[2], s[3]);
+  // four rows at a time: all loads before the first store (dst may be src, which the compiler must assume anyway)
+  for (long long r = (long long)blockIdx.y * 8 + rl; r < rows; r += 4 * step) {
+    float4 v[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (r + q * step < rows) v[q] = *reinterpret_cast<const float4*>(src + (r + q * step) * ld + c0);
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      if (r + q * step < rows) *reinterpret_cast<uint4*>(dst + (r + q * step) * ld + c0) = f2g_f16_split4(v[q], s4);
+  }
 }
 
 // ---- the GEMM -----------------------------------------------------------------------------------------------------
@@ -147,16 +213,203 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(const f2g_gemm_desc d, 
   gemm_epilogue<2, 2>(d.E, acc, M, N, m0, n0, wm, wn, li, h, true);
 }
 
+// ---- the weight gradient: C[m,n] (+)= sum_r A[r,m] B[r,n] over f2g_split_f16x2_cols images ----------------------
+// gemm_leanw3_kernel<false>'s structure (gemm_wgrad.hip has the layout): buffer loads with the K advance in a scalar
+// register (rows past the last one lie behind the resource = zeros; so do the chunks of a partial tile's columns
+// past M / N, whose offsets carry bit 31), the 16-byte chunks stored as they lie in memory into hi and lo planes of
+// 32 rows x 128 halves with the (row & 3) swizzle, fragments through the transposing ds_read_b64_tr_b16, no vector
+// ALU instruction in the K loop.  What differs is what differs between gemm_h3_kernel and the lean kernel: the f16
+// MFMA, two accumulator sets, ONE fragment set per 16-k step (the second accumulator set takes the registers of
+// leanw3's prefetched one), and the rescale by the reciprocal COLUMN scales of both operands before the generic
+// epilogue.  The rescale is linear, so the partial tiles of a K split are rescaled and then added atomically.
+__global__ __launch_bounds__(256, 2) void gemm_h3w_kernel(const f2g_gemm_desc d, int M, int N, int K, int kchunk) {
+  constexpr int PL = 32 * 256;            // bytes of one plane (32 rows x 128 halves)
+  constexpr int BUF = 4 * PL;             // [A hi | A lo | B hi | B lo]
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  unsigned char* sm = reinterpret_cast<unsigned char*>(smem);
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int wm = wave >> 1, wn = wave & 1, li = lane & 31, h = lane >> 5;
+  int m0, n0;
+  tile_of_block(128, 128, m0, n0);
+  const int kbeg = blockIdx.z * kchunk;
+  int kend = kbeg + kchunk;
+  if (kend > K) kend = K;
+  const int nt = (kend - kbeg + BK - 1) / BK;
+  if (nt <= 0) return;
+
+  // staging: thread = (row rid + 8q of the slab, 16-byte chunk c of the 128-wide tile row)
+  const int rid = tid >> 5, c = tid & 31;
+  __amdgpu_buffer_rsrc_t ra = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)d.A.base, 0, (unsigned)((long long)K * d.A.seq_stride * 4), 0x00020000);
+  __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
+      (void*)d.B.base, 0, (unsigned)((long long)K * d.B.seq_stride * 4), 0x00020000);
+  // (M % 4 == 0 and N % 4 == 0: a chunk lies inside the matrix or outside it)
+  const unsigned pastA = m0 + 4 * c < M ? 0u : 0x80000000u, pastB = n0 + 4 * c < N ? 0u : 0x80000000u;
+  unsigned offA[4], offB[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    offA[q] = (unsigned)(((long long)(rid + 8 * q) * d.A.seq_stride + m0 + 4 * c) * 4) | pastA;
+    offB[q] = (unsigned)(((long long)(rid + 8 * q) * d.B.seq_stride + n0 + 4 * c) * 4) | pastB;
+  }
+  const int stepA = (int)(BK * d.A.seq_stride * 4), stepB = (int)(BK * d.B.seq_stride * 4);
+  // LDS store offsets (row r, chunk c): r*256 + (((c >> 3) ^ (r & 3)) << 6) + (c & 7)*8
+  int wofs[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int r = rid + 8 * q;
+    wofs[q] = r * 256 + ((((c >> 3) ^ (r & 3))) << 6) + (c & 7) * 8;
+  }
+  // transposed-fragment addresses: 16-lane group g = (m half, k half), lane i = (row i>>2, quad i&3)
+  const int g = lane >> 4, i16 = lane & 15;
+  const int rrow = (g >> 1) * 8 + (i16 >> 2), sw = i16 >> 2, within = (g & 1) * 32 + (i16 & 3) * 8;
+  int rofA[2], rofB[2];
+#pragma unroll
+  for (int t = 0; t < 2; ++t) {
+    rofA[t] = rrow * 256 + ((((wm * 2 + t) ^ sw)) << 6) + within;
+    rofB[t] = rrow * 256 + ((((wn * 2 + t) ^ sw)) << 6) + within;
+  }
+
+  f32x16 acc[2][2], acx[2][2];
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[mi][ni][e] = acx[mi][ni][e] = 0.f;
+
+  int ka = (int)((long long)kbeg * d.A.seq_stride * 4), kb = (int)((long long)kbeg * d.B.seq_stride * 4);
+  const int ka0 = ka, kb0 = kb;
+  auto gload = [&](bool valid, u32x4 (&la)[4], u32x4 (&lb)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      la[q] = __builtin_amdgcn_raw_buffer_load_b128(ra, offA[q], valid ? ka : ka0, 0);
+      lb[q] = __builtin_amdgcn_raw_buffer_load_b128(rb, offB[q], valid ? kb : kb0, 0);
+    }
+  };
+  auto advance = [&]() {
+    ka += stepA;
+    kb += stepB;
+  };
+  auto lstore = [&](int bufoff, const u32x4 (&la)[4], const u32x4 (&lb)[4]) {
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      unsigned char* pa = sm + bufoff + wofs[q];
+      *reinterpret_cast<u32x2*>(pa) = u32x2{la[q].x, la[q].y};
+      *reinterpret_cast<u32x2*>(pa + PL) = u32x2{la[q].z, la[q].w};
+      *reinterpret_cast<u32x2*>(pa + 2 * PL) = u32x2{lb[q].x, lb[q].y};
+      *reinterpret_cast<u32x2*>(pa + 3 * PL) = u32x2{lb[q].z, lb[q].w};
+    }
+  };
+  // fragments of 16-k step ks: [0..1] = hi of the two sub-tiles, [2..3] = lo
+  auto frags = [&](int bufoff, int ks, f16x8 (&fa)[4], f16x8 (&fb)[4]) {
+    const unsigned char* base = sm + bufoff + ks * 16 * 256;
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      fa[t] = __builtin_bit_cast(f16x8, tr_frag(base + rofA[t]));
+      fa[2 + t] = __builtin_bit_cast(f16x8, tr_frag(base + PL + rofA[t]));
+      fb[t] = __builtin_bit_cast(f16x8, tr_frag(base + 2 * PL + rofB[t]));
+      fb[2 + t] = __builtin_bit_cast(f16x8, tr_frag(base + 3 * PL + rofB[t]));
+    }
+  };
+  auto mfma12 = [&](const f16x8 (&fa)[4], const f16x8 (&fb)[4]) {
+#pragma unroll
+    for (int term = 0; term < 3; ++term)
+#pragma unroll
+      for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+          if (term == 0)
+            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[mi], fb[ni], acc[mi][ni], 0, 0, 0);
+          else
+            acx[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(term == 1 ? fa[mi] : fa[2 + mi],
+                                                                 term == 1 ? fb[2 + ni] : fb[ni], acx[mi][ni], 0, 0, 0);
+        }
+  };
+  // two register stages: slab t's MFMAs run while slab t + 1 (in registers since the previous step) goes to LDS and
+  // the loads of slab t + 2 fly
+  u32x4 xa[4], xb[4], ya[4], yb[4];
+  gload(true, xa, xb);
+  lstore(0, xa, xb);
+  advance();
+  gload(nt > 1, xa, xb);
+  __syncthreads();
+  auto step = [&](int t, int curoff, int nxtoff, const u32x4 (&wa)[4], const u32x4 (&wb)[4], u32x4 (&la)[4],
+                  u32x4 (&lb)[4]) {
+    f16x8 fa[4], fb[4];
+    advance();
+    gload(t + 2 < nt, la, lb);      // past the end: the first slab again (never used)
+    frags(curoff, 0, fa, fb);
+    // (the loads stay in front: left to itself the scheduler sinks them behind the LDS stores, to the barrier, and
+    // the next step waits for them at once)
+    __builtin_amdgcn_sched_barrier(0);
+    mfma12(fa, fb);
+    lstore(nxtoff, wa, wb);
+    __builtin_amdgcn_sched_barrier(0);
+    frags(curoff, 1, fa, fb);
+    mfma12(fa, fb);
+    __builtin_amdgcn_sched_barrier(0);
+    __syncthreads();
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  int t = 0;
+  for (; t + 1 < nt; t += 2) {
+    step(t, 0, BUF, xa, xb, ya, yb);
+    step(t + 1, BUF, 0, ya, yb, xa, xb);
+  }
+  if (t < nt) step(t, 0, BUF, xa, xb, ya, yb);
+
+  // v = (acc0 + 2^-11 acc1) / s_a[m] / s_b[n], the reciprocals one after the other, then the generic epilogue
+  // (a row's scale is loaded once for both column sub-tiles)
+  float sb[2];
+#pragma unroll
+  for (int ni = 0; ni < 2; ++ni) {
+    const int col = n0 + (wn * 2 + ni) * 32 + li;
+    sb[ni] = col < N ? d.B.rscale[col] : 0.f;
+  }
+#pragma unroll
+  for (int mi = 0; mi < 2; ++mi)
+#pragma unroll
+    for (int e = 0; e < 16; ++e) {
+      const int row = m0 + (wm * 2 + mi) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+      const float sa = row < M ? d.A.rscale[row] : 0.f;
+#pragma unroll
+      for (int ni = 0; ni < 2; ++ni)
+        acc[mi][ni][e] = (acc[mi][ni][e] + acx[mi][ni][e] * 0x1p-11f) * sa * sb[ni];
+    }
+  gemm_epilogue<2, 2>(d.E, acc, M, N, m0, n0, wm, wn, li, h, blockIdx.z == 0);
+}
+
 inline bool h3_operand_ok(const f2g_operand& S) {
   return host_plain(S) && !S.alpha && S.rows > 0 && S.cols >= BK && S.cols % BK == 0 && S.cols <= F2G_F16_MAX_K &&
          al16(S.base) && (S.seq_stride & 3) == 0 && S.seq_stride >= S.cols &&
          (long long)S.rows * S.seq_stride * 4 < 0x7ff00000ll;
 }
 
-// 0: not for this kernel; 1: as handed over (both operands f2g_split_f16x2 images with their reciprocal scales);
-// 2: once both fp32 operands are replaced by their images
+// form 2 (weight gradient): what gemm_leanw6_kernel<false> takes for two plain operands, with partial tiles (any
+// M, N that are multiples of 4) and without a bf16 output
+inline bool h3w_operand_ok(const f2g_operand& S) {
+  return host_plain(S) && !S.alpha && S.rows > 0 && S.cols >= 4 && S.cols % 4 == 0 && al16(S.base) &&
+         (S.seq_stride & 3) == 0 && S.seq_stride >= S.cols &&
+         // (the kernel's 32-bit byte offsets reach one slab of 32 rows past the last row: they must not wrap)
+         ((long long)S.rows + 32) * S.seq_stride * 4 < 0x7ff00000ll;
+}
+
+int h3w_ok(const f2g_gemm_desc& d) {
+  if (d.precision != 4 || d.A.rows != d.B.rows || !h3w_operand_ok(d.A) || !h3w_operand_ok(d.B)) return 0;
+  const f2g_epilogue& E = d.E;
+  if (E.x3_out || E.colsum_part_ld > 0 || E.c_bf16 || (d.split_k > 1 && !E.atomic)) return 0;
+  // (the combinations f2g_gemm refuses for every form-2 kernel)
+  if (E.prelu_slope || E.mask_src || (E.aux && !E.alpha_n)) return 0;
+  if (d.A.split == 6 && d.B.split == 6) return d.A.rscale && d.B.rscale ? 1 : 0;
+  return d.A.split == 0 && d.B.split == 0 ? 2 : 0;
+}
+
+// 0: not for these kernels; 1: as handed over (form 0: both operands f2g_split_f16x2 images, form 2: both
+// f2g_split_f16x2_cols images, with their reciprocal scales); 2: once both fp32 operands are replaced by their images
 int h3_ok(const f2g_gemm_desc& d) {
-  if (d.form != 0 || !d.A.base || !d.B.base || !d.E.C || d.A.cols != d.B.cols) return 0;
+  if (!d.A.base || !d.B.base || !d.E.C) return 0;
+  if (d.form == 2) return h3w_ok(d);
+  if (d.form != 0 || d.A.cols != d.B.cols) return 0;
   if (!h3_operand_ok(d.A) || !h3_operand_ok(d.B)) return 0;
   const f2g_epilogue& E = d.E;
   if (d.split_k > 1 || E.x3_out || E.colsum_part_ld > 0 || E.c_bf16) return 0;
@@ -174,15 +427,46 @@ extern "C" int f2g_gemm_f16_ok(const f2g_gemm_desc* dp) { return dp ? h3_ok(*dp)
 
 int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st) {
   if (h3_ok(d) != 1) {
-    f2g_set_error("f2g_gemm precision 4: form 0 over f2g_split_f16x2 images of two plain matrices "
-                  "(f2g_gemm_f16_ok(d) != 1 for this descriptor)");
+    f2g_set_error("f2g_gemm precision 4: form 0 over f2g_split_f16x2 images, or form 2 over f2g_split_f16x2_cols "
+                  "images, of two plain matrices (f2g_gemm_f16_ok(d) != 1 for this descriptor)");
     return F2G_EINVAL;
+  }
+  if (d.form == 2) {
+    const int M = d.A.cols, N = d.B.cols, K = d.A.rows, split = d.split_k > 1 ? d.split_k : 1;
+    const int kchunk = ((K + split - 1) / split + BK - 1) / BK * BK;
+    constexpr int smem = 2 * 4 * 32 * 256;      // [buf][A hi | A lo | B hi | B lo] planes of 32 rows x 128 halves
+    dyn_lds_once<gemm_h3w_kernel>(smem);
+    f2g_note_kernel("h3w", split, 6);
+    hipLaunchKernelGGL(gemm_h3w_kernel, dim3((M + 127) / 128, (N + 127) / 128, (K + kchunk - 1) / kchunk), dim3(256),
+                       smem, st, d, M, N, K, kchunk);
+    return f2g_check_launch();
   }
   const int M = d.A.rows, N = d.B.rows, K = d.A.cols;
   constexpr int smem = 4 * 128 * LDR * 4;
   dyn_lds_once<gemm_h3_kernel>(smem);
   f2g_note_kernel("h3<ep=all>", 1, 6);
   hipLaunchKernelGGL(gemm_h3_kernel, dim3((M + 127) / 128, (N + 127) / 128), dim3(256), smem, st, d, M, N, K);
+  return f2g_check_launch();
+}
+
+extern "C" int f2g_split_f16x2_cols(float* dst, float* rscale, uint32_t* work, const float* src, int64_t ld,
+                                    int32_t rows, int32_t cols, f2g_stream_t stream) {
+  if (!dst || !rscale || !work || !src || rows < 1 || cols < 4 || (cols & 3) || ld < cols || (ld & 3) || !al16(dst) ||
+      !al16(src))
+    return F2G_EINVAL;
+  hipStream_t st = (hipStream_t)stream;
+  const hipError_t zeroed = hipMemsetAsync(work, 0, (size_t)cols * 4, st);
+  if (zeroed != hipSuccess) {
+    f2g_set_error(hipGetErrorString(zeroed));
+    return F2G_ELAUNCH;
+  }
+  const int bands = (cols + 127) / 128;
+  int gy = (rows + 31) / 32, cap = 4096 / bands;
+  if (cap < 1) cap = 1;
+  if (gy > cap) gy = cap;
+  hipLaunchKernelGGL(cols_amax_kernel, dim3(bands, gy), dim3(256), 0, st, work, src, (long long)ld, rows, cols);
+  hipLaunchKernelGGL(cols_split_kernel, dim3(bands, gy), dim3(256), 0, st, dst, rscale, work, src, (long long)ld, rows,
+                     cols);
   return f2g_check_launch();
 }
 

@@ -1,5 +1,6 @@
 // Row routine of f2g_split_f16x2 (gemm_f16.hip) and of its f2g_multi entry (multi.hip: weight images rebuilt in
-// one batched launch): the two-piece fp16 image of fp32 rows and their reciprocal scales.
+// one batched launch): the two-piece fp16 image of fp32 rows and their reciprocal scales.  f2g_split_f16x2_cols
+// (gemm_f16.hip: the K-major operands of a weight gradient, one scale per COLUMN) shares the arithmetic below.
 #pragma once
 #include "common.h"
 
@@ -40,6 +41,21 @@ __device__ __forceinline__ uint4 f2g_f16_split4(const float4& v, float s) {
   return make_uint4(h01, h23, l01, l23);
 }
 
+// ... with one scale per element (four columns of a K-major operand)
+__device__ __forceinline__ uint4 f2g_f16_split4(const float4& v, const float4& s) {
+  unsigned l01, l23;
+  const unsigned h01 = f2g_f16_pair(__fmul_rn(v.x, s.x), __fmul_rn(v.y, s.y), l01);
+  const unsigned h23 = f2g_f16_pair(__fmul_rn(v.z, s.z), __fmul_rn(v.w, s.w), l23);
+  return make_uint4(h01, h23, l01, l23);
+}
+
+// Exponent of the scale s = 2^sexp of a row (or column) whose largest sign-less bit pattern is m
+__device__ __forceinline__ int f2g_f16_scale_exp(unsigned m) {
+  int sexp = 14 - ((int)(m >> 23) - 127);          // (a subnormal amax: beyond the clamp either way)
+  sexp = sexp > 126 ? 126 : (sexp < -126 ? -126 : sexp);
+  return (m == 0u || m >= 0x7f800000u) ? 0 : sexp;
+}
+
 // One wave per row: its largest magnitude is the integer maximum of the sign-less bit patterns (the same order as
 // the values'; a NaN ranks above inf; a fixed butterfly, no atomics), then every aligned group of four floats is
 // stored as four hi and four lo halves -- the 16 bytes of f2g_split_bf16 at the same offset.  dst may be src.
@@ -71,9 +87,7 @@ __device__ __forceinline__ void f2g_split_f16x2_rows(float* dst, float* __restri
       const unsigned t = (unsigned)__shfl_xor((int)m, o);
       m = m > t ? m : t;
     }
-    int sexp = 14 - ((int)(m >> 23) - 127);          // (a subnormal amax: beyond the clamp either way)
-    sexp = sexp > 126 ? 126 : (sexp < -126 ? -126 : sexp);
-    if (m == 0u || m >= 0x7f800000u) sexp = 0;
+    const int sexp = f2g_f16_scale_exp(m);
     const float s = __uint_as_float((unsigned)(127 + sexp) << 23);
     if (lane == 0) rscale[r] = __uint_as_float((unsigned)(127 - sexp) << 23);
     uint4* d4 = reinterpret_cast<uint4*>(dst + r * ld);

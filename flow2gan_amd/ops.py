@@ -447,7 +447,7 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
     padded to whole K slabs): what bench.py's FLOP count uses; the launch itself ignores them.
     split_k: 0 = let the library decide (forms 0/1: split-K onto a zeroed output when the tile
     grid would leave most of the last wave of CUs idle), 1 = off, > 1 = as given."""
-    global FP16X3_LAUNCHES
+    global FP16X3_LAUNCHES, FP16X3_WGRAD_LAUNCHES
     if form == 1:
         # data gradient C[r,n] = sum_k A[r,k] W[k,n] as a forward GEMM against the cached transpose
         # W^T [n][k]: same products in the same order, and the lean forward kernel applies
@@ -512,6 +512,15 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
             d.A, d.B = _f16_operand(A), _f16_operand(Bm)
             f16 = True
             FP16X3_LAUNCHES += 1
+    if GEMM_PRECISION == 3 and FP16X3 and form == 2 and atomic and A.split == 0 and Bm.split == 0 \
+            and A.lrelu_src is None and A.rows >= FP16X3_WGRAD_MIN_ROWS and out.dtype == torch.float32:
+        # fp16x3 weight gradient: both operands are activations, K-major -- their f2g_split_f16x2_cols images (one
+        # scale per column) are made here, per call; what the library declines goes the bf16x6 way
+        d.precision = 4
+        if L.lib.f2g_gemm_f16_ok(C.byref(d)) == 2:
+            d.A, d.B = _f16_cols_operand(A), _f16_cols_operand(Bm)
+            f16 = True
+            FP16X3_WGRAD_LAUNCHES += 1
     if GEMM_PRECISION == 3 and f16:
         if x3_out:
             out._f2g_x3_bad = True     # (no image from this kernel: the next consumer builds its own)
@@ -934,6 +943,24 @@ def _f16_operand(o: Operand) -> Operand:
     return n
 
 
+def _f16_cols_operand(o: Operand) -> Operand:
+    """Copy of a plain fp32 K-major operand of a weight gradient over its f2g_split_f16x2_cols image (same
+    addressing; one scale per column), made per call: [image: rows * ld floats | reciprocal column scales: cols |
+    the call's scratch words: cols] in one allocation.  The image is rows * ld floats, not (rows - 1) * ld + cols:
+    gemm_h3w_kernel's buffer resource ends at rows * seq_stride * 4 bytes."""
+    rows, cols, ld = o.rows, o.cols, o.seq_stride
+    buf = torch.empty(rows * ld + 2 * cols, device=o._keep[0].device, dtype=torch.float32)
+    call("f2g_split_f16x2_cols", ptr(buf), ptr(buf) + 4 * rows * ld, ptr(buf) + 4 * (rows * ld + cols), o.base, ld,
+         rows, cols)
+    n = Operand()
+    C.memmove(C.byref(n), C.byref(o), C.sizeof(Operand))
+    n.base = ptr(buf)
+    n.rscale = ptr(buf) + 4 * rows * ld
+    n.split = 6
+    n._keep = (buf,) + tuple(o._keep)
+    return n
+
+
 CONV32_X6 = opt("conv32_x6", True)    # bf16x6 mode: fp32-class direct MRD convs (bench.py reads it)
 
 
@@ -1274,6 +1301,16 @@ FP16X3_MIN_K = opt("fp16x3_min_k", 160)
 # in place: 0 of 36 launches lose by more than their spread, stage 1 31.46 against 31.12 ms, stage 2 162.11 : 161.70
 FP16X3_MIN_N = opt("fp16x3_min_n", 2048)
 FP16X3_LAUNCHES = 0        # launches gemm_h3_kernel took (tests and tools)
+# fewest reduction rows at which a weight gradient (form 2, two plain activation operands) goes to gemm_h3w_kernel:
+# both operands pay f2g_split_f16x2_cols (two passes: 12 bytes of HBM traffic per element, the GEMM reads 4 more,
+# against 4 for gemm_leanw6_kernel's in-kernel split).  Measured per launch, both image calls included, on one box
+# (tools/fp16x3_wgrad_shapes.py -> profiles/fp16x3_wgrad_shapes.txt): no shape of the generator wins -- 1.06-1.24 of
+# the bf16x6 time at (768, 2304), 1.48-1.52 at (512, 1536), 1.72-1.86 at (384, 1152); stage 1 35.77 against 32.53 ms
+# with every weight gradient on the kernel.  Hence the default: FP16X3_WGRAD_OFF = the route is disabled (tests and
+# the tool lower it)
+FP16X3_WGRAD_OFF = 1 << 30
+FP16X3_WGRAD_MIN_ROWS = opt("fp16x3_wgrad_min_rows", FP16X3_WGRAD_OFF)
+FP16X3_WGRAD_LAUNCHES = 0  # launches gemm_h3w_kernel took (tests and tools)
 
 
 def set_gemm_precision(name: str) -> None:

@@ -82,7 +82,9 @@ typedef struct {
    * 2: `base` is a TRUE bf16 tensor (f2g_to_bf16 or a bf16 producer): strides / offsets stay in
    *    elements, the reduction needs whole 64-element slabs (precision 2, lean kernel only);
    * 5: `base` holds the two-piece fp16 image written by f2g_split_f16x2 (same addressing as the plain fp32
-   *    matrix it was made of) and `rscale` its reciprocal row scales (precision 4, form 0, plain matrices only) */
+   *    matrix it was made of) and `rscale` its reciprocal row scales (precision 4, form 0, plain matrices only);
+   * 6: `base` holds the two-piece fp16 image written by f2g_split_f16x2_cols (same addressing as the plain fp32
+   *    matrix) and `rscale` its reciprocal COLUMN scales, `cols` floats (precision 4, form 2, plain matrices only) */
   int32_t split;
   const float* alpha;
   const float* lrelu_src;
@@ -92,7 +94,8 @@ typedef struct {
    * with is zero there -- the weight gradient of a conv whose gradient map carries zero halo rows.
    * Only the split-bf16 weight-gradient kernel looks at it. */
   int32_t unbounded;
-  /* split = 5 only: 1 / s per row of the operand (f2g_split_f16x2), `rows` floats; NULL otherwise */
+  /* split = 5: 1 / s per row of the operand (f2g_split_f16x2), `rows` floats; split = 6: 1 / s per column
+   * (f2g_split_f16x2_cols), `cols` floats; NULL otherwise */
   const float* rscale;
 } f2g_operand;
 
@@ -179,7 +182,9 @@ typedef struct {
    *     for form 2, with E.atomic when split_k > 1 -- split into pieces inside the kernel;
    * 4 = fp16x3: fp32-class products from TWO fp16 pieces per operand, three MFMAs per product (per-product error
    *     <= 3 * 2^-22): form 0 over two plain matrices, both given as f2g_split_f16x2 images (f2g_operand.split = 5
-   *     with rscale).  A descriptor f2g_gemm_f16_ok does not answer with 1 is F2G_EINVAL, never run elsewhere. */
+   *     with rscale); form 2 (weight gradient) over two plain matrices, both given as f2g_split_f16x2_cols images
+   *     (split = 6 with rscale: one scale per column, which leaves the sum over rows), E.atomic when split_k > 1.
+   *     A descriptor f2g_gemm_f16_ok does not answer with 1 is F2G_EINVAL, never run elsewhere. */
   int32_t precision;
   int32_t _pad3;
 } f2g_gemm_desc;
@@ -247,15 +252,35 @@ int32_t f2g_gemm_colsum_part_rows(const f2g_gemm_desc* d);
 int f2g_split_f16x2(float* dst, float* rscale, const float* src, int64_t ld, int32_t rows, int32_t K,
                     f2g_stream_t stream);
 int f2g_gemm_f16_ok(const f2g_gemm_desc* d);
+/* The image of a K-MAJOR operand of a precision-4 weight gradient (form 2: C[m,n] (+)= sum_r A[r,m] B[r,n]; the
+ * reduction walks rows, so the power-of-two scale that leaves the sum is one per COLUMN).  src: (rows, cols)
+ * row-major fp32, row stride ld floats; cols % 4 == 0, ld % 4 == 0, ld >= cols, rows >= 1, dst and src 16-byte
+ * aligned (F2G_EINVAL otherwise).  The arithmetic of f2g_split_f16x2 with "row" read as "column": s[c] = 2^(14 -
+ * floor(log2 max_r |x[r,c]|)), exponent clamped to +-126, s = 1 for an all-zero column and for one holding an inf or
+ * a NaN; y = x s, hi = fp16(y), lo = fp16(2^11 (y - hi)).  dst (same row stride; may be src) receives the layout of
+ * f2g_split_bf16 -- every aligned group of four floats, four consecutive columns of a row, becomes its four hi
+ * halves followed by its four lo halves at the same offset; nothing outside the rows' `cols` columns is written.
+ * rscale[c] = 1 / s[c], `cols` floats.  work: `cols` 32-bit words of scratch, zeroed by the call itself on the
+ * stream.  Two passes, no allocation, no synchronisation: the column maxima (integer maxima of the sign-less bit
+ * patterns: per thread, per block, atomicMax across blocks -- a maximum does not depend on the order, the image is
+ * reproducible), then the split.  12 bytes of HBM traffic per element, and the GEMM reads 4 more.
+ * f2g_gemm with precision = 4, form = 2 computes, for two such images over the same rows, acc0 += hi_a hi_b,
+ * acc1 += hi_a lo_b + lo_a hi_b and hands v = (acc0 + 2^-11 acc1) * rscale_a[m] * rscale_b[n] to the generic
+ * epilogue; cols % 4 == 0 for both operands (partial 128 x 128 tiles are fine), split_k > 1 with E.atomic only (the
+ * rescale is linear: partial tiles are rescaled, then added), no window operand, no bf16 output, no x3_out, no
+ * colsum_part_ld.  f2g_gemm_f16_ok answers for form 2 as for form 0 (2 = once both fp32 operands are replaced by
+ * their column images), asked with precision = 4 set as for the launch: 0 at any other precision.  f2g_gemm_last_kernel reports "h3w". */
+int f2g_split_f16x2_cols(float* dst, float* rscale, uint32_t* work, const float* src, int64_t ld, int32_t rows,
+                         int32_t cols, f2g_stream_t stream);
 
 /* Kernel family the last f2g_gemm call dispatched to (benchmark diagnostics, not thread safe):
  * 0 generic MFMA kernels, 1 lean kernel, 2 lean kernel in stream-K mode, 3 narrow VALU kernels,
  * 4 the precision-3 kernels, 5 the precision-3 kernel for <= 32 output columns (gemm_x6n_kernel),
- * 6 the fp16x3 kernel (precision 4). */
+ * 6 the fp16x3 kernels (precision 4). */
 int f2g_gemm_last_path(void);
 /* Kernel instance the last f2g_gemm call launched (tests and diagnostics, not thread safe; "" when it
  * launched nothing), e.g. "lean<sk=1,ep=3,pm=0>" (lean kernel: stream-K, epilogue instance, operand mode),
- * "lean_tall<ep=2,pm=1>", "lean_tap<ep=3>", "narrow_wgrad4<4>", "x6f<wimg=1>", "h3<ep=all>" or "generic<F1,GF,PF> split=3"
+ * "lean_tall<ep=2,pm=1>", "lean_tap<ep=3>", "narrow_wgrad4<4>", "x6f<wimg=1>", "h3<ep=all>", "h3w" or "generic<F1,GF,PF> split=3"
  * (generic MFMA tiles: form, loader modes of A and B, and the K split when > 1). */
 const char* f2g_gemm_last_kernel(void);
 
