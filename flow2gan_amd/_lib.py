@@ -239,6 +239,7 @@ _SIGS = {
     "f2g_split_bf16x3": [_P, _P, _L, _I, _I],
     "f2g_split_f16x2": [_P, _P, _P, _L, _I, _I],
     "f2g_split_f16x2_cols": [_P, _P, _P, _P, _L, _I, _I],
+    "f2g_split_f16x2_seq": [_P, _P, _P, _L, _I, _I],
     "f2g_multi": [C.POINTER(MultiDesc)],
 }
 EXPORTS = sorted(list(_SIGS) + ["f2g_version", "f2g_last_error", "f2g_gemm_last_path", "f2g_gemm_last_kernel",

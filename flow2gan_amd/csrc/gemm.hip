@@ -893,13 +893,13 @@ extern "C" int f2g_gemm(const f2g_gemm_desc* dp, f2g_stream_t stream) {
   hipStream_t st = (hipStream_t)stream;
   int split = d.split_k > 0 ? d.split_k : 1;
   if (d.E.colsum_part_ld > 0 && f2g_gemm_colsum_part_rows(dp) == 0) {
-    f2g_set_error("f2g_gemm: E.colsum_part_ld needs a precision-3 launch with the wide epilogue "
+    f2g_set_error("f2g_gemm: E.colsum_part_ld needs a launch with the wide epilogue "
                   "(f2g_gemm_colsum_part_rows(d) == 0 for this descriptor)");
     return F2G_EINVAL;
   }
   if (d.precision == 4) return f2g_gemm_h3(d, st);   // fp16x3: its own kernels or F2G_EINVAL
-  if (d.A.split == 5 || d.B.split == 5 || d.A.split == 6 || d.B.split == 6) {
-    f2g_set_error("f2g_gemm: f2g_split_f16x2 / f2g_split_f16x2_cols images (split = 5 / 6) belong to precision 4");
+  if ((d.A.split >= 5 && d.A.split <= 7) || (d.B.split >= 5 && d.B.split <= 7)) {
+    f2g_set_error("f2g_gemm: f2g_split_f16x2 / _cols / _seq images (split = 5 / 6 / 7) belong to precision 4");
     return F2G_EINVAL;
   }
   if (d.precision == 3 && d.form == 2) {

@@ -1,5 +1,5 @@
 // What more than one of the GEMM translation units needs (gemm.hip, gemm_lean.hip, gemm_wgrad.hip, gemm_x6.hip,
-// gemm_x6p.hip, gemm_f16.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
+// gemm_x6p.hip, gemm_f16.hip, gemm_f16p.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
 // three-piece split, the LDS barrier, the lab switches, and the host functions that cross those files.  Everything
 // defined here has internal linkage; no GEMM file includes another.
 #pragma once
@@ -21,6 +21,11 @@ int f2g_gemm_x6(const f2g_gemm_desc& d, hipStream_t st);
 // gemm_f16.hip: precision 4 -- form 0 over f2g_split_f16x2 images, form 2 over f2g_split_f16x2_cols images (checks
 // the descriptor, launches)
 int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st);
+// gemm_f16p.hip: precision 4, form 0 over stride-1 windows of 5 or 2 positions of a halo map (gemm_h3p_kernel).
+// f2g_h3p_ok: 1 = runs as handed over (both operands f2g_split_f16x2_seq images with their reciprocal scales), 2 = once
+// both fp32 operands are replaced by those images, 0 = not for this kernel; `taps` receives 5 or 2
+int f2g_h3p_ok(const f2g_gemm_desc& d, int* taps);
+int f2g_launch_h3p(const f2g_gemm_desc& d, int taps, hipStream_t st);
 
 // ---- lab switches (product builds: both 0) ---------------------------------------------------------------------
 // F2G_LABVAR (tools/micro/build_variants.sh; timing only): ablations of the bf16 lean K loop (gemm_lean.hip) --
@@ -82,6 +87,29 @@ inline bool host_plain(const f2g_operand& S) {
 }
 
 inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// extent in elements of what the A operand's rows may touch, or 0 if precision 3 cannot read it
+inline long long x6_a_extent(const f2g_operand& A) {
+  if (host_plain(A)) return (long long)A.rows * A.cols;
+  // single-segment windows that never leave their sequence (halo layouts), everything on slab boundaries
+  if (A.P1 != 1 || A.L1 != 1 || A.P0 < 1 || A.seglen < A.cols || A.reflect || A.pad0 > 0 || A.rows % A.P0)
+    return 0;
+  const long long step = (long long)A.step0 * A.unit, off = -(long long)A.pad0 * A.unit;
+  if ((step % 32) || (off % 32) || (A.seq_stride % 32) || step < 0) return 0;
+  if ((long long)(A.P0 - 1) * step + off + A.cols > A.L0u) return 0;
+  return (long long)(A.rows / A.P0 - 1) * A.seq_stride + A.L0u;
+}
+
+// stride-1 conv windows of TAPS positions x C channels over a halo map image (gemm_x6p_kernel, gemm_h3p_kernel)
+inline bool x6_tap_ok(const f2g_gemm_desc& d, int taps) {
+  const f2g_operand& A = d.A;
+  if (host_plain(A) || A.P1 != 1 || A.step0 != 1 || A.unit < 32 || (A.unit % 32)) return false;
+  if (A.cols != taps * A.unit || A.seglen < A.cols || (A.seq_stride % A.unit) || (A.pad0 > 0)) return false;
+  const int HpIn = (int)(A.seq_stride / A.unit);
+  if (A.P0 < 8 || HpIn < A.P0) return false;
+  // staged positions of a tile: its rows, the taps' overhang, the extra positions of every sequence end inside
+  return 128 + taps - 1 + (HpIn - A.P0) * (128 / A.P0 + 1) <= 160;
+}
 
 // Raises the dynamic-LDS limit of the kernels KERNS to `bytes`, the first time a launcher comes by.
 template <auto... KERNS>

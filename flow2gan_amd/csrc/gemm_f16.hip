@@ -1,6 +1,7 @@
 // fp16x3: fp32-class products from TWO scaled fp16 pieces per operand, three MFMAs per product (gemm.hip has the
 // family, gemm_common.h what the GEMM files share).  f2g_split_f16x2 writes the operand images, gemm_h3_kernel reads them;
 // f2g_split_f16x2_cols writes the images of K-major operands (one scale per column), gemm_h3w_kernel reads those.
+// (gemm_f16p.hip: f2g_split_f16x2_seq and gemm_h3p_kernel, the same over stride-1 windows of a halo map.)
 #include <stddef.h>
 #include <stdint.h>
 
@@ -404,11 +405,14 @@ int h3w_ok(const f2g_gemm_desc& d) {
   return d.A.split == 0 && d.B.split == 0 ? 2 : 0;
 }
 
-// 0: not for these kernels; 1: as handed over (form 0: both operands f2g_split_f16x2 images, form 2: both
-// f2g_split_f16x2_cols images, with their reciprocal scales); 2: once both fp32 operands are replaced by their images
+// 0: not for these kernels; 1: as handed over (form 0: both operands f2g_split_f16x2 images -- over stride-1 windows
+// of a halo map: f2g_split_f16x2_seq images --, form 2: both f2g_split_f16x2_cols images, with their reciprocal
+// scales); 2: once both fp32 operands are replaced by their images
 int h3_ok(const f2g_gemm_desc& d) {
   if (!d.A.base || !d.B.base || !d.E.C) return 0;
   if (d.form == 2) return h3w_ok(d);
+  // windows of a halo map, or f2g_split_f16x2_seq images: the tap-walking kernel (gemm_f16p.hip) or nothing
+  if (d.form == 0 && (!host_plain(d.A) || d.A.split == 7 || d.B.split == 7)) return f2g_h3p_ok(d, nullptr);
   if (d.form != 0 || d.A.cols != d.B.cols) return 0;
   if (!h3_operand_ok(d.A) || !h3_operand_ok(d.B)) return 0;
   const f2g_epilogue& E = d.E;
@@ -428,8 +432,14 @@ extern "C" int f2g_gemm_f16_ok(const f2g_gemm_desc* dp) { return dp ? h3_ok(*dp)
 int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st) {
   if (h3_ok(d) != 1) {
     f2g_set_error("f2g_gemm precision 4: form 0 over f2g_split_f16x2 images, or form 2 over f2g_split_f16x2_cols "
-                  "images, of two plain matrices (f2g_gemm_f16_ok(d) != 1 for this descriptor)");
+                  "images, of two plain matrices, or form 0 over f2g_split_f16x2_seq images of stride-1 windows of 5 or "
+                  "2 positions (f2g_gemm_f16_ok(d) != 1 for this descriptor)");
     return F2G_EINVAL;
+  }
+  if (d.form == 0 && d.A.split == 7) {
+    int taps = 0;
+    (void)f2g_h3p_ok(d, &taps);
+    return f2g_launch_h3p(d, taps, st);
   }
   if (d.form == 2) {
     const int M = d.A.cols, N = d.B.cols, K = d.A.rows, split = d.split_k > 1 ? d.split_k : 1;

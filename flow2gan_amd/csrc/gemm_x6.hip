@@ -699,17 +699,8 @@ __global__ __launch_bounds__(256, 2) void gemm_x6n_kernel(const f2g_gemm_desc d,
   }
 }
 
-// extent in elements of what the A operand's rows may touch, or 0 if precision 3 cannot read it
-static long long x6_a_extent(const f2g_operand& A) {
-  if (host_plain(A)) return (long long)A.rows * A.cols;
-  // single-segment windows that never leave their sequence (halo layouts), everything on slab boundaries
-  if (A.P1 != 1 || A.L1 != 1 || A.P0 < 1 || A.seglen < A.cols || A.reflect || A.pad0 > 0 || A.rows % A.P0)
-    return 0;
-  const long long step = (long long)A.step0 * A.unit, off = -(long long)A.pad0 * A.unit;
-  if ((step % 32) || (off % 32) || (A.seq_stride % 32) || step < 0) return 0;
-  if ((long long)(A.P0 - 1) * step + off + A.cols > A.L0u) return 0;
-  return (long long)(A.rows / A.P0 - 1) * A.seq_stride + A.L0u;
-}
+// (x6_a_extent -- the extent of what the A operand's rows may touch -- and x6_tap_ok -- stride-1 conv windows of
+// TAPS positions over a halo map image -- live in gemm_common.h: gemm_f16p.hip applies them too)
 
 static bool x6_shape_ok(const f2g_gemm_desc& d) {
   if (d.form != 0 || !host_plain(d.B) || d.A.cols != d.B.cols) return false;
@@ -724,17 +715,6 @@ static bool x6_shape_ok(const f2g_gemm_desc& d) {
     if (E.P0o > 0 ? ((E.seq_stride_o | E.row_stride_o | E.off_o) & 7) != 0 : (E.ldc & 7) != 0) return false;
   }
   return true;
-}
-
-// stride-1 conv windows of TAPS positions x C channels over a halo map image (gemm_x6t_kernel)
-static bool x6_tap_ok(const f2g_gemm_desc& d, int taps) {
-  const f2g_operand& A = d.A;
-  if (host_plain(A) || A.P1 != 1 || A.step0 != 1 || A.unit < 32 || (A.unit % 32)) return false;
-  if (A.cols != taps * A.unit || A.seglen < A.cols || (A.seq_stride % A.unit) || (A.pad0 > 0)) return false;
-  const int HpIn = (int)(A.seq_stride / A.unit);
-  if (A.P0 < 8 || HpIn < A.P0) return false;
-  // staged positions of a tile: its rows, the taps' overhang, the extra positions of every sequence end inside
-  return 128 + taps - 1 + (HpIn - A.P0) * (128 / A.P0 + 1) <= 160;
 }
 
 // 1: the launch takes the wide epilogue (x6_epilogue.h; else the generic one + image read-back)
@@ -848,9 +828,11 @@ extern "C" int f2g_gemm_x6_ok(const f2g_gemm_desc* d) {
 // Rows of the partial column-sum matrices (E.colsum_part_ld > 0) the launch of `d` writes: one per 64 output
 // rows of whole tiles -- or 0 when the kernel x6_choose picks has no wide epilogue.
 extern "C" int32_t f2g_gemm_colsum_part_rows(const f2g_gemm_desc* dp) {
-  if (!dp || dp->precision != 3 || dp->form != 0) return 0;
+  if (!dp || (dp->precision != 3 && dp->precision != 4) || dp->form != 0) return 0;
   f2g_gemm_desc d = *dp;
   if (d.E.colsum_part_ld <= 0) d.E.colsum_part_ld = 4;          // (alignment of the pointers is the caller's)
+  // precision 4: the tap-walking kernel alone has the wide epilogue (gemm_f16p.hip; 256-row tiles)
+  if (d.precision == 4) return f2g_h3p_ok(d, nullptr) ? 4 * ((d.A.rows + 255) / 256) : 0;
   if (!x6_wide(d)) return 0;
   const int M = d.A.rows;
   switch (x6_choose(d).kind) {

@@ -436,6 +436,22 @@ def win2d(t, nseq: int, H: int, W: int, Cin: int, W_out: int, kh: int, kw: int, 
     return o
 
 
+def _ask_with_x3_out(d, out, out_offset: int, x3_out: bool, prelu_out, ask):
+    """Set d.E.x3_out to the reserved three-piece image of `out` (x3_reserve) where the caller wants it written and
+    the store qualifies, then ask() the library about d; if it declines, drop the image (its alignment conditions:
+    the GEMM alone may still go) and ask again.  Returns ask()'s last answer; d.E.x3_out says whether the image is
+    written.  Shared by the bf16x6 route and the fp16x3 tap-walking route of gemm()."""
+    buf = getattr(out, "_f2g_x3_buf", None) if x3_out else None
+    if buf is not None and X6F != 1 and not getattr(out, "_f2g_x3_bad", False) \
+            and out_offset % 32 == 0 and prelu_out is None:
+        d.E.x3_out = ptr(buf) + (out_offset // 32) * 192
+    how = ask()
+    if not how and d.E.x3_out:
+        d.E.x3_out = None
+        how = ask()
+    return how
+
+
 def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None, *, bias=None,
          res=None, ldres: Optional[int] = None, gamma=None, aux=None, ldaux: Optional[int] = None,
          alpha_n=None, colsum_alpha=None, colsum=None, lrelu: float = 0.0, scale: float = 0.0,
@@ -447,7 +463,7 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
     padded to whole K slabs): what bench.py's FLOP count uses; the launch itself ignores them.
     split_k: 0 = let the library decide (forms 0/1: split-K onto a zeroed output when the tile
     grid would leave most of the last wave of CUs idle), 1 = off, > 1 = as given."""
-    global FP16X3_LAUNCHES, FP16X3_WGRAD_LAUNCHES
+    global FP16X3_LAUNCHES, FP16X3_WGRAD_LAUNCHES, FP16X3_TAP_LAUNCHES
     if form == 1:
         # data gradient C[r,n] = sum_k A[r,k] W[k,n] as a forward GEMM against the cached transpose
         # W^T [n][k]: same products in the same order, and the lean forward kernel applies
@@ -502,7 +518,7 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
     d.split_k = split_k
     d.precision = GEMM_PRECISION
     f16 = False
-    if GEMM_PRECISION == 3 and FP16X3 and form == 0 and A.split == 0 and Bm.split == 0 \
+    if GEMM_PRECISION == 3 and FP16X3 and form == 0 and A.split == 0 and Bm.split == 0 and A.P0 == 1 and A.P1 == 1 \
             and A.cols >= FP16X3_MIN_K and Bm.rows >= FP16X3_MIN_N and split_k <= 1 and out.dtype == torch.float32:
         # fp16x3: two plain matrices (a data gradient arrives here as form 0 over the cached transpose) as
         # f2g_split_f16x2 images -- the weight's from the derived-weight cache, the activation's made here.  The
@@ -521,8 +537,30 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
             d.A, d.B = _f16_cols_operand(A), _f16_cols_operand(Bm)
             f16 = True
             FP16X3_WGRAD_LAUNCHES += 1
+    if GEMM_PRECISION == 3 and FP16X3 and form == 0 and A.split == 0 and Bm.split == 0 and A.P1 == 1 and A.P0 > 1 \
+            and A.step0 == 1 and A.cols in (5 * A.unit, 2 * A.unit) and A.rows >= FP16X3_TAP_MIN_ROWS \
+            and A.cols >= X6_MIN_K \
+            and not atomic and split_k <= 1 and out.dtype == torch.float32 and _f16_seq_window_ok(A):
+        # fp16x3 over stride-1 windows of 5 or 2 positions of a contiguous halo map (the MPD's 1024-channel layer, its
+        # data gradient, the residue data gradients of the stride-3 layers): f2g_split_f16x2_seq images, one scale per
+        # sequence -- the map's made here, per call, the weight's from the derived-weight cache.  Reductions from
+        # X6_MIN_K on: the launches the bf16x6 mode gives to its image kernels (a shorter one reads the fp32 map as
+        # it is there, without any image pass).  The kernel has the
+        # bf16x6 kernels' wide epilogue, so the output's three-piece image is written as there (its consumers stay
+        # the bf16x6 kernels).  What the library declines goes the bf16x6 way
+        d.precision = 4
+        how = _ask_with_x3_out(d, out, out_offset, x3_out, prelu_out,
+                               lambda: L.lib.f2g_gemm_f16_ok(C.byref(d)) == 2)
+        if how:
+            d.A, d.B = _f16_seq_operand(A), _f16_seq_operand(Bm)
+            f16 = True
+            FP16X3_TAP_LAUNCHES += 1
+            if x3_out and d.E.x3_out:
+                out._f2g_x3 = out._f2g_x3_buf
+        else:
+            d.E.x3_out = None
     if GEMM_PRECISION == 3 and f16:
-        if x3_out:
+        if x3_out and not d.E.x3_out:
             out._f2g_x3_bad = True     # (no image from this kernel: the next consumer builds its own)
     elif GEMM_PRECISION == 3:
         d.precision = 0       # (what does not qualify below runs on the exact fp32 MFMA)
@@ -542,14 +580,7 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
             # writer of the buffer must do so, or the image is dropped: x3_reserve / _x3_operand).  The
             # library is asked with the descriptor as it will be launched (f2g_gemm_x6_ok applies the
             # tests of f2g_gemm's own dispatch, E.x3_out included)
-            buf = getattr(out, "_f2g_x3_buf", None) if x3_out else None
-            if buf is not None and X6F != 1 and not getattr(out, "_f2g_x3_bad", False) \
-                    and out_offset % 32 == 0 and prelu_out is None:
-                d.E.x3_out = ptr(buf) + (out_offset // 32) * 192
-            how = L.lib.f2g_gemm_x6_ok(C.byref(d))
-            if not how and d.E.x3_out:      # (the image's alignment conditions: the GEMM alone may still go)
-                d.E.x3_out = None
-                how = L.lib.f2g_gemm_x6_ok(C.byref(d))
+            how = _ask_with_x3_out(d, out, out_offset, x3_out, prelu_out, lambda: L.lib.f2g_gemm_x6_ok(C.byref(d)))
             if how:
                 if in_kernel and not (how & 4):
                     # the in-kernel split cannot read these views (alignment / strides): the image
@@ -586,7 +617,7 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
             # the K loop); weights come from the derived-weight cache, activations are split here
             d.A, d.B = _split_operand(A), _split_operand(Bm)
     parts = None
-    if COLSUM_PARTS and d.precision == 3 and form == 0 and (colsum is not None or colsum_alpha is not None) \
+    if COLSUM_PARTS and d.precision in (3, 4) and form == 0 and (colsum is not None or colsum_alpha is not None) \
             and A.rows >= COLSUM_PARTS_MIN_ROWS:
         # d(bias) / d(PReLU slope) column sums of a precision-3 forward-form launch as PARTIAL rows (one per 64
         # output rows, plain stores) summed by one f2g_colsum per vector, instead of rows / 64 same-address
@@ -939,6 +970,52 @@ def _f16_operand(o: Operand) -> Operand:
     n.base = ptr(buf)
     n.rscale = ptr(buf) + 4 * soff
     n.split = 5
+    n._keep = (buf,) + tuple(o._keep)
+    return n
+
+
+def split_f16_seq(t, nseq: int, seq_floats: int, ld: Optional[int] = None, offset: int = 0):
+    """f2g_split_f16x2_seq image of `nseq` runs of `seq_floats` floats of `t`, `ld` floats apart, from `offset` floats
+    in: one allocation [image: nseq * ld floats, the runs' own addressing | reciprocal scales: nseq]."""
+    ld = seq_floats if ld is None else ld
+    buf = torch.empty(nseq * ld + nseq, device=t.device, dtype=torch.float32)
+    call("f2g_split_f16x2_seq", ptr(buf), ptr(buf) + 4 * nseq * ld, ptr(t) + 4 * offset, ld, nseq, seq_floats)
+    return buf
+
+
+def _f16_seq_window_ok(o: Operand) -> bool:
+    """windows over whole sequences of a contiguous fp32 buffer, from the start of one of them.  The per-sequence
+    maximum of f2g_split_f16x2_seq covers EVERY float of a sequence, the positions no window reads included: the
+    route relies on the buffer being fully initialised -- _halo_rows zeroes the halo rows and the producers write
+    every interior row, which holds for the MPD maps (a stray inf / NaN there would set the sequence's scale to 1,
+    a stray huge value would push its windows towards the floor term)."""
+    t = o._keep[0]
+    if t is None or t.dtype != torch.float32 or not t.is_contiguous() or o.seq_stride % 32 or o.rows % o.P0:
+        return False
+    off = (o.base - ptr(t)) // 4
+    return off % o.seq_stride == 0 and off + (o.rows // o.P0) * o.seq_stride <= t.numel() and ptr(t) % 16 == 0
+
+
+def _f16_seq_operand(o: Operand) -> Operand:
+    """Copy of an operand of the fp16x3 tap-walking route over its f2g_split_f16x2_seq image (same addressing, the
+    reciprocal scales behind the image): a window operand's runs are its sequences (made here, per call), a plain
+    weight matrix's are its rows (cached for weights and cached re-layouts of weights; built by a launch of its own
+    at first use -- also when a batched rebuild replays the chain, which it then flushes in front of itself)."""
+    t = o._keep[0]
+    off = (o.base - ptr(t)) // 4
+    if o.P0 == 1 and o.P1 == 1:
+        nseq, run, ld = o.rows, o.cols, o.seq_stride
+        tag = ("f16x2seq", off, nseq, run, ld)
+        buf = derived(t, tag, lambda tt: split_f16_seq(tt, nseq, run, ld, off)) if _is_const(t) \
+            else split_f16_seq(t, nseq, run, ld, off)
+    else:
+        nseq, ld = o.rows // o.P0, o.seq_stride
+        buf = split_f16_seq(t, nseq, ld, ld, off)
+    n = Operand()
+    C.memmove(C.byref(n), C.byref(o), C.sizeof(Operand))
+    n.base = ptr(buf)
+    n.rscale = ptr(buf) + 4 * nseq * ld
+    n.split = 7
     n._keep = (buf,) + tuple(o._keep)
     return n
 
@@ -1311,6 +1388,19 @@ FP16X3_LAUNCHES = 0        # launches gemm_h3_kernel took (tests and tools)
 FP16X3_WGRAD_OFF = 1 << 30
 FP16X3_WGRAD_MIN_ROWS = opt("fp16x3_wgrad_min_rows", FP16X3_WGRAD_OFF)
 FP16X3_WGRAD_LAUNCHES = 0  # launches gemm_h3w_kernel took (tests and tools)
+# fewest output rows at which a forward-form GEMM over stride-1 windows of 5 or 2 positions of a halo map (the MPD's
+# 1024-channel layer, its data gradient, the residue data gradients of the stride-3 layers) goes to gemm_h3p_kernel:
+# the map pays f2g_split_f16x2_seq per call (two reads and one write: 12 bytes per element), the weight's image is
+# cached.  Measured per launch, image pass included, against the bf16x6 launch over a producer-written image, on one
+# box (tools/fp16x3_tap_shapes.py -> profiles/fp16x3_tap_shapes.txt): every launch the library accepts wins by more
+# than its spread -- the five-tap layer and its data gradient at 0.59-0.64 of the bf16x6 time from 9504 rows (B = 16)
+# to 38528 (B = 64), the two-tap residues at 0.74-0.83 from 18944 rows -- and the stage-2 step goes 162.67 -> 148.72
+# ms (route off -> on); below 9504 rows the library's own grid rule (option x6p = 1: chip-filling grids) keeps the launches on the
+# bf16x6 kernels, so nothing smaller was measured.  Hence the default: on, from the smallest row count that won.
+# FP16X3_TAP_OFF disables the route (tests and the tool set the threshold themselves)
+FP16X3_TAP_OFF = 1 << 30
+FP16X3_TAP_MIN_ROWS = opt("fp16x3_tap_min_rows", 9504)
+FP16X3_TAP_LAUNCHES = 0    # launches gemm_h3p_kernel took (tests and tools)
 
 
 def set_gemm_precision(name: str) -> None:

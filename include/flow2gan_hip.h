@@ -84,7 +84,12 @@ typedef struct {
    * 5: `base` holds the two-piece fp16 image written by f2g_split_f16x2 (same addressing as the plain fp32
    *    matrix it was made of) and `rscale` its reciprocal row scales (precision 4, form 0, plain matrices only);
    * 6: `base` holds the two-piece fp16 image written by f2g_split_f16x2_cols (same addressing as the plain fp32
-   *    matrix) and `rscale` its reciprocal COLUMN scales, `cols` floats (precision 4, form 2, plain matrices only) */
+   *    matrix) and `rscale` its reciprocal COLUMN scales, `cols` floats (precision 4, form 2, plain matrices only);
+   * 7: `base` holds the flat two-piece fp16 image written by f2g_split_f16x2_seq (precision 4, form 0, over stride-1
+   *    windows of 5 or 2 positions only): operand A = windows over a halo map, the image of the contiguous buffer
+   *    the windows address -- same addressing as the fp32 buffer, element e in the 128 bytes at (e / 32) * 128 --
+   *    with one run per sequence (`seq_stride` floats) and `rscale` = one reciprocal scale per SEQUENCE, rows / P0
+   *    floats; operand B = the plain weight matrix with one run per row (row stride % 32 == 0), `rows` scales */
   int32_t split;
   const float* alpha;
   const float* lrelu_src;
@@ -95,7 +100,8 @@ typedef struct {
    * Only the split-bf16 weight-gradient kernel looks at it. */
   int32_t unbounded;
   /* split = 5: 1 / s per row of the operand (f2g_split_f16x2), `rows` floats; split = 6: 1 / s per column
-   * (f2g_split_f16x2_cols), `cols` floats; NULL otherwise */
+   * (f2g_split_f16x2_cols), `cols` floats; split = 7: 1 / s per run (f2g_split_f16x2_seq): per sequence of a
+   * window operand (rows / P0 floats), per row of a plain matrix; NULL otherwise */
   const float* rscale;
 } f2g_operand;
 
@@ -140,13 +146,14 @@ typedef struct {
   const float* fm_wdev;
   float mask_slope;
   float fm_w;
-  /* precision 3 only: besides C, the value is written into the f2g_split_bf16x3 image of the CONTIGUOUS
+  /* precision 3 (and the tap-walking kernel of precision 4, whose consumers stay the precision-3 kernels): besides C, the value is written into the f2g_split_bf16x3 image of the CONTIGUOUS
    * buffer C points into -- element e of that buffer (e = the store offset from C) at
    * x3_out + (e / 32) * 192 + piece * 64 + (e % 32) * 2 bytes -- so the next precision-3 GEMM reads its
    * operand without an image pass.  C must sit on a 32-element boundary of that buffer; plain /
    * row-mapped / accumulating stores (no atomics, no prelu_out). */
   void* x3_out;
-  /* > 0 (precision 3, form 0, the wide epilogue only -- ask f2g_gemm_colsum_part_rows first): `colsum` /
+  /* > 0 (precision 3 or the tap-walking kernel of precision 4, form 0, the wide epilogue only -- ask
+   * f2g_gemm_colsum_part_rows first): `colsum` /
    * `colsum_alpha` point at PARTIAL-sum matrices with one row per 64 output rows, `colsum_part_ld` floats
    * apart (16-byte aligned, ld % 4 == 0): the wave that owns output rows [64 i, 64 i + 64) STORES its column
    * sums into row i instead of adding them atomically to a shared vector, and the caller sums the rows
@@ -183,7 +190,9 @@ typedef struct {
    * 4 = fp16x3: fp32-class products from TWO fp16 pieces per operand, three MFMAs per product (per-product error
    *     <= 3 * 2^-22): form 0 over two plain matrices, both given as f2g_split_f16x2 images (f2g_operand.split = 5
    *     with rscale); form 2 (weight gradient) over two plain matrices, both given as f2g_split_f16x2_cols images
-   *     (split = 6 with rscale: one scale per column, which leaves the sum over rows), E.atomic when split_k > 1.
+   *     (split = 6 with rscale: one scale per column, which leaves the sum over rows), E.atomic when split_k > 1;
+   *     form 0 over stride-1 windows of 5 or 2 positions of a halo map against a plain weight matrix, both given as
+   *     f2g_split_f16x2_seq images (split = 7 with rscale: one scale per sequence, which leaves every window's sum).
    *     A descriptor f2g_gemm_f16_ok does not answer with 1 is F2G_EINVAL, never run elsewhere. */
   int32_t precision;
   int32_t _pad3;
@@ -272,6 +281,32 @@ int f2g_gemm_f16_ok(const f2g_gemm_desc* d);
  * their column images), asked with precision = 4 set as for the launch: 0 at any other precision.  f2g_gemm_last_kernel reports "h3w". */
 int f2g_split_f16x2_cols(float* dst, float* rscale, uint32_t* work, const float* src, int64_t ld, int32_t rows,
                          int32_t cols, f2g_stream_t stream);
+/* The image of a HALO MAP whose stride-1 conv windows are the A operand of a precision-4, form-0 GEMM, and of that
+ * GEMM's weight matrix.  A map position belongs to several overlapping windows, so a per-row scale does not leave
+ * the sums; a window never leaves its sequence, so ONE scale per sequence does.  src: nseq runs of seq_floats
+ * contiguous floats, ld floats apart (seq_floats % 32 == 0, ld % 32 == 0, ld >= seq_floats, dst and src 16-byte
+ * aligned, dst != src and not overlapping it; F2G_EINVAL otherwise).  The arithmetic of f2g_split_f16x2 with "row"
+ * read as "run": s = 2^(14 - floor(log2 max |x|)) over the run, exponent clamped to +-126, s = 1 for an all-zero run
+ * and for one holding an inf or a NaN; y = x s, hi = fp16(y), lo = fp16(2^11 (y - hi)); rscale[run] = 1 / s.
+ * LAYOUT (this is NOT f2g_split_f16x2's group-of-four layout): every aligned slab of 32 floats of a run becomes 64
+ * bytes of hi (its 32 halves in order) followed by 64 bytes of lo -- the fp32 buffer's own addressing, element e in
+ * the 128 bytes at (e / 32) * 128 of the image, the image as large as the buffer -- so that a 16-byte read is eight
+ * consecutive-k halves of one piece.  Nothing outside the runs is written.  One block per run, two reads of the run
+ * (its maximum, then the split; the second finds the cache), the maximum by a fixed tree (no atomics: reproducible).
+ * A weight row of any length is a run (f2g_split_f16x2 stops at K = 4096): nseq = rows, seq_floats = K.
+ * f2g_gemm with precision = 4, form = 0 computes, for A = stride-1 windows of 5 or 2 positions over such an image
+ * (f2g_operand.split = 7, rscale per sequence; the conditions of the precision-3 tap-walking instance: unit % 32 ==
+ * 0, unit >= 64, pad0 <= 0, seq_stride % unit == 0, at most 160 staged positions per 128 rows, L0u <= seq_stride)
+ * and B = a plain matrix image (split = 7, rscale per row), v = (acc0 + 2^-11 acc1) * rscale_a[row / P0] *
+ * rscale_b[col] on 256 x 128 tiles and hands it to the wide epilogue of the precision-3 kernels: bias, residual,
+ * leaky ReLU, PReLU, PReLU backward, mask + feature-matching term, row map, accumulate, column sums and their
+ * partial rows (colsum_part_ld), x3_out (the three-piece image for precision-3 consumers); N % 8 == 0, no atomic
+ * accumulation, no bf16 output, no split-K.  Error: 3 * 2^-22 |a| |b| per product plus at most 2^-28 amax_seq
+ * sum_k |b[n,k]| per output (elements 2^-28 below their sequence's largest are subnormal in hi).  Library option
+ * x6p applies (0 off, 1 chip-filling grids only, 2 any grid).  f2g_gemm_f16_ok answers 1 / 2 / 0 as for the other
+ * forms; f2g_gemm_last_kernel reports "h3p<taps=5>" / "h3p<taps=2>", path 6. */
+int f2g_split_f16x2_seq(float* dst, float* rscale, const float* src, int64_t ld, int32_t nseq, int32_t seq_floats,
+                        f2g_stream_t stream);
 
 /* Kernel family the last f2g_gemm call dispatched to (benchmark diagnostics, not thread safe):
  * 0 generic MFMA kernels, 1 lean kernel, 2 lean kernel in stream-K mode, 3 narrow VALU kernels,
@@ -280,7 +315,7 @@ int f2g_split_f16x2_cols(float* dst, float* rscale, uint32_t* work, const float*
 int f2g_gemm_last_path(void);
 /* Kernel instance the last f2g_gemm call launched (tests and diagnostics, not thread safe; "" when it
  * launched nothing), e.g. "lean<sk=1,ep=3,pm=0>" (lean kernel: stream-K, epilogue instance, operand mode),
- * "lean_tall<ep=2,pm=1>", "lean_tap<ep=3>", "narrow_wgrad4<4>", "x6f<wimg=1>", "h3<ep=all>", "h3w" or "generic<F1,GF,PF> split=3"
+ * "lean_tall<ep=2,pm=1>", "lean_tap<ep=3>", "narrow_wgrad4<4>", "x6f<wimg=1>", "h3<ep=all>", "h3w", "h3p<taps=5>" or "generic<F1,GF,PF> split=3"
  * (generic MFMA tiles: form, loader modes of A and B, and the K split when > 1). */
 const char* f2g_gemm_last_kernel(void);
 

@@ -1,0 +1,237 @@
+#!/usr/bin/env python
+"""fp16x3 against bf16x6 on the MPD's tap-walking GEMMs and on the stage-2 step -- one box, one process.
+
+Per period (2, 3, 5, 7, 11) at B = 64 x 1 s of 24 kHz audio, real and generated halves together (S = 128 p sequences):
+  fwd5    the forward of the 1024 -> 1024 stride-1 layer (five taps, K = 5120; bias + leaky ReLU, halo row map)
+  dgrad5  that layer's data gradient (five taps; row map, leaky-ReLU mask, column sums, the result's bf16x3 image)
+  dgrad4  the two two-tap residue data gradients of the 512 -> 1024 stride-3 layer below (K = 2048; row map, mask,
+          column sums), timed together
+and the same at B = 32, 16 and 8 for periods 2 and 11 (where the route's row threshold lies),
+each timed in both modes, the modes ALTERNATING block by block (time_blocks / med_spread of tools/fp16x3_shapes.py),
+with everything a launch costs in its mode inside the timed region: fp16x3 = the map's f2g_split_f16x2_seq image pass
+plus gemm_h3p_kernel (the weight's image is cached, as in the step); bf16x6 = the launch as that mode routes it
+(gemm_x6p_kernel over the map's three-piece image: written by the producer's epilogue in the step, made once outside
+the timed region here -- the baseline pays no image pass).
+
+Then the stage-2 step as tools/fp16x3_shapes.py runs it, in three legs that alternate block by block: bf16x6, fp16x3
+with the route off, fp16x3 with the route on.
+
+The tool, whose purpose is to measure the route, sets the threshold itself: --min-rows, default 1 = every launch the
+library accepts goes to the new kernel.  The header of the output states the command it was made with.
+
+    python tools/fp16x3_tap_shapes.py [--out profiles/fp16x3_tap_shapes.txt] [--append] [--no-shapes] [--no-steps]
+                                      [--min-rows R]
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+from fp16x3_shapes import med_spread, time_blocks  # noqa: E402
+
+PERIODS = (2, 3, 5, 7, 11)
+B, T = 64, 24000
+
+
+def heights(p):
+    hs = [(T + p - 1) // p]
+    for st in (3, 3, 3, 3, 1):
+        hs.append((hs[-1] + 4 - 5) // st + 1)
+    return hs
+
+
+def cases(ops, FD, p, dev, batch=B):
+    """(name, rows, K, N, fn) of period p at `batch` clips; the operands are allocated here, outside the timed region"""
+    S, hs = 2 * batch * p, heights(p)
+    H3, H4 = hs[3], hs[4]
+    g = torch.Generator().manual_seed(p)
+
+    def halo_map(H, Cc, scale=1.0, x3=False):
+        buf = FD._halo_rows(S, H, Cc, dev, x3=x3)
+        FD.unhalo(buf, S, H).copy_((torch.randn(S, H, Cc, generator=g) * scale).to(dev))
+        if x3 and getattr(buf, "_f2g_x3_buf", None) is not None:      # the producer's image, made once
+            buf._f2g_x3 = ops.x3_flat_image(buf)
+        return buf
+
+    w5 = torch.nn.Parameter((torch.randn(1024, 1024, 5, 1, generator=g) * 5120 ** -0.5).to(dev))
+    w4 = torch.nn.Parameter((torch.randn(1024, 512, 5, 1, generator=g) * 2560 ** -0.5).to(dev))
+    b5 = torch.randn(1024, generator=g).to(dev)
+    out = []
+    # forward of layer 5
+    x4 = halo_map(H4, 1024, x3=True)
+    y5 = FD._halo_rows(S, H4, 1024, dev)
+    wp = ops.derived(w5, "pack", FD.pack_conv_weight)
+    out.append(("fwd5", S * H4, 5120, 1024, lambda: ops.gemm(
+        ops.win1d(x4, S, H4 + 2 * FD.HALO, 1024, H4, 1, 0, 5), ops.mat(wp), y5, bias=b5, lrelu=FD.SLOPE,
+        rowmap=FD._halo_map(H4, 1024))))
+    # data gradients: of layer 5 (one five-tap residue), of layer 4 (its two two-tap residues)
+    for name, w, stride, Hin, Cin in (("dgrad5", w5, 1, H4, 1024), ("dgrad4", w4, 3, H3, 512)):
+        gpre = halo_map(H4, 1024, 1e-3, x3=True)
+        act = halo_map(Hin, Cin)
+        want_img = 2 * Cin >= ops.X6_MIN_K
+        gx = FD._halo_rows(S, Hin, Cin, dev, x3=want_img)
+        cs = torch.zeros(Cin, device=dev)
+        launches = []
+        for rho, j0, nt, e0, Lq in FD._residues(5, stride, 2, Hin):
+            if Lq == 0 or nt not in (5, 2):
+                continue
+            wq = FD._dgrad_weight(w, stride, j0, nt)
+            launches.append((wq, (nt - 1) - e0 - FD.HALO, nt, Lq,
+                             (Lq, (Hin + 2 * FD.HALO) * Cin, stride * Cin, (FD.HALO + rho) * Cin)))
+
+        def fn(gpre=gpre, act=act, gx=gx, cs=cs, launches=launches, want_img=want_img):
+            for wq, pad, nt, Lq, rm in launches:
+                ops.gemm(ops.win1d(gpre, S, H4 + 2 * FD.HALO, 1024, Lq, 1, pad, nt), ops.mat(wq), gx, rowmap=rm,
+                         mask=(act, 0, FD.SLOPE), colsum=cs, x3_out=want_img)
+        rows = sum(S * l[3] for l in launches)
+        out.append((name, rows, launches[0][2] * 1024, Cin, fn))
+    return out
+
+
+def shapes_table(ops, dev, say):
+    from flow2gan_amd import fused_disc as FD
+    ops.set_gemm_precision("bf16x6")        # (the maps' three-piece images are reserved in this mode only)
+    say("batch period  launch     rows      K      N  bf16x6_us  spread  fp16x3_us  spread  ratio  TFLOP/s(fp16x3)  kernels")
+    worst = []
+    # the step's own shapes (B = 64, every period), then smaller batches at the two outer periods: where the rule's
+    # row threshold lies (a launch the library keeps off the kernel -- a grid that does not fill the chip, library
+    # option x6p = 1 -- runs the bf16x6 kernel in both legs and is marked so)
+    for batch, periods in ((B, PERIODS), (32, (2, 11)), (16, (2, 11)), (8, (2, 11))):
+        for p in periods:
+            for name, rows, K, N, fn in cases(ops, FD, p, dev, batch):
+                n0 = ops.FP16X3_TAP_LAUNCHES
+                per, kern = time_blocks(ops, fn)
+                taken = ops.FP16X3_TAP_LAUNCHES > n0
+                assert taken or batch < B, f"period {p} {name}: the fp16x3 leg never took the route"
+                (a, sa), (b, sb) = med_spread(per["bf16x6"]), med_spread(per["fp16x3"])
+                say(f"{batch:5d} {p:6d}  {name:7s} {rows:7d} {K:6d} {N:6d} {a:10.1f} {sa:7.3f} {b:10.1f} {sb:7.3f} "
+                    f"{b / a:6.3f} {2.0 * rows * K * N / b * 1e-6:12.1f}      {kern['bf16x6']} | {kern['fp16x3']}"
+                    + ("" if taken else "   (not taken: the grid does not fill the chip)"))
+                if taken:
+                    worst.append((b / a, max(sa, sb), p, f"B {batch} {name}", rows // (2 if name == "dgrad4" else 1)))
+            torch.cuda.empty_cache()
+    won = [w for w in worst if w[0] < 1.0 - w[1]]
+    lost = [w for w in worst if w[0] > 1.0 + w[1]]
+    say(f"# launches where fp16x3 wins by more than the spread: {len(won)} of {len(worst)}"
+        + "".join(f"\n#   period {p} {n} rows {r}: ratio {q:.3f}, spread {s:.3f}" for q, s, p, n, r in won))
+    say(f"# launches where fp16x3 loses by more than the spread: {len(lost)} of {len(worst)}"
+        + "".join(f"\n#   period {p} {n} rows {r}: ratio {q:.3f}, spread {s:.3f}" for q, s, p, n, r in lost))
+    if won:
+        say(f"# fewest output rows of a winning launch (dgrad4: of one of its two launches): {min(w[4] for w in won)}")
+        say(f"# rule: ops.FP16X3_TAP_MIN_ROWS = {min(w[4] for w in won)} -- on, from the smallest row count that wins by "
+            "more than its spread" + ("" if lost else "; no launch the library accepts loses"))
+
+
+def steps_table(ops, dev, say, min_rows, steps=4):
+    import flow2gan_amd
+    from flow2gan_amd import harness
+    from flow2gan_amd.models.config import get_gan_config, get_generator_config
+    from flow2gan_amd.models.gan import GAN
+    gcfg = get_generator_config("mel_24k_base")
+    sr = gcfg["sampling_rate"]
+    torch.manual_seed(1234)
+    gen = flow2gan_amd.MelAudioGenerator(**gcfg)
+    gen.branch_dropout = 0.0
+    gan = GAN(gen, **get_gan_config("gan_multi_scale_mel_recon")).to(dev)
+    logmel = flow2gan_amd.LogMelSpectrogram(sr, gcfg["mel_n_fft"], gcfg["mel_hop_length"], gcfg["n_mels"]).to(dev)
+    g = torch.Generator().manual_seed(99)
+    audio = (0.1 * torch.randn(B, sr, generator=g)).clamp_(-1, 1).to(dev)
+    lens = torch.full((B,), sr, dtype=torch.int64)
+    g_params, d_params = list(gan.generator.parameters()), list(gan.discriminator.parameters())
+
+    def stage2():
+        for disc, params in ((True, d_params), (False, g_params)):
+            for p in params:
+                p.grad = None
+            loss, _ = harness.compute_loss_stage2(audio, lens, gan, logmel, 1, train_disc=disc)
+            loss.backward()
+            ops.bump_weight_epoch(params)
+            ops.rebuild_derived(params)
+
+    legs = (("bf16x6", "bf16x6", ops.FP16X3_TAP_OFF), ("fp16x3 route off", "fp16x3", ops.FP16X3_TAP_OFF),
+            ("fp16x3 route on", "fp16x3", min_rows))
+
+    def enter(leg):
+        ops.set_gemm_precision(leg[1])
+        ops.FP16X3_TAP_MIN_ROWS = leg[2]
+
+    per = {leg[0]: [] for leg in legs}
+    launches = {leg[0]: 0 for leg in legs}
+    for leg in legs:
+        enter(leg)
+        stage2(), stage2()
+    torch.cuda.synchronize()
+    for _ in range(7):
+        for leg in legs:
+            enter(leg)
+            n0 = ops.FP16X3_TAP_LAUNCHES
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(steps):
+                stage2()
+            torch.cuda.synchronize()
+            per[leg[0]].append((time.perf_counter() - t0) * 1e3 / steps)
+            launches[leg[0]] = max(launches[leg[0]], (ops.FP16X3_TAP_LAUNCHES - n0) // steps)
+    say("# stage-2 step: medians of 7 alternating blocks of 4 steps per leg; spread = (max - min) / median")
+    say("stage-2 step        ms  spread  ratio to bf16x6  tap-route launches per step")
+    base = med_spread(per["bf16x6"])[0]
+    for leg in legs:
+        m, s = med_spread(per[leg[0]])
+        say(f"{leg[0]:17s} {m:7.2f} {s:7.3f} {m / base:8.3f}          {launches[leg[0]]}")
+    off, on = med_spread(per["fp16x3 route off"]), med_spread(per["fp16x3 route on"])
+    say(f"# route on / route off (the same mode, the route alone differing): {on[0] / off[0]:.3f} "
+        f"(spreads {on[1]:.3f} / {off[1]:.3f})")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fp16x3_tap_shapes.txt"))
+    ap.add_argument("--append", action="store_true", help="add this run's table to --out instead of replacing it")
+    ap.add_argument("--no-steps", action="store_true")
+    ap.add_argument("--no-shapes", action="store_true")
+    ap.add_argument("--min-rows", type=int, default=1, help="ops.FP16X3_TAP_MIN_ROWS for this run (1: every launch "
+                    "of the table on the new kernel)")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "needs an MI355X"
+    from flow2gan_amd import ops
+    if args.min_rows < 1 or args.min_rows >= ops.FP16X3_TAP_OFF:
+        ap.error("--min-rows must enable the route: both modes would time the same bf16x6 launch otherwise")
+    was_rows = ops.FP16X3_TAP_MIN_ROWS
+    dev = torch.device("cuda")
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    given = [a for i, a in enumerate(sys.argv[1:], 1) if a != "--out" and sys.argv[i - 1] != "--out"]
+    say("# command (the output path aside): python tools/fp16x3_tap_shapes.py " + " ".join(given))
+    say(f"# tools/fp16x3_tap_shapes.py  {ops.L.version()}  FP16X3_TAP_MIN_ROWS={args.min_rows} "
+        f"X6_MIN_K={ops.X6_MIN_K}  {torch.cuda.get_device_name(0)}")
+    say("# per-launch medians of 5 alternating blocks of 12 launches (us), the map's image pass included in the fp16x3 "
+        "leg; spread = (max - min) / median of a mode's blocks; ratio = fp16x3 / bf16x6 (< 1: fp16x3 faster)")
+    from test_hip_gemm_f16 import mode_name       # (the one place that names the mode in force)
+    was = mode_name(ops)
+    try:
+        if not args.no_shapes:
+            ops.FP16X3_TAP_MIN_ROWS = args.min_rows
+            shapes_table(ops, dev, say)
+        if not args.no_steps:
+            steps_table(ops, dev, say, args.min_rows)
+    finally:
+        ops.FP16X3_TAP_MIN_ROWS = was_rows
+        ops.set_gemm_precision(was)
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "a" if args.append else "w") as f:
+        f.write(("#\n# ---- another run of the same tool\n" if args.append else "") + "\n".join(lines) + "\n")
+
+
+if __name__ == "__main__":
+    main()
