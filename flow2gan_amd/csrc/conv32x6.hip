@@ -9,9 +9,11 @@
 // The patch of a tile is split ONCE while it is staged (each element then feeds 27 taps x 32 outputs):
 // a staged pixel is [32 p0 | 32 p1 | 32 p2 | pad] bf16 = 208 bytes (52 dwords: conflict-free
 // ds_read_b128); the weights arrive as the f2g_split_bf16x3 image of the packed matrix (192 contiguous
-// bytes per output channel and tap) and go to LDS unchanged.  208-byte pixels need 83 KB for the
-// forward patch, so ONE block of 8 waves per CU: the blocks are persistent (a block walks tiles b,
-// b + G, ...) and request the next tile's patch into registers before they compute the current one.
+// bytes per output channel and tap).  208-byte pixels need 83 KB for the forward patch, so ONE block of
+// 8 waves per CU: the blocks are persistent (a block walks tiles b, b + G, ...) and request the next
+// tile's patch into registers before they compute the current one.  Forward and data gradient split a
+// tile's reduction over the waves, which hold the weight fragments of their k steps in registers for the
+// block's life (no weight ever passes through LDS); the (3, 3) layer keeps its nine weight tiles in LDS.
 #include <stdlib.h>
 
 #include "common.h"
@@ -27,9 +29,6 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int C = 32, KH = 3, KW = 9, NTAP = KH * KW;
 constexpr int PB = 208;            // bytes of a staged pixel / weight row
-constexpr int TG = 4;              // taps per barrier: two for each half of the block's waves
-constexpr int WBB = C * PB;        // bytes of one staged weight tile
-constexpr int WCH = C * 12;        // 16-byte chunks of one weight tile in the image (32 rows x 192 bytes)
 
 __device__ __attribute__((aligned(16))) float c6_zero[4] = {0.f, 0.f, 0.f, 0.f};
 
@@ -105,34 +104,33 @@ __device__ __forceinline__ void px_of_row(int pg, int r, int& ph, int& pw) {
   }
 }
 
-// weights of a tap group: 4 tiles x 384 chunks of 16 bytes = 3 chunks per thread (512 threads)
-struct wplan {
-  int src[3];      // byte offset inside the image WITHOUT the tap term (row * row_stride + part * 16)
-  int dst[3];      // byte offset inside a group's LDS buffer
-  int u[3];        // tap of the group this chunk belongs to
-};
-
 // ---- forward ----------------------------------------------------------------------------------------
-// 8 waves: pixel group pg = wave & 3 (32 of the tile's 128 pixels), tap half = wave >> 2 (taps 4g, 4g+1 /
-// 4g+2, 4g+3 of group g); the halves' partial tiles meet through LDS at the end of a tile.
+// The reduction of a tile is 54 k steps of 16 (27 taps x the two halves of the input channels), split over
+// the block's 8 waves: waves 0..5 take seven consecutive k steps, waves 6 and 7 six.  A wave loads the B
+// fragments of ITS k steps once, straight from the f2g_split_bf16x3 image (lane li = output channel, 16 bytes
+// at q * 64 + ks * 32 + hh * 16 of the (co, tap) row), and keeps them in 84 registers until it exits: no
+// weight passes through LDS, and a tile costs no weight traffic at all.  Per tile a wave computes all four
+// 32-pixel groups over its own k steps -- three ds_read_b128 of the staged pixel's pieces per six MFMAs --
+// and the eight partial 128 x 32 tiles meet through 64 KB of LDS in two phases of two pixel groups: every
+// wave writes its partials [wave][group][pixel][channel], and wave w then owns 8 pixels of each group pair,
+// which it sums over the waves in the fixed order 0..7 (no atomics: the result is bit-reproducible) and
+// stores as 16-byte [pixel][channel] row segments after bias and leaky ReLU.  Four barriers per tile.
 template <int TH_, int TW_>
 __global__ __launch_bounds__(512, 1) void conv32_s2_fwd6_kernel(const f2g_conv32_desc d, int tiles_w,
                                                                int tiles_h, int ntiles) {
   constexpr int IHv = TH_ + KH - 1, IWv = TW_ + (KW - 1) / 2, XW = 2 * IWv - 1;
   constexpr int SUBB = IHv * IWv * PB + 64;             // bytes of one column parity of the patch
   constexpr int NCHK = (IHv * XW * (C / 4) + 511) / 512;
-  // 7 groups of four taps + one empty pipeline slot: with an EVEN count the LDS buffer and the register stage
-  // of a group are the same in every tile (group g: buffer g & 1)
-  constexpr int NG = (NTAP + TG - 1) / TG + 1;
-  static_assert(NG % 2 == 0, "the weight double buffer must come back to buffer 0 at a tile's end");
+  constexpr int PGB = (TW_ == 16 ? 2 : 4) * IWv * PB;    // bytes from a pixel group's staged pixels to the next's
+  constexpr int NKS = 2 * NTAP, KPW = 7;                // k steps of a tile / of a wave (waves 6, 7: one less)
   static_assert(TH_ * TW_ == 128, "a block owns 128 output pixels");
+  static_assert(6 * KPW + 2 * (KPW - 1) == NKS, "the k split covers the reduction exactly");
   extern __shared__ __attribute__((aligned(16))) unsigned char smb[];
   unsigned char* At = smb;                               // [2 parities][IHv][IWv] pixels
-  unsigned char* Bt = smb + 2 * SUBB;                    // [2 buffers][TG taps][32 rows]
-  float* red = reinterpret_cast<float*>(Bt + 2 * TG * WBB);   // [4 pixel groups][16][64 lanes]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float* red = reinterpret_cast<float*>(smb + 2 * SUBB); // [8 waves][2 pixel groups][32 pixels][32 channels]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, hh = lane >> 5;
-  const int pg = wave & 3, half = wave >> 2;
   const int c4 = tid & 7;
   const int px0 = tid >> 3;
   auto tile_pos = [&](int tile, int& sq, int& h0, int& w0) {
@@ -143,132 +141,130 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_fwd6_kernel(const f2g_conv32
     w0 = tw * TW_;
   };
   // chunk q of this thread = 4 channels of patch pixel px0 + 64 q = (row r, column xr); recomputed per
-  // tile (a multiplication) instead of kept in 21 registers beside the fragment stages
+  // tile (a multiplication) instead of kept in 21 registers beside the weights: the empty asm makes px0 opaque,
+  // or the compiler hoists every chunk's offsets out of the tile loop and spills them
   auto load_patch = [&](int tile, f32x4 (&pf)[NCHK]) {
     int sq, h0, w0;
     tile_pos(tile, sq, h0, w0);
     const int x0 = 2 * w0 - (KW - 1) / 2;
     const float* org = d.x + (long long)sq * d.x_seq + (long long)(h0 - 1) * d.x_line + (long long)x0 * C + c4 * 4;
+    const int xl = (int)d.x_line;                // (< 2^24, checked by the launcher: row offsets fit 32 bits)
+    int pxb = px0;
+    asm volatile("" : "+v"(pxb));                // (keeps the chunk arithmetic inside the tile loop, see above)
 #pragma unroll
     for (int q = 0; q < NCHK; ++q) {
-      const int px = px0 + 64 * q;
+      const int px = pxb + 64 * q;
       const int r = div_small<XW>(px), xr = px - r * XW;
       const int h = h0 - 1 + r, x = x0 + xr;
       const bool ok = px < IHv * XW && h >= 0 && h < d.H && x >= 0 && x < d.Win;
-      pf[q] = *reinterpret_cast<const f32x4*>(ok ? org + (long long)r * d.x_line + xr * C : c6_zero);
+      pf[q] = *reinterpret_cast<const f32x4*>(ok ? org + (r * xl + xr * C) : c6_zero);
     }
   };
   auto store_patch = [&](const f32x4 (&pf)[NCHK]) {
+    int pxb = px0;
+    asm volatile("" : "+v"(pxb));
 #pragma unroll
     for (int q = 0; q < NCHK; ++q) {
-      const int px = px0 + 64 * q;
+      const int px = pxb + 64 * q;
       const int r = div_small<XW>(px), xr = px - r * XW;
       if (px < IHv * XW) store_px3(At + (xr & 1) * SUBB + (r * IWv + (xr >> 1)) * PB + c4 * 8, pf[q]);
     }
   };
-  // weights: the image is [co][27 taps][3 pieces][32] bf16 = 192 bytes per (co, tap)
-  const unsigned char* wimg = reinterpret_cast<const unsigned char*>(d.w);
-  wplan wp;
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int c = tid + 512 * k;
-    const int u = c / WCH, rem = c - u * WCH;
-    const int row = rem / 12, part = rem - row * 12;
-    wp.u[k] = u;
-    wp.src[k] = row * (NTAP * 192) + part * 16;
-    wp.dst[k] = u * WBB + row * PB + part * 16;
-  }
-  auto load_w = [&](int g, u32x4 (&wn)[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      int t = g * TG + wp.u[k];
-      t = t < NTAP ? t : NTAP - 1;
-      wn[k] = *reinterpret_cast<const u32x4*>(wimg + wp.src[k] + t * 192);
-    }
-  };
-  auto store_w = [&](int buf, const u32x4 (&wn)[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x4*>(Bt + buf * (TG * WBB) + wp.dst[k]) = wn[k];
-  };
-  int ph, pw;                                   // this lane's output pixel inside the tile
-  px_of_row<TW_>(pg, li, ph, pw);
-  const unsigned char* Ap = At + (ph * IWv + pw) * PB + hh * 16;
-  const unsigned char* Bp = Bt + li * PB + hh * 16;
-  const float bias = d.bias ? d.bias[li] : 0.f;
-
   int tile = blockIdx.x;
   if (tile >= ntiles) return;
-  // weight pipeline: group g + 1 is requested at the start of group g and goes to LDS at its end (two
-  // groups ahead through a second register stage measured the same and spilled beside the fragment stages)
-  u32x4 wn[3];
+  f32x4 pf[NCHK];
+  load_patch(tile, pf);
+  // this wave's k steps k0 .. k0 + nk - 1 (k = 2 tap + channel half): weight fragments for the block's life
+  // and the wave-uniform patch offsets (the image is [co][27 taps][3 pieces][32] bf16 = 192 bytes per (co, tap))
+  const int k0 = wave * KPW - (wave == 7 ? 1 : 0);
+  const bool seven = wave < 6;
+  bf16x8 wf[KPW][3];
+  int koff[KPW];
   {
-    f32x4 pf[NCHK];
-    load_patch(tile, pf);
-    load_w(0, wn);
-    store_patch(pf);
-    store_w(0, wn);
+    const unsigned char* wrow = reinterpret_cast<const unsigned char*>(d.w) + li * (NTAP * 192) + hh * 16;
+#pragma unroll
+    for (int j = 0; j < KPW; ++j) {
+      int k = k0 + j;
+      k = k < NKS ? k : NKS - 1;                      // (the unused seventh step of waves 6, 7: any valid one)
+      const int t = k >> 1, ks = k & 1;
+      const int dh = t / KW, jw = t - dh * KW;
+      koff[j] = (jw & 1) * SUBB + (dh * IWv + (jw >> 1)) * PB + ks * 32;
+#pragma unroll
+      for (int q = 0; q < 3; ++q) wf[j][q] = *reinterpret_cast<const bf16x8*>(wrow + t * 192 + q * 64 + ks * 32);
+    }
   }
+  int ph, pw;                                   // this lane's output pixel inside pixel group 0
+  px_of_row<TW_>(0, li, ph, pw);
+  const unsigned char* Ap = At + (ph * IWv + pw) * PB + hh * 16;
+  // owner role: pixel (wave & 3) * 8 + (lane >> 3) of pixel group 2 * phase + (wave >> 2), channels 4 (lane & 7) ..
+  const int orow = (wave & 3) * 8 + (lane >> 3), och = 4 * (lane & 7);
+  f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
+  if (d.bias) bias4 = f32x4{d.bias[och], d.bias[och + 1], d.bias[och + 2], d.bias[och + 3]};
+  store_patch(pf);
   __syncthreads();
-  // patch offset of tap t (a literal after unrolling)
-#define F2G_C6_AOFF(T) ((((T) % KW) & 1) * SUBB + (((T) / KW) * IWv + (((T) % KW) >> 1)) * PB)
   for (; tile < ntiles; tile += gridDim.x) {
     const int nxt = tile + gridDim.x;
     const bool more = nxt < ntiles;
-    f32x4 pf[NCHK];
     load_patch(more ? nxt : tile, pf);          // (the last tile re-requests its own: never stored)
-    f32x16 acc0, acc1;
+    f32x16 acc[4];
 #pragma unroll
-    for (int e = 0; e < 16; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; }
+    for (int g4 = 0; g4 < 4; ++g4)
 #pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      load_w(g + 1 < NG ? g + 1 : 0, wn);       // next group (group 0 of the next tile after the last)
-      const int buf = g & 1;
+      for (int e = 0; e < 16; ++e) acc[g4][e] = 0.f;
+    // unit u = (k step u >> 2, pixel group u & 3): the three fragments of unit u + 1 are requested in front of
+    // unit u's six MFMAs (i + j <= 2, smallest terms first), and the scheduler may not move anything across a
+    // unit's end -- left alone it sinks the reads to their first use and waits lgkmcnt(0) in front of most MFMAs
+    bf16x8 a[2][3];
 #pragma unroll
-      for (int u2 = 0; u2 < 2; ++u2) {
-        // tap of this wave half: 4 g + 2 half + u2 (both candidates are literals; the choice is wave-uniform)
-        const int t0 = g * TG + u2, t1 = g * TG + 2 + u2;
-        if (t0 < NTAP && (half ? t1 : t0) < NTAP)
-          tap6(Ap + (half ? F2G_C6_AOFF(t1) : F2G_C6_AOFF(t0)), Bp + (buf * TG + half * 2 + u2) * WBB, acc0, acc1);
+    for (int q = 0; q < 3; ++q) a[0][q] = *reinterpret_cast<const bf16x8*>(Ap + koff[0] + q * 64);
+#pragma unroll
+    for (int u = 0; u < 4 * KPW; ++u) {
+      const int j = u >> 2, g4 = u & 3;
+      if (u + 1 < 4 * KPW) {                       // (waves 6, 7 read their clamped seventh step and drop it)
+        const unsigned char* an = Ap + koff[(u + 1) >> 2] + ((u + 1) & 3) * PGB;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) a[(u + 1) & 1][q] = *reinterpret_cast<const bf16x8*>(an + q * 64);
       }
-      store_w(buf ^ 1, wn);
-      __syncthreads();
+      __builtin_amdgcn_sched_barrier(0);
+      if (j < KPW - 1 || seven) {
+#define F2G_X6_ONE(I, J) acc[g4] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[u & 1][I], wf[j][J], acc[g4], 0, 0, 0);
+        F2G_X6_ONE(2, 0) F2G_X6_ONE(1, 1) F2G_X6_ONE(0, 2) F2G_X6_ONE(1, 0) F2G_X6_ONE(0, 1) F2G_X6_ONE(0, 0)
+#undef F2G_X6_ONE
+      }
+      __builtin_amdgcn_sched_barrier(0);
     }
-#undef F2G_C6_AOFF
-    // the halves' partial tiles meet; the next patch goes to LDS (every wave is done with this one)
+    int sq, h0, w0;
+    tile_pos(tile, sq, h0, w0);
+    float* ys = d.y + (long long)sq * d.y_seq;
+    __syncthreads();                              // the owners of the previous tile are done with `red`
 #pragma unroll
-    for (int e = 0; e < 16; ++e) acc0[e] += acc1[e];
-    if (half == 1) {
+    for (int p2 = 0; p2 < 2; ++p2) {
+      if (p2) __syncthreads();                    // the owners have read phase 0
 #pragma unroll
-      for (int e = 0; e < 16; ++e) red[(pg * 16 + e) * 64 + lane] = acc0[e];
-    }
-    if (more) store_patch(pf);
-    __syncthreads();
-    if (half == 0) {
-      // (round 5) the finished 32 pixels x 32 channels leave through this pixel group's 4 KB of `red`, turned to
-      // [pixel][channel]: four 16-byte stores per lane instead of sixteen 4-byte ones
-      int sq, h0, w0;
-      tile_pos(tile, sq, h0, w0);
-      float* ys = d.y + (long long)sq * d.y_seq;
-      float* turn = red + pg * (16 * 64);
-      float v[16];
+      for (int g2 = 0; g2 < 2; ++g2)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        v[e] = acc0[e] + red[(pg * 16 + e) * 64 + lane] + bias;
-        if (d.lrelu_slope != 0.f) v[e] = v[e] > 0.f ? v[e] : d.lrelu_slope * v[e];
+        for (int e = 0; e < 16; ++e)
+          red[((wave * 2 + g2) * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh) * 32 + li] = acc[2 * p2 + g2][e];
+      __syncthreads();                            // (phase 0: every wave is also done with this tile's patch)
+      f32x4 s = *reinterpret_cast<const f32x4*>(red + (((wave >> 2)) * 32 + orow) * 32 + och);
+#pragma unroll
+      for (int w8 = 1; w8 < 8; ++w8) {
+        const f32x4 v = *reinterpret_cast<const f32x4*>(red + ((w8 * 2 + (wave >> 2)) * 32 + orow) * 32 + och);
+        s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
       }
-      __builtin_amdgcn_wave_barrier();            // (the partner half's partial sums are in registers)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) turn[((e & 3) + 8 * (e >> 2) + 4 * hh) * 32 + li] = v[e];
-      __builtin_amdgcn_wave_barrier();
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        int qh, qw;
-        px_of_row<TW_>(pg, (lane >> 3) + 8 * j, qh, qw);
-        const int oh = h0 + qh, ow = w0 + qw;
-        const f32x4 u = *reinterpret_cast<const f32x4*>(turn + ((lane >> 3) + 8 * j) * 32 + 4 * (lane & 7));
-        if (oh < d.H && ow < d.Wout)
-          *reinterpret_cast<f32x4*>(ys + (long long)oh * d.y_line + (long long)ow * C + 4 * (lane & 7)) = u;
+      s.x += bias4.x, s.y += bias4.y, s.z += bias4.z, s.w += bias4.w;
+      if (d.lrelu_slope != 0.f) {
+        s.x = s.x > 0.f ? s.x : d.lrelu_slope * s.x;
+        s.y = s.y > 0.f ? s.y : d.lrelu_slope * s.y;
+        s.z = s.z > 0.f ? s.z : d.lrelu_slope * s.z;
+        s.w = s.w > 0.f ? s.w : d.lrelu_slope * s.w;
       }
+      int qh, qw;
+      px_of_row<TW_>(2 * p2 + (wave >> 2), orow, qh, qw);
+      const int oh = h0 + qh, ow = w0 + qw;
+      if (oh < d.H && ow < d.Wout)
+        *reinterpret_cast<f32x4*>(ys + (long long)oh * d.y_line + (long long)ow * C + och) = s;
+      if (p2 == 0 && more) store_patch(pf);       // the next tile's patch, behind the first phase's sums
     }
   }
 }
@@ -277,28 +273,32 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_fwd6_kernel(const f2g_conv32
 // gx[h, x, ci] = sum_{dh, j, co} g[h + 1 - dh, (x + 4 - j) / 2, co] * w[co, ci, dh, j] over the taps with
 // x + 4 - j even (conv32.hip): input columns of parity E = x & 1 use the taps j = E + 2u (5 / 4 of them per
 // row) and read CONSECUTIVE gradient columns m + 2 - u (x = 2 m + E) -- both parities read the SAME
-// gradient patch.  Here a tile is 128 positions m x BOTH parities: wave half 0 computes the even input
-// columns (15 taps), half 1 the odd ones (12 taps), from one staged patch, and nothing has to be
-// reduced across waves.  d.x = g (S, H, Wout, 32), d.y = gx (S, H, Win, 32),
+// gradient patch.  Here a tile is 128 positions m x BOTH parities: waves 0..3 compute the even input columns
+// (15 taps = 30 k steps of 16 output channels, split 8 / 8 / 7 / 7), waves 4..7 the odd ones (12 taps = 24 k
+// steps, 6 each), from one staged patch.  As in the forward kernel a wave holds the B fragments of its k steps
+// in registers for the block's life (<= 96), computes all four position groups of its parity over them, and the
+// four partial tiles of a parity meet through LDS in two phases of two position groups, summed in the fixed
+// order of the waves; wave wq of a parity then owns 16 positions of each phase as four 16-byte
+// [position][channel] items per tile, which is also the epilogue's store form.
+// d.x = g (S, H, Wout, 32), d.y = gx (S, H, Win, 32),
 // d.w = the f2g_split_bf16x3 image of wT [27 taps][ci][co] as an (864, 32) matrix: 192 bytes per (tap, ci).
 template <int TH_, int TW_>
 __global__ __launch_bounds__(512, 1) void conv32_s2_dgrad6_kernel(const f2g_conv32_desc d, int tiles_w,
                                                                  int tiles_h, int ntiles) {
   constexpr int IHv = TH_ + KH - 1, GWv = TW_ + 4;
   constexpr int NCHK = (IHv * GWv * (C / 4) + 511) / 512;
-  constexpr int NG = 8;                                  // groups of 2 taps per parity: 15 -> 8, 12 -> 6
+  constexpr int PGB = (TW_ == 16 ? 2 : 4) * GWv * PB;    // bytes from a position group's staged pixels to the next's
+  constexpr int KPW = 8;                                 // k steps of a wave at most
   static_assert(TH_ * TW_ == 128, "a block owns 128 positions of each column parity");
   extern __shared__ __attribute__((aligned(16))) unsigned char smb[];
   unsigned char* At = smb;                               // [IHv][GWv] pixels
-  unsigned char* Bt = smb + IHv * GWv * PB;              // [2 buffers][TG taps][32 rows]
-  // (round 5) epilogue turn: a wave's 32 positions x 32 channels leave through a private 4 KB patch as 16-byte
-  // row segments -- 4 stores (and 4 mask loads) per lane and tile instead of 16 four-byte ones
-  float* turn = reinterpret_cast<float*>(Bt + 2 * TG * WBB) + (threadIdx.x >> 6) * (32 * 32);
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  float* red = reinterpret_cast<float*>(smb + IHv * GWv * PB);   // [8 waves][2 groups][32 positions][32 channels]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int li = lane & 31, hh = lane >> 5;
-  const int pg = wave & 3, E = wave >> 2;                // E = column parity of this wave half
+  const int wq = wave & 3, E = wave >> 2;                // E = column parity of this wave half
   const int c4 = tid & 7;
-  const int NU = E ? 4 : 5, NT = KH * NU;
+  const int NU = E ? 4 : 5;
   const int Wp = (d.Win + 1 - E) / 2;                    // input columns of this parity
   const int px0 = tid >> 3;
   auto tile_pos = [&](int tile, int& sq, int& h0, int& m0) {
@@ -308,17 +308,21 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_dgrad6_kernel(const f2g_conv
     h0 = th * TH_;
     m0 = tw * TW_;
   };
+  // (the empty asm keeps the chunk arithmetic inside the tile loop: see the forward kernel)
   auto load_patch = [&](int tile, f32x4 (&pf)[NCHK]) {
     int sq, h0, m0;
     tile_pos(tile, sq, h0, m0);
     const float* org = d.x + (long long)sq * d.x_seq + (long long)(h0 - 1) * d.x_line + (long long)(m0 - 2) * C + c4 * 4;
+    const int xl = (int)d.x_line;
+    int pxb = px0;
+    asm volatile("" : "+v"(pxb));
 #pragma unroll
     for (int q = 0; q < NCHK; ++q) {
-      const int px = px0 + 64 * q;
+      const int px = pxb + 64 * q;
       const int r = div_small<GWv>(px), xc = px - r * GWv;
       const int h = h0 - 1 + r, c = m0 - 2 + xc;
       const bool ok = px < IHv * GWv && h >= 0 && h < d.H && c >= 0 && c < d.Wout;
-      pf[q] = *reinterpret_cast<const f32x4*>(ok ? org + (long long)r * d.x_line + xc * C : c6_zero);
+      pf[q] = *reinterpret_cast<const f32x4*>(ok ? org + (r * xl + xc * C) : c6_zero);
     }
   };
   auto store_patch = [&](const f32x4 (&pf)[NCHK]) {
@@ -328,324 +332,174 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_dgrad6_kernel(const f2g_conv
       if (px < IHv * GWv) store_px3(At + px * PB + c4 * 8, pf[q]);
     }
   };
-  // weights of group g: taps 2g, 2g+1 of parity 0 (slots 0, 1) and of parity 1 (slots 2, 3); tap index
-  // ti of parity e -> weight tile (ti / nu) * 9 + e + 2 * (ti % nu); image rows = (tile, ci), 192 bytes each
-  const unsigned char* wimg = reinterpret_cast<const unsigned char*>(d.w);
-  int wsrc[3], wdst[3], wslot[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int c = tid + 512 * k;
-    const int u = c / WCH, rem = c - u * WCH;
-    const int row = rem / 12, part = rem - row * 12;
-    wslot[k] = u;
-    wsrc[k] = row * 192 + part * 16;
-    wdst[k] = u * WBB + row * PB + part * 16;
-  }
-  auto load_w = [&](int g, u32x4 (&wn)[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int e = wslot[k] >> 1, nu = e ? 4 : 5, nt = KH * nu;
-      int ti = 2 * g + (wslot[k] & 1);
-      ti = ti < nt ? ti : nt - 1;
-      const int dh = e ? ti >> 2 : (ti * 13) >> 6;        // ti / nu for ti < 15 without a division
-      const int tile_w = dh * KW + e + 2 * (ti - dh * nu);
-      wn[k] = *reinterpret_cast<const u32x4*>(wimg + (long long)tile_w * (C * 192) + wsrc[k]);
-    }
-  };
-  auto store_w = [&](int buf, const u32x4 (&wn)[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x4*>(Bt + buf * (TG * WBB) + wdst[k]) = wn[k];
-  };
-  int ph, pw;
-  px_of_row<TW_>(pg, li, ph, pw);
-  const unsigned char* Ap = At + ((ph + 2) * GWv + pw + 4) * PB + hh * 16;
-  const unsigned char* Bp = Bt + (E * 2) * WBB + li * PB + hh * 16;
-  const bool msk = d.mask_src != nullptr, fm = d.fm_ref != nullptr;
-  const float fmw = fm ? d.fm_w * (d.fm_wdev ? d.fm_wdev[0] : 1.f) : 0.f;
-  float cs[4] = {0.f, 0.f, 0.f, 0.f};            // column sums of what this lane stores (channels 4 (lane & 7) ..)
-
   int tile = blockIdx.x;
   if (tile >= ntiles) return;
-  u32x4 wn[3];                                  // weight pipeline as in the forward kernel
+  f32x4 pf[NCHK];
+  load_patch(tile, pf);
+  // this wave's k steps k0 .. k0 + nk - 1 of its parity (k = 2 ti + half of the output channels; tap index ti of
+  // parity E -> weight tile (ti / NU) * 9 + E + 2 * (ti % NU), gradient pixel (ti / NU) rows up and ti % NU
+  // columns left of the position's): fragments for the block's life, wave-uniform patch offsets
+  const int nk = E ? 6 : (wq < 2 ? 8 : 7);
+  const int k0 = E ? 6 * wq : (wq < 2 ? 8 * wq : 16 + 7 * (wq - 2));
+  bf16x8 wf[KPW][3];
+  int koff[KPW];
   {
-    f32x4 pf[NCHK];
-    load_patch(tile, pf);
-    load_w(0, wn);
-    store_patch(pf);
-    store_w(0, wn);
+    const unsigned char* wrow = reinterpret_cast<const unsigned char*>(d.w) + li * 192 + hh * 16;
+    const int nks = 2 * KH * NU;
+#pragma unroll
+    for (int j = 0; j < KPW; ++j) {
+      int k = k0 + j;
+      k = k < nks ? k : nks - 1;                      // (steps past nk: any valid one, never multiplied)
+      const int ti = k >> 1, ks = k & 1;
+      const int dh = E ? ti >> 2 : (ti * 13) >> 6;    // ti / NU for ti < 15 without a division
+      const int u = ti - dh * NU;
+      koff[j] = ks * 32 - (dh * GWv + u) * PB;
+      const int tile_w = dh * KW + E + 2 * u;
+#pragma unroll
+      for (int q = 0; q < 3; ++q)
+        wf[j][q] = *reinterpret_cast<const bf16x8*>(wrow + tile_w * (C * 192) + q * 64 + ks * 32);
+    }
   }
+  int ph, pw;
+  px_of_row<TW_>(0, li, ph, pw);
+  const unsigned char* Ap = At + ((ph + 2) * GWv + pw + 4) * PB + hh * 16;
+  // owner role: item jj = position (wq & 1) * 16 + (lane >> 3) + 8 (jj & 1) of position group 2 (jj >> 1) + (wq >> 1),
+  // channels 4 (lane & 7) ..
+  const int och = 4 * (lane & 7);
+  const bool msk = d.mask_src != nullptr, fm = d.fm_ref != nullptr;
+  const float fmw = fm ? d.fm_w * (d.fm_wdev ? d.fm_wdev[0] : 1.f) : 0.f;
+  float cs[4] = {0.f, 0.f, 0.f, 0.f};            // column sums of what this lane stores (channels och ..)
+  store_patch(pf);
   __syncthreads();
   for (; tile < ntiles; tile += gridDim.x) {
     const int nxt = tile + gridDim.x;
     const bool more = nxt < ntiles;
-    f32x4 pf[NCHK];
     load_patch(more ? nxt : tile, pf);
     int sq, h0, m0;
     tile_pos(tile, sq, h0, m0);
-    // (round 5) the mask of this tile's outputs is requested HERE, four 16-byte segments per lane (item j =
-    // position (lane >> 3) + 8 j of the wave's 32, channels 4 (lane & 7) ..): read in the epilogue it put a
-    // memory round trip behind every tile's MFMAs with nothing else resident on the CU -- which is why the
-    // fused leaky-ReLU backward used to lose against a separate pass over the map
-    long long ioff[4];
-    f32x4 my[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      int qh, qw;
-      px_of_row<TW_>(pg, (lane >> 3) + 8 * j, qh, qw);
-      const int oh = h0 + qh, om = m0 + qw;
-      ioff[j] = (oh < d.H && om < Wp)
-                    ? (long long)sq * d.y_seq + (long long)oh * d.y_line + (long long)(2 * om + E) * C + 4 * (lane & 7)
-                    : -1;
-      // (a clamped offset, not a pointer select against a zero block: that costs a GOT load + wait per request)
-      if (msk && !fm) my[j] = *reinterpret_cast<const f32x4*>(d.mask_src + (ioff[j] >= 0 ? ioff[j] : 0));
-    }
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; }
-    // patch offset of this parity's tap ti (a literal after unrolling; E is wave-uniform)
-#define F2G_C6_GOFF(TI) ((E ? ((TI) / 4) * GWv + (TI) % 4 : ((TI) / 5) * GWv + (TI) % 5) * PB)
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      load_w(g + 1 < NG ? g + 1 : 0, wn);
-      const int buf = g & 1;                    // (NG is even: group 0 is always in buffer 0)
-#pragma unroll
-      for (int u2 = 0; u2 < 2; ++u2)
-        if (2 * g + u2 < NT) tap6(Ap - F2G_C6_GOFF(2 * g + u2), Bp + (buf * TG + u2) * WBB, acc0, acc1);
-      store_w(buf ^ 1, wn);
-      __syncthreads();
-    }
-#undef F2G_C6_GOFF
-    // ---- epilogue: the wave's tile through its private patch ([position][channel]); optional leaky-ReLU
-    // backward of the layer below (+ feature-matching term), column sums
-#pragma unroll
-    for (int q = 0; q < 16; ++q) turn[((q & 3) + 8 * (q >> 2) + 4 * hh) * 32 + li] = acc0[q] + acc1[q];
-    __builtin_amdgcn_wave_barrier();
-    // three separate paths, so that the plain and the prefetched-mask path carry no wait of the path that
-    // loads its mask / reference values here (a merged loop waited vmcnt(0) -- i.e. for the previous item's
-    // STORE -- in front of every item: 10.5 instead of 6.4 ms over the 45 masked launches of a pass)
-    auto item = [&](int j) {
-      return *reinterpret_cast<const f32x4*>(turn + ((lane >> 3) + 8 * j) * 32 + 4 * (lane & 7));
+    // the mask of this tile's outputs is requested HERE, one 16-byte segment per item: read in the epilogue it
+    // put a memory round trip behind every tile's MFMAs with nothing else resident on the CU -- which is why the
+    // fused leaky-ReLU backward used to lose against a separate pass over the map.  An item's offset is the
+    // tile's (wave-uniform, 64 bits) + the lane's inside the tile (32 bits: y_line < 2^24), recomputed where it
+    // is used instead of kept beside the weights; -1 = outside the map.
+    const long long tbase = (long long)sq * d.y_seq + (long long)h0 * d.y_line + (long long)(2 * m0 + E) * C;
+    auto item_off = [&](int jj) {
+      int qh, qw, l8 = lane >> 3;
+      asm volatile("" : "+v"(l8));               // (opaque: or every item's terms are hoisted and spilled)
+      px_of_row<TW_>(2 * (jj >> 1) + (wq >> 1), (wq & 1) * 16 + l8 + 8 * (jj & 1), qh, qw);
+      return (h0 + qh < d.H && m0 + qw < Wp) ? qh * (int)d.y_line + 2 * qw * C + och : -1;
     };
-    if (!msk) {
+    f32x4 my[4];
+    if (msk && !fm) {
+      // (a clamped offset, not a pointer select against a zero block: that costs a GOT load + wait per request)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const f32x4 u = item(j);
-        if (ioff[j] < 0) continue;
-        cs[0] += u.x, cs[1] += u.y, cs[2] += u.z, cs[3] += u.w;
-        *reinterpret_cast<f32x4*>(d.y + ioff[j]) = u;
-      }
-    } else if (!fm) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const f32x4 u = item(j);
-        if (ioff[j] < 0) continue;
-        f32x4 v;
-        v.x = u.x * (my[j].x > 0.f ? 1.f : d.mask_slope);
-        v.y = u.y * (my[j].y > 0.f ? 1.f : d.mask_slope);
-        v.z = u.z * (my[j].z > 0.f ? 1.f : d.mask_slope);
-        v.w = u.w * (my[j].w > 0.f ? 1.f : d.mask_slope);
-        cs[0] += v.x, cs[1] += v.y, cs[2] += v.z, cs[3] += v.w;
-        *reinterpret_cast<f32x4*>(d.y + ioff[j]) = v;
-      }
-    } else {
-      f32x4 yv[4], fv[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const long long o = ioff[j] >= 0 ? ioff[j] : 0;
-        yv[j] = *reinterpret_cast<const f32x4*>(d.mask_src + o);
-        fv[j] = *reinterpret_cast<const f32x4*>(d.fm_ref + o);
-      }
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const f32x4 u = item(j);
-        if (ioff[j] < 0) continue;
-        float v[4] = {u.x, u.y, u.z, u.w};
-        const float y[4] = {yv[j].x, yv[j].y, yv[j].z, yv[j].w}, f[4] = {fv[j].x, fv[j].y, fv[j].z, fv[j].w};
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float dl = y[e] - f[e];
-          v[e] += fmw * (dl > 0.f ? 1.f : (dl < 0.f ? -1.f : 0.f));
-          v[e] *= y[e] > 0.f ? 1.f : d.mask_slope;
-          cs[e] += v[e];
-        }
-        *reinterpret_cast<f32x4*>(d.y + ioff[j]) = f32x4{v[0], v[1], v[2], v[3]};
+      for (int jj = 0; jj < 4; ++jj) {
+        const int o = item_off(jj);
+        my[jj] = *reinterpret_cast<const f32x4*>(d.mask_src + (o >= 0 ? tbase + o : 0));
       }
     }
-    __builtin_amdgcn_wave_barrier();
-    if (more) store_patch(pf);
-    __syncthreads();
+    f32x16 acc[4];
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4)
+#pragma unroll
+      for (int e = 0; e < 16; ++e) acc[g4][e] = 0.f;
+    // units (k step, position group) with the next unit's fragments requested first: see the forward kernel
+    bf16x8 a[2][3];
+#pragma unroll
+    for (int q = 0; q < 3; ++q) a[0][q] = *reinterpret_cast<const bf16x8*>(Ap + koff[0] + q * 64);
+#pragma unroll
+    for (int u = 0; u < 4 * KPW; ++u) {
+      const int j = u >> 2, g4 = u & 3;
+      if (u + 1 < 4 * KPW) {
+        const unsigned char* an = Ap + koff[(u + 1) >> 2] + ((u + 1) & 3) * PGB;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) a[(u + 1) & 1][q] = *reinterpret_cast<const bf16x8*>(an + q * 64);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      if (j < 6 || j < nk) {
+#define F2G_X6_ONE(I, J) acc[g4] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[u & 1][I], wf[j][J], acc[g4], 0, 0, 0);
+        F2G_X6_ONE(2, 0) F2G_X6_ONE(1, 1) F2G_X6_ONE(0, 2) F2G_X6_ONE(1, 0) F2G_X6_ONE(0, 1) F2G_X6_ONE(0, 0)
+#undef F2G_X6_ONE
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __syncthreads();                              // the owners of the previous tile are done with `red`
+#pragma unroll
+    for (int p2 = 0; p2 < 2; ++p2) {
+      if (p2) __syncthreads();                    // the owners have read phase 0
+      // the mask + feature-matching instance requests this phase's two items of both maps here, in front of the
+      // partial tiles' way through LDS (16 registers that the MFMA loop has no room for)
+      f32x4 fv[2];
+      if (msk && fm) {
+#pragma unroll
+        for (int i2 = 0; i2 < 2; ++i2) {
+          const int o = item_off(2 * p2 + i2);
+          const long long oo = o >= 0 ? tbase + o : 0;
+          my[2 * p2 + i2] = *reinterpret_cast<const f32x4*>(d.mask_src + oo);
+          fv[i2] = *reinterpret_cast<const f32x4*>(d.fm_ref + oo);
+        }
+      }
+#pragma unroll
+      for (int g2 = 0; g2 < 2; ++g2)
+#pragma unroll
+        for (int e = 0; e < 16; ++e)
+          red[((wave * 2 + g2) * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh) * 32 + li] = acc[2 * p2 + g2][e];
+      __syncthreads();                            // (phase 0: every wave is also done with this tile's patch)
+      // ---- epilogue: optional leaky-ReLU backward of the layer below (+ feature-matching term), column sums.
+      // Three separate paths, so that the plain and the mask path carry no wait of the path with two maps.
+#pragma unroll
+      for (int i2 = 0; i2 < 2; ++i2) {
+        const int jj = 2 * p2 + i2;
+        const float* rp = red + (((E * 4) * 2 + (wq >> 1)) * 32 + (wq & 1) * 16 + (lane >> 3) + 8 * i2) * 32 + och;
+        f32x4 s = *reinterpret_cast<const f32x4*>(rp);
+#pragma unroll
+        for (int w4 = 1; w4 < 4; ++w4) {
+          const f32x4 v = *reinterpret_cast<const f32x4*>(rp + w4 * (2 * 32 * 32));
+          s.x += v.x, s.y += v.y, s.z += v.z, s.w += v.w;
+        }
+        const int o = item_off(jj);
+        if (o < 0) continue;
+        float v[4] = {s.x, s.y, s.z, s.w};
+        if (msk && !fm) {
+          const float y[4] = {my[jj].x, my[jj].y, my[jj].z, my[jj].w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) v[e] *= y[e] > 0.f ? 1.f : d.mask_slope;
+        } else if (msk) {
+          const float y[4] = {my[jj].x, my[jj].y, my[jj].z, my[jj].w}, f[4] = {fv[i2].x, fv[i2].y, fv[i2].z, fv[i2].w};
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            const float dl = y[e] - f[e];
+            v[e] += fmw * (dl > 0.f ? 1.f : (dl < 0.f ? -1.f : 0.f));
+            v[e] *= y[e] > 0.f ? 1.f : d.mask_slope;
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) cs[e] += v[e];
+        *reinterpret_cast<f32x4*>(d.y + tbase + o) = f32x4{v[0], v[1], v[2], v[3]};
+      }
+      if (p2 == 0 && more) store_patch(pf);       // the next tile's patch, behind the first phase's items
+    }
   }
+  // column sums: the waves' sums meet in LDS (the patch: nobody reads it after the last tile's MFMAs) and leave
+  // as ONE 32-lane atomic per block.  Four 8-lane atomics per wave were 8192 atomic instructions per launch on
+  // one 128-byte line: serialised in L2 they took longer than the masked launch's extra map read.
   if (d.colsum) {
+    float* csl = reinterpret_cast<float*>(At);     // [8 waves][32 channels]
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
       float v = cs[e];
       v += __shfl_xor(v, 8);
       v += __shfl_xor(v, 16);
       v += __shfl_xor(v, 32);
-      if (lane < 8) atomicAdd(d.colsum + 4 * lane + e, v);
+      if (lane < 8) csl[wave * 32 + 4 * lane + e] = v;
     }
-  }
-}
-
-// The masked instance (mask_src set: the D-step's fused leaky-ReLU backward): the narrow epilogue of round 4
-// with the tile's sixteen mask values per lane requested before the MFMAs.  The LDS-turned epilogue above is
-// 3 % faster without a mask and 30 % SLOWER with one (10.5 : 8.0 ms over the 45 masked launches of a pass,
-// whatever the form of its loads and waits -- profiles/r05_conv32_dgrad_mask.txt), so both stay.
-template <int TH_, int TW_>
-__global__ __launch_bounds__(512, 1) void conv32_s2_dgrad6m_kernel(const f2g_conv32_desc d, int tiles_w,
-                                                                 int tiles_h, int ntiles) {
-  constexpr int IHv = TH_ + KH - 1, GWv = TW_ + 4;
-  constexpr int NCHK = (IHv * GWv * (C / 4) + 511) / 512;
-  constexpr int NG = 8;                                  // groups of 2 taps per parity: 15 -> 8, 12 -> 6
-  static_assert(TH_ * TW_ == 128, "a block owns 128 positions of each column parity");
-  extern __shared__ __attribute__((aligned(16))) unsigned char smb[];
-  unsigned char* At = smb;                               // [IHv][GWv] pixels
-  unsigned char* Bt = smb + IHv * GWv * PB;              // [2 buffers][TG taps][32 rows]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, hh = lane >> 5;
-  const int pg = wave & 3, E = wave >> 2;                // E = column parity of this wave half
-  const int c4 = tid & 7;
-  const int NU = E ? 4 : 5, NT = KH * NU;
-  const int Wp = (d.Win + 1 - E) / 2;                    // input columns of this parity
-  const int px0 = tid >> 3;
-  auto tile_pos = [&](int tile, int& sq, int& h0, int& m0) {
-    const int tw = tile % tiles_w, rest = tile / tiles_w;
-    const int th = rest % tiles_h;
-    sq = rest / tiles_h;
-    h0 = th * TH_;
-    m0 = tw * TW_;
-  };
-  auto load_patch = [&](int tile, f32x4 (&pf)[NCHK]) {
-    int sq, h0, m0;
-    tile_pos(tile, sq, h0, m0);
-    const float* org = d.x + (long long)sq * d.x_seq + (long long)(h0 - 1) * d.x_line + (long long)(m0 - 2) * C + c4 * 4;
-#pragma unroll
-    for (int q = 0; q < NCHK; ++q) {
-      const int px = px0 + 64 * q;
-      const int r = div_small<GWv>(px), xc = px - r * GWv;
-      const int h = h0 - 1 + r, c = m0 - 2 + xc;
-      const bool ok = px < IHv * GWv && h >= 0 && h < d.H && c >= 0 && c < d.Wout;
-      pf[q] = *reinterpret_cast<const f32x4*>(ok ? org + (long long)r * d.x_line + xc * C : c6_zero);
-    }
-  };
-  auto store_patch = [&](const f32x4 (&pf)[NCHK]) {
-#pragma unroll
-    for (int q = 0; q < NCHK; ++q) {
-      const int px = px0 + 64 * q;
-      if (px < IHv * GWv) store_px3(At + px * PB + c4 * 8, pf[q]);
-    }
-  };
-  // weights of group g: taps 2g, 2g+1 of parity 0 (slots 0, 1) and of parity 1 (slots 2, 3); tap index
-  // ti of parity e -> weight tile (ti / nu) * 9 + e + 2 * (ti % nu); image rows = (tile, ci), 192 bytes each
-  const unsigned char* wimg = reinterpret_cast<const unsigned char*>(d.w);
-  int wsrc[3], wdst[3], wslot[3];
-#pragma unroll
-  for (int k = 0; k < 3; ++k) {
-    const int c = tid + 512 * k;
-    const int u = c / WCH, rem = c - u * WCH;
-    const int row = rem / 12, part = rem - row * 12;
-    wslot[k] = u;
-    wsrc[k] = row * 192 + part * 16;
-    wdst[k] = u * WBB + row * PB + part * 16;
-  }
-  auto load_w = [&](int g, u32x4 (&wn)[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-      const int e = wslot[k] >> 1, nu = e ? 4 : 5, nt = KH * nu;
-      int ti = 2 * g + (wslot[k] & 1);
-      ti = ti < nt ? ti : nt - 1;
-      const int dh = e ? ti >> 2 : (ti * 13) >> 6;        // ti / nu for ti < 15 without a division
-      const int tile_w = dh * KW + e + 2 * (ti - dh * nu);
-      wn[k] = *reinterpret_cast<const u32x4*>(wimg + (long long)tile_w * (C * 192) + wsrc[k]);
-    }
-  };
-  auto store_w = [&](int buf, const u32x4 (&wn)[3]) {
-#pragma unroll
-    for (int k = 0; k < 3; ++k) *reinterpret_cast<u32x4*>(Bt + buf * (TG * WBB) + wdst[k]) = wn[k];
-  };
-  int ph, pw;
-  px_of_row<TW_>(pg, li, ph, pw);
-  const unsigned char* Ap = At + ((ph + 2) * GWv + pw + 4) * PB + hh * 16;
-  const unsigned char* Bp = Bt + (E * 2) * WBB + li * PB + hh * 16;
-  const bool msk = d.mask_src != nullptr, fm = d.fm_ref != nullptr;
-  const float fmw = fm ? d.fm_w * (d.fm_wdev ? d.fm_wdev[0] : 1.f) : 0.f;
-  float cs = 0.f;
-
-  int tile = blockIdx.x;
-  if (tile >= ntiles) return;
-  u32x4 wn[3];                                  // weight pipeline as in the forward kernel
-  {
-    f32x4 pf[NCHK];
-    load_patch(tile, pf);
-    load_w(0, wn);
-    store_patch(pf);
-    store_w(0, wn);
-  }
-  __syncthreads();
-  for (; tile < ntiles; tile += gridDim.x) {
-    const int nxt = tile + gridDim.x;
-    const bool more = nxt < ntiles;
-    f32x4 pf[NCHK];
-    load_patch(more ? nxt : tile, pf);
-    int sq, h0, m0;
-    tile_pos(tile, sq, h0, m0);
-    // (round 5) the mask of this tile's outputs is requested HERE, sixteen values per lane: read in the
-    // epilogue it put a memory round trip behind every tile's MFMAs with nothing else resident on the CU --
-    // which is why the fused leaky-ReLU backward used to lose against a separate pass over the map
-    float my[16];
-    if (msk && !fm) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) {
-        int qh, qw;
-        px_of_row<TW_>(pg, (q & 3) + 8 * (q >> 2) + 4 * hh, qh, qw);
-        const int oh = h0 + qh, om = m0 + qw;
-        const long long off = (long long)sq * d.y_seq + (long long)oh * d.y_line + (long long)(2 * om + E) * C + li;
-        my[q] = (oh < d.H && om < Wp) ? d.mask_src[off] : 1.f;
-      }
-    }
-    f32x16 acc0, acc1;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) { acc0[e] = 0.f; acc1[e] = 0.f; }
-    // patch offset of this parity's tap ti (a literal after unrolling; E is wave-uniform)
-#define F2G_C6_GOFF(TI) ((E ? ((TI) / 4) * GWv + (TI) % 4 : ((TI) / 5) * GWv + (TI) % 5) * PB)
-#pragma unroll
-    for (int g = 0; g < NG; ++g) {
-      load_w(g + 1 < NG ? g + 1 : 0, wn);
-      const int buf = g & 1;                    // (NG is even: group 0 is always in buffer 0)
-#pragma unroll
-      for (int u2 = 0; u2 < 2; ++u2)
-        if (2 * g + u2 < NT) tap6(Ap - F2G_C6_GOFF(2 * g + u2), Bp + (buf * TG + u2) * WBB, acc0, acc1);
-      store_w(buf ^ 1, wn);
-      __syncthreads();
-    }
-#undef F2G_C6_GOFF
-    // ---- epilogue: optional leaky-ReLU backward of the layer below (+ feature-matching term)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) {
-      int qh, qw;
-      px_of_row<TW_>(pg, (q & 3) + 8 * (q >> 2) + 4 * hh, qh, qw);
-      const int oh = h0 + qh, om = m0 + qw;
-      if (oh < d.H && om < Wp) {
-        const long long off = (long long)sq * d.y_seq + (long long)oh * d.y_line + (long long)(2 * om + E) * C + li;
-        float v = acc0[q] + acc1[q];
-        if (msk) {
-          const float y = fm ? d.mask_src[off] : my[q];
-          if (fm) {
-            const float dl = y - d.fm_ref[off];
-            v += fmw * (dl > 0.f ? 1.f : (dl < 0.f ? -1.f : 0.f));
-          }
-          v *= y > 0.f ? 1.f : d.mask_slope;
-        }
-        cs += v;
-        d.y[off] = v;
-      }
-    }
-    if (more) store_patch(pf);
     __syncthreads();
-  }
-  if (d.colsum) {
-    cs += __shfl_xor(cs, 32);
-    if (hh == 0) atomicAdd(d.colsum + li, cs);
+    if (tid < 32) {
+      float v = csl[tid];
+#pragma unroll
+      for (int w8 = 1; w8 < 8; ++w8) v += csl[w8 * 32 + tid];
+      atomicAdd(d.colsum + tid, v);
+    }
   }
 }
 
@@ -1123,11 +977,11 @@ __global__ __launch_bounds__(512, 1) void conv33_wgrad6_kernel(const f2g_conv32_
 
 template <int TH_, int TW_>
 constexpr size_t fwd6_smem() {
-  return (size_t)2 * ((TH_ + 2) * (TW_ + 4) * PB + 64) + 2 * TG * WBB + 4 * 16 * 64 * sizeof(float);
+  return (size_t)2 * ((TH_ + 2) * (TW_ + 4) * PB + 64) + 8 * 2 * 32 * 32 * sizeof(float);
 }
 template <int TH_, int TW_>
 constexpr size_t dgrad6_smem() {
-  return (size_t)(TH_ + 2) * (TW_ + 4) * PB + 2 * TG * WBB + 8 * 32 * 32 * sizeof(float);
+  return (size_t)(TH_ + 2) * (TW_ + 4) * PB + 8 * 2 * 32 * 32 * sizeof(float);
 }
 
 }  // namespace
@@ -1169,7 +1023,7 @@ int f2g_conv32_dgrad6_launch(const f2g_conv32_desc* d, hipStream_t st) {
   const int th = tall ? 16 : 8, tw = tall ? 8 : 16;
   const int tiles_h = (d->H + th - 1) / th, tiles_w = (Wp0 + tw - 1) / tw;
   const long long nt = (long long)tiles_h * tiles_w * d->S;
-  if (nt >= (1ll << 30) || d->x_line >= (1ll << 24)) return F2G_EINVAL;
+  if (nt >= (1ll << 30) || d->x_line >= (1ll << 24) || d->y_line >= (1ll << 24)) return F2G_EINVAL;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_dgrad6_kernel<8, 16>),
@@ -1179,23 +1033,6 @@ int f2g_conv32_dgrad6_launch(const f2g_conv32_desc* d, hipStream_t st) {
     attr = true;
   }
   const int grid = (int)(nt < 256 ? nt : 256);
-  if (d->mask_src) {      // masked: the narrow epilogue with the prefetched mask (see conv32_s2_dgrad6m_kernel)
-    static bool attrm = false;
-    if (!attrm) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_dgrad6m_kernel<8, 16>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(dgrad6_smem<8, 16>()));
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_dgrad6m_kernel<16, 8>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)(dgrad6_smem<16, 8>()));
-      attrm = true;
-    }
-    if (tall)
-      hipLaunchKernelGGL((conv32_s2_dgrad6m_kernel<16, 8>), dim3(grid), dim3(512), (dgrad6_smem<16, 8>()), st, *d,
-                         tiles_w, tiles_h, (int)nt);
-    else
-      hipLaunchKernelGGL((conv32_s2_dgrad6m_kernel<8, 16>), dim3(grid), dim3(512), (dgrad6_smem<8, 16>()), st, *d,
-                         tiles_w, tiles_h, (int)nt);
-    return f2g_check_launch();
-  }
   if (tall)
     hipLaunchKernelGGL((conv32_s2_dgrad6_kernel<16, 8>), dim3(grid), dim3(512), (dgrad6_smem<16, 8>()), st, *d,
                        tiles_w, tiles_h, (int)nt);
