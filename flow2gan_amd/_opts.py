@@ -16,7 +16,8 @@ x6_min_k, x6_min_rows, x6_nopass_k, x6f_min_k, x6f_min_n, x6f_min_tiles, x6f_tal
 fp16x3_wgrad_min_rows (the fewest reduction rows at which a weight gradient takes the fp16x3 weight-gradient kernel),
 fp16x3_tap_min_rows (the fewest output rows at which a GEMM over stride-1 windows of a halo map takes the fp16x3
 tap-walking kernel; the route also asks for a reduction of at least x6_min_k, i.e. the launches the bf16x6 mode gives
-to its image kernels).
+to its image kernels), fp16x3_tapw_min_rows (the fewest reduction rows at which the weight gradient of a stride-1
+five-tap layer over a halo map takes the fp16x3 tap-walking weight-gradient kernel; off by default).
 
 Environment switches that remain on their own (user-facing, or needed before anything is imported):
 F2G_GEMM (arithmetic of the GEMMs), F2G_STREAMS (launch lanes), F2G_DETERMINISTIC (no splits on the library's

@@ -1,5 +1,5 @@
 // What more than one of the GEMM translation units needs (gemm.hip, gemm_lean.hip, gemm_wgrad.hip, gemm_x6.hip,
-// gemm_x6p.hip, gemm_f16.hip, gemm_f16p.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
+// gemm_x6p.hip, gemm_f16.hip, gemm_f16p.hip, gemm_f16wt.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
 // three-piece split, the LDS barrier, the lab switches, and the host functions that cross those files.  Everything
 // defined here has internal linkage; no GEMM file includes another.
 #pragma once
@@ -26,6 +26,12 @@ int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st);
 // both fp32 operands are replaced by those images, 0 = not for this kernel; `taps` receives 5 or 2
 int f2g_h3p_ok(const f2g_gemm_desc& d, int* taps);
 int f2g_launch_h3p(const f2g_gemm_desc& d, int taps, hipStream_t st);
+// gemm_f16wt.hip: precision 4, form 2 over unbounded stride-1 windows of 5 positions of a halo map (gemm_h3wt_kernel:
+// the tap-walking weight gradient).  f2g_h3wt_ok: 1 = runs as handed over (A and the whole map as
+// f2g_split_f16x2_cols images with their reciprocal scales), 2 = once both fp32 operands are replaced by those
+// images, 0 = not for this kernel
+int f2g_h3wt_ok(const f2g_gemm_desc& d);
+int f2g_launch_h3wt(const f2g_gemm_desc& d, hipStream_t st);
 
 // ---- lab switches (product builds: both 0) ---------------------------------------------------------------------
 // F2G_LABVAR (tools/micro/build_variants.sh; timing only): ablations of the bf16 lean K loop (gemm_lean.hip) --

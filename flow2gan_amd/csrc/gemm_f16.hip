@@ -1,7 +1,8 @@
 // fp16x3: fp32-class products from TWO scaled fp16 pieces per operand, three MFMAs per product (gemm.hip has the
 // family, gemm_common.h what the GEMM files share).  f2g_split_f16x2 writes the operand images, gemm_h3_kernel reads them;
 // f2g_split_f16x2_cols writes the images of K-major operands (one scale per column), gemm_h3w_kernel reads those.
-// (gemm_f16p.hip: f2g_split_f16x2_seq and gemm_h3p_kernel, the same over stride-1 windows of a halo map.)
+// (gemm_f16p.hip: f2g_split_f16x2_seq and gemm_h3p_kernel, the same over stride-1 windows of a halo map;
+// gemm_f16wt.hip: gemm_h3wt_kernel, the weight gradient of such a layer over column images.)
 #include <stddef.h>
 #include <stdint.h>
 
@@ -396,6 +397,8 @@ inline bool h3w_operand_ok(const f2g_operand& S) {
 }
 
 int h3w_ok(const f2g_gemm_desc& d) {
+  // B a window operand: the tap-walking weight gradient (gemm_f16wt.hip) or nothing
+  if (d.precision == 4 && host_plain(d.A) && !host_plain(d.B)) return f2g_h3wt_ok(d);
   if (d.precision != 4 || d.A.rows != d.B.rows || !h3w_operand_ok(d.A) || !h3w_operand_ok(d.B)) return 0;
   const f2g_epilogue& E = d.E;
   if (E.x3_out || E.colsum_part_ld > 0 || E.c_bf16 || (d.split_k > 1 && !E.atomic)) return 0;
@@ -407,7 +410,8 @@ int h3w_ok(const f2g_gemm_desc& d) {
 
 // 0: not for these kernels; 1: as handed over (form 0: both operands f2g_split_f16x2 images -- over stride-1 windows
 // of a halo map: f2g_split_f16x2_seq images --, form 2: both f2g_split_f16x2_cols images, with their reciprocal
-// scales); 2: once both fp32 operands are replaced by their images
+// scales -- B as unbounded stride-1 five-tap windows of a halo map: the image of the whole map --); 2: once both fp32
+// operands are replaced by their images
 int h3_ok(const f2g_gemm_desc& d) {
   if (!d.A.base || !d.B.base || !d.E.C) return 0;
   if (d.form == 2) return h3w_ok(d);
@@ -433,7 +437,8 @@ int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st) {
   if (h3_ok(d) != 1) {
     f2g_set_error("f2g_gemm precision 4: form 0 over f2g_split_f16x2 images, or form 2 over f2g_split_f16x2_cols "
                   "images, of two plain matrices, or form 0 over f2g_split_f16x2_seq images of stride-1 windows of 5 or "
-                  "2 positions (f2g_gemm_f16_ok(d) != 1 for this descriptor)");
+                  "2 positions, or form 2 + atomic over f2g_split_f16x2_cols images of a plain matrix and of the map "
+                  "under unbounded stride-1 windows of 5 positions (f2g_gemm_f16_ok(d) != 1 for this descriptor)");
     return F2G_EINVAL;
   }
   if (d.form == 0 && d.A.split == 7) {
@@ -441,6 +446,7 @@ int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st) {
     (void)f2g_h3p_ok(d, &taps);
     return f2g_launch_h3p(d, taps, st);
   }
+  if (d.form == 2 && !host_plain(d.B)) return f2g_launch_h3wt(d, st);
   if (d.form == 2) {
     const int M = d.A.cols, N = d.B.cols, K = d.A.rows, split = d.split_k > 1 ? d.split_k : 1;
     const int kchunk = ((K + split - 1) / split + BK - 1) / BK * BK;

@@ -463,7 +463,7 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
     padded to whole K slabs): what bench.py's FLOP count uses; the launch itself ignores them.
     split_k: 0 = let the library decide (forms 0/1: split-K onto a zeroed output when the tile
     grid would leave most of the last wave of CUs idle), 1 = off, > 1 = as given."""
-    global FP16X3_LAUNCHES, FP16X3_WGRAD_LAUNCHES, FP16X3_TAP_LAUNCHES
+    global FP16X3_LAUNCHES, FP16X3_WGRAD_LAUNCHES, FP16X3_TAP_LAUNCHES, FP16X3_TAPW_LAUNCHES
     if form == 1:
         # data gradient C[r,n] = sum_k A[r,k] W[k,n] as a forward GEMM against the cached transpose
         # W^T [n][k]: same products in the same order, and the lean forward kernel applies
@@ -529,14 +529,29 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
             f16 = True
             FP16X3_LAUNCHES += 1
     if GEMM_PRECISION == 3 and FP16X3 and form == 2 and atomic and A.split == 0 and Bm.split == 0 \
-            and A.lrelu_src is None and A.rows >= FP16X3_WGRAD_MIN_ROWS and out.dtype == torch.float32:
-        # fp16x3 weight gradient: both operands are activations, K-major -- their f2g_split_f16x2_cols images (one
-        # scale per column) are made here, per call; what the library declines goes the bf16x6 way
+            and A.lrelu_src is None and A.rows >= FP16X3_WGRAD_MIN_ROWS and out.dtype == torch.float32 \
+            and Bm.P0 == 1 and Bm.P1 == 1:
+        # fp16x3 weight gradient: both operands are PLAIN activation matrices, K-major -- their f2g_split_f16x2_cols
+        # images (one scale per column) are made here, per call; what the library declines goes the bf16x6 way
         d.precision = 4
         if L.lib.f2g_gemm_f16_ok(C.byref(d)) == 2:
             d.A, d.B = _f16_cols_operand(A), _f16_cols_operand(Bm)
             f16 = True
             FP16X3_WGRAD_LAUNCHES += 1
+    if GEMM_PRECISION == 3 and FP16X3 and form == 2 and atomic and A.split == 0 and Bm.split == 0 \
+            and A.lrelu_src is None and A.P0 == 1 and A.P1 == 1 and Bm.P1 == 1 and Bm.P0 > 1 and Bm.step0 == 1 \
+            and Bm.unbounded and Bm.cols == 5 * Bm.unit and A.rows >= FP16X3_TAPW_MIN_ROWS \
+            and out.dtype == torch.float32 and _f16_cols_window_ok(Bm):
+        # fp16x3 tap-walking weight gradient (the MPD's stride-1 1024-channel layer): the gradient as a plain K-major
+        # matrix, the map under unbounded stride-1 windows of five positions.  The taps shift ROWS of the map, so one
+        # scale per COLUMN of the whole map serves every tap: both f2g_split_f16x2_cols images are made here, per
+        # call (the gradient's into a buffer of its own -- the data gradient reads the fp32 values again); what the
+        # library declines goes the bf16x6 way
+        d.precision = 4
+        if L.lib.f2g_gemm_f16_ok(C.byref(d)) == 2:
+            d.A, d.B = _f16_cols_operand(A), _f16_cols_window_operand(Bm)
+            f16 = True
+            FP16X3_TAPW_LAUNCHES += 1
     if GEMM_PRECISION == 3 and FP16X3 and form == 0 and A.split == 0 and Bm.split == 0 and A.P1 == 1 and A.P0 > 1 \
             and A.step0 == 1 and A.cols in (5 * A.unit, 2 * A.unit) and A.rows >= FP16X3_TAP_MIN_ROWS \
             and A.cols >= X6_MIN_K \
@@ -1038,6 +1053,37 @@ def _f16_cols_operand(o: Operand) -> Operand:
     return n
 
 
+def _f16_cols_window_ok(o: Operand) -> bool:
+    """unbounded windows over a whole contiguous fp32 buffer of rows of `unit` floats, from its first float (what
+    win1d(..., unbounded=True) grants).  The column maxima of f2g_split_f16x2_cols cover EVERY row of the map, the
+    halo rows included: they are zero in the MPD maps and stay zero in the image (as for _f16_seq_window_ok, the
+    buffer must be fully initialised)."""
+    t = o._keep[0]
+    if t is None or t.dtype != torch.float32 or not t.is_contiguous() or not o.unbounded or o.unit % 4:
+        return False
+    if o.base != ptr(t) or ptr(t) % 16 or o.rows % o.P0 or o.seq_stride % o.unit:
+        return False
+    return (o.rows // o.P0) * o.seq_stride == t.numel()
+
+
+def _f16_cols_window_operand(o: Operand) -> Operand:
+    """Copy of an unbounded window operand of a weight gradient over the f2g_split_f16x2_cols image of its WHOLE map
+    (xrows x unit floats, halo rows included; same addressing, so the window fields stay as they are), made per call:
+    [image | reciprocal column scales: unit | the call's scratch words: unit] in one allocation."""
+    Cin = o.unit
+    xrows = (o.rows // o.P0) * (o.seq_stride // Cin)
+    buf = torch.empty(xrows * Cin + 2 * Cin, device=o._keep[0].device, dtype=torch.float32)
+    call("f2g_split_f16x2_cols", ptr(buf), ptr(buf) + 4 * xrows * Cin, ptr(buf) + 4 * (xrows * Cin + Cin), o.base, Cin,
+         xrows, Cin)
+    n = Operand()
+    C.memmove(C.byref(n), C.byref(o), C.sizeof(Operand))
+    n.base = ptr(buf)
+    n.rscale = ptr(buf) + 4 * xrows * Cin
+    n.split = 6
+    n._keep = (buf,) + tuple(o._keep)
+    return n
+
+
 CONV32_X6 = opt("conv32_x6", True)    # bf16x6 mode: fp32-class direct MRD convs (bench.py reads it)
 
 
@@ -1401,6 +1447,18 @@ FP16X3_WGRAD_LAUNCHES = 0  # launches gemm_h3w_kernel took (tests and tools)
 FP16X3_TAP_OFF = 1 << 30
 FP16X3_TAP_MIN_ROWS = opt("fp16x3_tap_min_rows", 9504)
 FP16X3_TAP_LAUNCHES = 0    # launches gemm_h3p_kernel took (tests and tools)
+# fewest reduction rows at which the weight gradient of a stride-1 five-tap layer over a halo map (the MPD's
+# 1024-channel layer; ops.wgrad over unbounded windows) goes to gemm_h3wt_kernel: the gradient and the whole map pay
+# f2g_split_f16x2_cols per call (two reads and one write each: 12 bytes per element), against gemm_leanw6t_kernel's
+# in-kernel split.  Measured per launch, both image calls included, on one box (tools/fp16x3_tapw_shapes.py ->
+# profiles/fp16x3_tapw_shapes.txt): all ten launches win by more than their spread -- 0.74 of the bf16x6 time at B = 64
+# (39168-43648 rows, 1.22-1.35 ms against 1.65-1.81), 0.78-0.80 at B = 16 (9792-10912 rows, spreads up to 0.19) -- but
+# the stage-2 step moved by less than its spread in two runs (146.76 -> 144.33 ms, spreads 0.010 / 0.100; 144.95 ->
+# 143.38, spreads 0.005 / 0.049; five launches per step).
+# Hence the default, until a quieter step measurement: FP16X3_TAP_OFF = the route is disabled (tests and the tool
+# lower it; F2G_OPTS=fp16x3_tapw_min_rows=1 turns it on)
+FP16X3_TAPW_MIN_ROWS = opt("fp16x3_tapw_min_rows", FP16X3_TAP_OFF)
+FP16X3_TAPW_LAUNCHES = 0   # launches gemm_h3wt_kernel took (tests and tools)
 
 
 def set_gemm_precision(name: str) -> None:

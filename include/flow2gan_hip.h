@@ -84,7 +84,9 @@ typedef struct {
    * 5: `base` holds the two-piece fp16 image written by f2g_split_f16x2 (same addressing as the plain fp32
    *    matrix it was made of) and `rscale` its reciprocal row scales (precision 4, form 0, plain matrices only);
    * 6: `base` holds the two-piece fp16 image written by f2g_split_f16x2_cols (same addressing as the plain fp32
-   *    matrix) and `rscale` its reciprocal COLUMN scales, `cols` floats (precision 4, form 2, plain matrices only);
+   *    matrix) and `rscale` its reciprocal COLUMN scales, `cols` floats (precision 4, form 2: plain matrices, or --
+   *    operand B of the tap-walking weight gradient -- unbounded stride-1 windows of 5 positions over a halo map:
+   *    the image of the WHOLE contiguous map as a (map rows, unit) matrix, `unit` scales);
    * 7: `base` holds the flat two-piece fp16 image written by f2g_split_f16x2_seq (precision 4, form 0, over stride-1
    *    windows of 5 or 2 positions only): operand A = windows over a halo map, the image of the contiguous buffer
    *    the windows address -- same addressing as the fp32 buffer, element e in the 128 bytes at (e / 32) * 128 --
@@ -191,6 +193,9 @@ typedef struct {
    *     <= 3 * 2^-22): form 0 over two plain matrices, both given as f2g_split_f16x2 images (f2g_operand.split = 5
    *     with rscale); form 2 (weight gradient) over two plain matrices, both given as f2g_split_f16x2_cols images
    *     (split = 6 with rscale: one scale per column, which leaves the sum over rows), E.atomic when split_k > 1;
+   *     form 2 with E.atomic over a plain matrix A and unbounded stride-1 windows B of 5 positions of a halo map (the
+   *     taps shift ROWS of the map, so one scale per column of the whole map leaves every tap's sum), both given as
+   *     f2g_split_f16x2_cols images (split = 6 with rscale);
    *     form 0 over stride-1 windows of 5 or 2 positions of a halo map against a plain weight matrix, both given as
    *     f2g_split_f16x2_seq images (split = 7 with rscale: one scale per sequence, which leaves every window's sum).
    *     A descriptor f2g_gemm_f16_ok does not answer with 1 is F2G_EINVAL, never run elsewhere. */
@@ -278,7 +283,17 @@ int f2g_gemm_f16_ok(const f2g_gemm_desc* d);
  * epilogue; cols % 4 == 0 for both operands (partial 128 x 128 tiles are fine), split_k > 1 with E.atomic only (the
  * rescale is linear: partial tiles are rescaled, then added), no window operand, no bf16 output, no x3_out, no
  * colsum_part_ld.  f2g_gemm_f16_ok answers for form 2 as for form 0 (2 = once both fp32 operands are replaced by
- * their column images), asked with precision = 4 set as for the launch: 0 at any other precision.  f2g_gemm_last_kernel reports "h3w". */
+ * their column images), asked with precision = 4 set as for the launch: 0 at any other precision.  f2g_gemm_last_kernel reports "h3w".
+ * ONE window operand is taken, the tap-walking weight gradient gw[co][t * unit + ci] += sum_r g[r][co] x[r + t -
+ * pad0][ci] of a stride-1 five-tap layer (gemm_h3wt_kernel, what gemm_leanw6t_kernel runs at precision 3): A plain
+ * with cols % 128 == 0; B with step0 == 1, P1 == 1, cols == 5 * unit, unit % 128 == 0, unbounded, seq_stride == P0 *
+ * unit (one flat row index over the whole contiguous map), 0 <= pad0 <= 8; a bare atomic epilogue (E.atomic, scale 0
+ * or 1, nothing else); both byte extents below 2^31 - 2^20.  A.base is the column image of the gradient, B.base the
+ * column image of the whole map made by ONE f2g_split_f16x2_cols call over (map rows, unit) with ld = unit -- halo
+ * rows included: zero rows stay zero and do not move a column's maximum --, B.rscale its `unit` scales.  The rescale
+ * (acc0 + 2^-11 acc1) * rscale_a[co] * rscale_b[ci] precedes the atomic add, so the K chunks the launcher cuts add up.
+ * f2g_gemm_f16_ok answers 1 / 2 / 0 as above; every other window operand at form 2 is 0 (F2G_EINVAL from f2g_gemm).
+ * f2g_gemm_last_kernel reports "h3wt<taps=5>", path 6. */
 int f2g_split_f16x2_cols(float* dst, float* rscale, uint32_t* work, const float* src, int64_t ld, int32_t rows,
                          int32_t cols, f2g_stream_t stream);
 /* The image of a HALO MAP whose stride-1 conv windows are the A operand of a precision-4, form-0 GEMM, and of that
