@@ -1,7 +1,7 @@
 // What more than one of the GEMM translation units needs (gemm.hip, gemm_lean.hip, gemm_wgrad.hip, gemm_x6.hip,
 // gemm_x6p.hip, gemm_f16.hip, gemm_f16p.hip, gemm_f16wt.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
 // three-piece split, the LDS barrier, the lab switches, and the host functions that cross those files.  Everything
-// defined here has internal linkage; no GEMM file includes another.
+// defined here has internal linkage; no GEMM file includes another.  (gemm_f16_common.h: what only fp16x3 shares.)
 #pragma once
 #include "common.h"
 
@@ -18,8 +18,8 @@ bool f2g_leanw_fp32_takes(const f2g_gemm_desc& d, int split);
 int f2g_launch_leanw(const f2g_gemm_desc& d, int pieces, int split, hipStream_t st);
 // gemm_x6.hip: form 0 at precision 3 (checks the descriptor, picks the kernel, launches)
 int f2g_gemm_x6(const f2g_gemm_desc& d, hipStream_t st);
-// gemm_f16.hip: precision 4 -- form 0 over f2g_split_f16x2 images, form 2 over f2g_split_f16x2_cols images (checks
-// the descriptor, launches)
+// gemm_f16.hip: precision 4 -- decides which of the four fp16x3 kernels a descriptor belongs to (its own two: form 0
+// over f2g_split_f16x2 images, form 2 over f2g_split_f16x2_cols images; the two below), checks it, launches that one
 int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st);
 // gemm_f16p.hip: precision 4, form 0 over stride-1 windows of 5 or 2 positions of a halo map (gemm_h3p_kernel).
 // f2g_h3p_ok: 1 = runs as handed over (both operands f2g_split_f16x2_seq images with their reciprocal scales), 2 = once
@@ -93,6 +93,13 @@ inline bool host_plain(const f2g_operand& S) {
 }
 
 inline bool al16(const void* p) { return (((uintptr_t)p) & 15) == 0; }
+
+// A precision-4 kernel's answer for an operand pair it otherwise accepts, given the kind of fp16 image it reads
+// (f2g_operand.split): 1 = both are such images with their reciprocal scales, 2 = both are fp32, 0 = anything else
+inline int f16_images_status(const f2g_operand& A, const f2g_operand& B, int split) {
+  if (A.split == split && B.split == split) return A.rscale && B.rscale ? 1 : 0;
+  return A.split == 0 && B.split == 0 ? 2 : 0;
+}
 
 // extent in elements of what the A operand's rows may touch, or 0 if precision 3 cannot read it
 inline long long x6_a_extent(const f2g_operand& A) {

@@ -2,16 +2,15 @@
 // family, gemm_common.h what the GEMM files share).  f2g_split_f16x2 writes the operand images, gemm_h3_kernel reads them;
 // f2g_split_f16x2_cols writes the images of K-major operands (one scale per column), gemm_h3w_kernel reads those.
 // (gemm_f16p.hip: f2g_split_f16x2_seq and gemm_h3p_kernel, the same over stride-1 windows of a halo map;
-// gemm_f16wt.hip: gemm_h3wt_kernel, the weight gradient of such a layer over column images.)
+// gemm_f16wt.hip: gemm_h3wt_kernel, the weight gradient of such a layer over column images.)  The four kernels share
+// gemm_f16_common.h, the image writers split_f16.h; h3_route_of below says which kernel a descriptor belongs to.
 #include <stddef.h>
 #include <stdint.h>
 
-#include "gemm_common.h"
+#include "gemm_f16_common.h"
 #include "split_f16.h"
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // One wave per row, four rows per block and pass (split_f16.h has the routine and the arithmetic)
 __global__ __launch_bounds__(256) void split_f16x2_kernel(float* dst, float* rscale, const float* src, long long ld,
@@ -68,9 +67,9 @@ __global__ __launch_bounds__(256) void cols_split_kernel(float* dst, float* rsca
   float s[4];
 #pragma unroll
   for (int j = 0; j < 4; ++j) {
-    const int sexp = f2g_f16_scale_exp(work[c0 + j]);
-    s[j] = __uint_as_float((unsigned)(127 + sexp) << 23);
-    if (blockIdx.y == 0 && rl == 0) rscale[c0 + j] = __uint_as_float((unsigned)(127 - sexp) << 23);
+    float rs;
+    f2g_f16_scales(work[c0 + j], s[j], rs);
+    if (blockIdx.y == 0 && rl == 0) rscale[c0 + j] = rs;
   }
   const float4 s4 = make_float4(s[0], s[1], s[2], s[3]);
   // four rows at a time: all loads before the first store (dst may be src, which the compiler must assume anyway)
@@ -123,12 +122,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(const f2g_gemm_desc d, 
   const int nt = K / BK;
 
   f32x16 acc[2][2], acx[2][2];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[mi][ni][e] = acx[mi][ni][e] = 0.f;
+  h3_zero<4>(acc[0], acx[0]);
 
   auto gload = [&](int so, u32x4 (&la)[4], u32x4 (&lb)[4]) {
 #pragma unroll
@@ -156,20 +150,6 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(const f2g_gemm_desc d, 
       fb[2 + i] = *reinterpret_cast<const f16x8*>(rB + off + i * 32 * LDR + ks * 8 + 16);
     }
   };
-  auto mfma12 = [&](const f16x8 (&fa)[4], const f16x8 (&fb)[4]) {
-#pragma unroll
-    for (int term = 0; term < 3; ++term)
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          if (term == 0)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[mi], fb[ni], acc[mi][ni], 0, 0, 0);
-          else
-            acx[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(term == 1 ? fa[mi] : fa[2 + mi],
-                                                                 term == 1 ? fb[2 + ni] : fb[ni], acx[mi][ni], 0, 0, 0);
-        }
-  };
   // two register stages: slab t's MFMAs run while slab t + 1 (in registers since the previous step) goes to LDS and
   // the loads of slab t + 2 fly
   u32x4 xa[4], xb[4], ya[4], yb[4];
@@ -182,10 +162,10 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(const f2g_gemm_desc d, 
     f16x8 fa[4], fb[4];
     gload(t + 2 < nt ? (t + 2) * BK * 4 : 0, la, lb);      // past the end: the first slab again (never used)
     frags(curoff, 0, fa, fb);
-    mfma12(fa, fb);
+    h3_mfma12(acc, acx, fa, fa + 2, fb, fb + 2);
     lstore(nxtoff, wa, wb);
     frags(curoff, 1, fa, fb);
-    mfma12(fa, fb);
+    h3_mfma12(acc, acx, fa, fa + 2, fb, fb + 2);
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
@@ -197,8 +177,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(const f2g_gemm_desc d, 
   }
   if (t < nt) step(t, 0, TSZ, xa, xb, ya, yb);
 
-  // v = (acc0 + 2^-11 acc1) / s_a[row] / s_b[col]: the reciprocals one after the other (their product may leave the
-  // float range), then the generic epilogue on v
+  // v = (acc0 + 2^-11 acc1) / s_a[row] / s_b[col] (gemm_f16_common.h: h3_value), then the generic epilogue on v
 #pragma unroll
   for (int ni = 0; ni < 2; ++ni) {
     const int col = n0 + (wn * 2 + ni) * 32 + li;
@@ -209,7 +188,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h3_kernel(const f2g_gemm_desc d, 
       for (int e = 0; e < 16; ++e) {
         const int row = m0 + (wm * 2 + mi) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
         const float sa = row < M ? d.A.rscale[row] : 0.f;
-        acc[mi][ni][e] = (acc[mi][ni][e] + acx[mi][ni][e] * 0x1p-11f) * sa * sb;
+        acc[mi][ni][e] = h3_value(acc[mi][ni][e], acx[mi][ni][e], sa, sb);
       }
   }
   gemm_epilogue<2, 2>(d.E, acc, M, N, m0, n0, wm, wn, li, h, true);
@@ -272,12 +251,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h3w_kernel(const f2g_gemm_desc d,
   }
 
   f32x16 acc[2][2], acx[2][2];
-#pragma unroll
-  for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-    for (int ni = 0; ni < 2; ++ni)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[mi][ni][e] = acx[mi][ni][e] = 0.f;
+  h3_zero<4>(acc[0], acx[0]);
 
   int ka = (int)((long long)kbeg * d.A.seq_stride * 4), kb = (int)((long long)kbeg * d.B.seq_stride * 4);
   const int ka0 = ka, kb0 = kb;
@@ -307,25 +281,11 @@ __global__ __launch_bounds__(256, 2) void gemm_h3w_kernel(const f2g_gemm_desc d,
     const unsigned char* base = sm + bufoff + ks * 16 * 256;
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-      fa[t] = __builtin_bit_cast(f16x8, tr_frag(base + rofA[t]));
-      fa[2 + t] = __builtin_bit_cast(f16x8, tr_frag(base + PL + rofA[t]));
-      fb[t] = __builtin_bit_cast(f16x8, tr_frag(base + 2 * PL + rofB[t]));
-      fb[2 + t] = __builtin_bit_cast(f16x8, tr_frag(base + 3 * PL + rofB[t]));
+      fa[t] = tr_frag_f16<256>(base + rofA[t]);
+      fa[2 + t] = tr_frag_f16<256>(base + PL + rofA[t]);
+      fb[t] = tr_frag_f16<256>(base + 2 * PL + rofB[t]);
+      fb[2 + t] = tr_frag_f16<256>(base + 3 * PL + rofB[t]);
     }
-  };
-  auto mfma12 = [&](const f16x8 (&fa)[4], const f16x8 (&fb)[4]) {
-#pragma unroll
-    for (int term = 0; term < 3; ++term)
-#pragma unroll
-      for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < 2; ++ni) {
-          if (term == 0)
-            acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[mi], fb[ni], acc[mi][ni], 0, 0, 0);
-          else
-            acx[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(term == 1 ? fa[mi] : fa[2 + mi],
-                                                                 term == 1 ? fb[2 + ni] : fb[ni], acx[mi][ni], 0, 0, 0);
-        }
   };
   // two register stages: slab t's MFMAs run while slab t + 1 (in registers since the previous step) goes to LDS and
   // the loads of slab t + 2 fly
@@ -344,11 +304,11 @@ __global__ __launch_bounds__(256, 2) void gemm_h3w_kernel(const f2g_gemm_desc d,
     // (the loads stay in front: left to itself the scheduler sinks them behind the LDS stores, to the barrier, and
     // the next step waits for them at once)
     __builtin_amdgcn_sched_barrier(0);
-    mfma12(fa, fb);
+    h3_mfma12(acc, acx, fa, fa + 2, fb, fb + 2);
     lstore(nxtoff, wa, wb);
     __builtin_amdgcn_sched_barrier(0);
     frags(curoff, 1, fa, fb);
-    mfma12(fa, fb);
+    h3_mfma12(acc, acx, fa, fa + 2, fb, fb + 2);
     __builtin_amdgcn_sched_barrier(0);
     __syncthreads();
     __builtin_amdgcn_sched_barrier(0);
@@ -360,8 +320,8 @@ __global__ __launch_bounds__(256, 2) void gemm_h3w_kernel(const f2g_gemm_desc d,
   }
   if (t < nt) step(t, 0, BUF, xa, xb, ya, yb);
 
-  // v = (acc0 + 2^-11 acc1) / s_a[m] / s_b[n], the reciprocals one after the other, then the generic epilogue
-  // (a row's scale is loaded once for both column sub-tiles)
+  // v = (acc0 + 2^-11 acc1) / s_a[m] / s_b[n] (gemm_f16_common.h: h3_value), then the generic epilogue (a row's
+  // scale is loaded once for both column sub-tiles)
   float sb[2];
 #pragma unroll
   for (int ni = 0; ni < 2; ++ni) {
@@ -375,8 +335,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h3w_kernel(const f2g_gemm_desc d,
       const int row = m0 + (wm * 2 + mi) * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
       const float sa = row < M ? d.A.rscale[row] : 0.f;
 #pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-        acc[mi][ni][e] = (acc[mi][ni][e] + acx[mi][ni][e] * 0x1p-11f) * sa * sb[ni];
+      for (int ni = 0; ni < 2; ++ni) acc[mi][ni][e] = h3_value(acc[mi][ni][e], acx[mi][ni][e], sa, sb[ni]);
     }
   gemm_epilogue<2, 2>(d.E, acc, M, N, m0, n0, wm, wn, li, h, blockIdx.z == 0);
 }
@@ -396,66 +355,81 @@ inline bool h3w_operand_ok(const f2g_operand& S) {
          ((long long)S.rows + 32) * S.seq_stride * 4 < 0x7ff00000ll;
 }
 
-int h3w_ok(const f2g_gemm_desc& d) {
-  // B a window operand: the tap-walking weight gradient (gemm_f16wt.hip) or nothing
-  if (d.precision == 4 && host_plain(d.A) && !host_plain(d.B)) return f2g_h3wt_ok(d);
-  if (d.precision != 4 || d.A.rows != d.B.rows || !h3w_operand_ok(d.A) || !h3w_operand_ok(d.B)) return 0;
-  const f2g_epilogue& E = d.E;
-  if (E.x3_out || E.colsum_part_ld > 0 || E.c_bf16 || (d.split_k > 1 && !E.atomic)) return 0;
-  // (the combinations f2g_gemm refuses for every form-2 kernel)
-  if (E.prelu_slope || E.mask_src || (E.aux && !E.alpha_n)) return 0;
-  if (d.A.split == 6 && d.B.split == 6) return d.A.rscale && d.B.rscale ? 1 : 0;
-  return d.A.split == 0 && d.B.split == 0 ? 2 : 0;
-}
+// The ONE route decision of precision 4: the kernel a descriptor belongs to -- gemm_h3_kernel, gemm_h3w_kernel,
+// gemm_h3p_kernel (gemm_f16p.hip), gemm_h3wt_kernel (gemm_f16wt.hip) --, what f2g_gemm_f16_ok answers for it (0: not for
+// that kernel; 1: runs as handed over, both operands the kernel's images with their reciprocal scales; 2: once both
+// fp32 operands are replaced by those images) and the taps of H3_TAP.  The shape of the operands picks the candidate,
+// the candidate's own conditions decide: a descriptor one kernel declines is never offered to another.
+enum h3_kernel { H3_NONE, H3_PLAIN, H3_WGRAD, H3_TAP, H3_TAPW };
+struct h3_route {
+  h3_kernel kernel = H3_NONE;
+  int status = 0, taps = 0;
+};
 
-// 0: not for these kernels; 1: as handed over (form 0: both operands f2g_split_f16x2 images -- over stride-1 windows
-// of a halo map: f2g_split_f16x2_seq images --, form 2: both f2g_split_f16x2_cols images, with their reciprocal
-// scales -- B as unbounded stride-1 five-tap windows of a halo map: the image of the whole map --); 2: once both fp32
-// operands are replaced by their images
-int h3_ok(const f2g_gemm_desc& d) {
-  if (!d.A.base || !d.B.base || !d.E.C) return 0;
-  if (d.form == 2) return h3w_ok(d);
-  // windows of a halo map, or f2g_split_f16x2_seq images: the tap-walking kernel (gemm_f16p.hip) or nothing
-  if (d.form == 0 && (!host_plain(d.A) || d.A.split == 7 || d.B.split == 7)) return f2g_h3p_ok(d, nullptr);
-  if (d.form != 0 || d.A.cols != d.B.cols) return 0;
-  if (!h3_operand_ok(d.A) || !h3_operand_ok(d.B)) return 0;
+int h3_plain_ok(const f2g_gemm_desc& d) {
+  if (d.A.cols != d.B.cols || !h3_operand_ok(d.A) || !h3_operand_ok(d.B)) return 0;
   const f2g_epilogue& E = d.E;
   if (d.split_k > 1 || E.x3_out || E.colsum_part_ld > 0 || E.c_bf16) return 0;
   // (the combinations f2g_gemm refuses for every kernel)
   if (E.prelu_slope && (E.atomic || E.accumulate || E.P0o > 0)) return 0;
   if (E.mask_src && (E.atomic || E.accumulate)) return 0;
   if (E.aux && !E.alpha_n) return 0;
-  if (d.A.split == 5 && d.B.split == 5) return d.A.rscale && d.B.rscale ? 1 : 0;
-  return d.A.split == 0 && d.B.split == 0 ? 2 : 0;
+  return f16_images_status(d.A, d.B, 5);
+}
+
+int h3w_ok(const f2g_gemm_desc& d) {
+  if (d.precision != 4 || d.A.rows != d.B.rows || !h3w_operand_ok(d.A) || !h3w_operand_ok(d.B)) return 0;
+  const f2g_epilogue& E = d.E;
+  if (E.x3_out || E.colsum_part_ld > 0 || E.c_bf16 || (d.split_k > 1 && !E.atomic)) return 0;
+  // (the combinations f2g_gemm refuses for every form-2 kernel)
+  if (E.prelu_slope || E.mask_src || (E.aux && !E.alpha_n)) return 0;
+  return f16_images_status(d.A, d.B, 6);
+}
+
+h3_route h3_route_of(const f2g_gemm_desc& d) {
+  h3_route r;
+  h3_kernel cand = H3_NONE;
+  if (!d.A.base || !d.B.base || !d.E.C) return r;
+  if (d.form == 2) {
+    // B a window operand: the tap-walking weight gradient or nothing
+    cand = d.precision == 4 && host_plain(d.A) && !host_plain(d.B) ? H3_TAPW : H3_WGRAD;
+    r.status = cand == H3_TAPW ? f2g_h3wt_ok(d) : h3w_ok(d);
+  } else if (d.form == 0) {
+    // windows of a halo map, or f2g_split_f16x2_seq images: the tap-walking kernel or nothing
+    cand = !host_plain(d.A) || d.A.split == 7 || d.B.split == 7 ? H3_TAP : H3_PLAIN;
+    r.status = cand == H3_TAP ? f2g_h3p_ok(d, &r.taps) : h3_plain_ok(d);
+  }
+  if (r.status) r.kernel = cand;
+  return r;
 }
 
 }  // namespace
 
-extern "C" int f2g_gemm_f16_ok(const f2g_gemm_desc* dp) { return dp ? h3_ok(*dp) : 0; }
+extern "C" int f2g_gemm_f16_ok(const f2g_gemm_desc* dp) { return dp ? h3_route_of(*dp).status : 0; }
 
 int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st) {
-  if (h3_ok(d) != 1) {
+  const h3_route r = h3_route_of(d);
+  if (r.status != 1) {
     f2g_set_error("f2g_gemm precision 4: form 0 over f2g_split_f16x2 images, or form 2 over f2g_split_f16x2_cols "
                   "images, of two plain matrices, or form 0 over f2g_split_f16x2_seq images of stride-1 windows of 5 or "
                   "2 positions, or form 2 + atomic over f2g_split_f16x2_cols images of a plain matrix and of the map "
                   "under unbounded stride-1 windows of 5 positions (f2g_gemm_f16_ok(d) != 1 for this descriptor)");
     return F2G_EINVAL;
   }
-  if (d.form == 0 && d.A.split == 7) {
-    int taps = 0;
-    (void)f2g_h3p_ok(d, &taps);
-    return f2g_launch_h3p(d, taps, st);
-  }
-  if (d.form == 2 && !host_plain(d.B)) return f2g_launch_h3wt(d, st);
-  if (d.form == 2) {
-    const int M = d.A.cols, N = d.B.cols, K = d.A.rows, split = d.split_k > 1 ? d.split_k : 1;
-    const int kchunk = ((K + split - 1) / split + BK - 1) / BK * BK;
-    constexpr int smem = 2 * 4 * 32 * 256;      // [buf][A hi | A lo | B hi | B lo] planes of 32 rows x 128 halves
-    dyn_lds_once<gemm_h3w_kernel>(smem);
-    f2g_note_kernel("h3w", split, 6);
-    hipLaunchKernelGGL(gemm_h3w_kernel, dim3((M + 127) / 128, (N + 127) / 128, (K + kchunk - 1) / kchunk), dim3(256),
-                       smem, st, d, M, N, K, kchunk);
-    return f2g_check_launch();
+  switch (r.kernel) {
+    case H3_TAP: return f2g_launch_h3p(d, r.taps, st);
+    case H3_TAPW: return f2g_launch_h3wt(d, st);
+    case H3_WGRAD: {
+      const int M = d.A.cols, N = d.B.cols, K = d.A.rows, split = d.split_k > 1 ? d.split_k : 1;
+      const int kchunk = ((K + split - 1) / split + BK - 1) / BK * BK;
+      constexpr int smem = 2 * 4 * 32 * 256;      // [buf][A hi | A lo | B hi | B lo] planes of 32 rows x 128 halves
+      dyn_lds_once<gemm_h3w_kernel>(smem);
+      f2g_note_kernel("h3w", split, 6);
+      hipLaunchKernelGGL(gemm_h3w_kernel, dim3((M + 127) / 128, (N + 127) / 128, (K + kchunk - 1) / kchunk),
+                         dim3(256), smem, st, d, M, N, K, kchunk);
+      return f2g_check_launch();
+    }
+    default: break;      // H3_PLAIN (H3_NONE has status 0)
   }
   const int M = d.A.rows, N = d.B.rows, K = d.A.cols;
   constexpr int smem = 4 * 128 * LDR * 4;

@@ -17,13 +17,11 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "gemm_common.h"
+#include "gemm_f16_common.h"
 #include "split_f16.h"
 #include "x6_epilogue.h"
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 // ---- the image ----------------------------------------------------------------------------------------------------
 // One block per run (a run is far longer than a register file -- 148 x 1024 floats for the fifth layer at period 2
@@ -42,19 +40,15 @@ __global__ __launch_bounds__(SEQ_THREADS) void split_f16x2_seq_kernel(uint4* dst
     m = f2g_f16_amax4(s4[2 * c], m);
     m = f2g_f16_amax4(s4[2 * c + 1], m);
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const unsigned t = (unsigned)__shfl_xor((int)m, o);
-    m = m > t ? m : t;
-  }
+  m = f2g_wave_max(m);
   if (lane == 0) part[tid >> 6] = m;
   __syncthreads();
   m = part[0];
 #pragma unroll
   for (int w = 1; w < SEQ_THREADS / 64; ++w) m = m > part[w] ? m : part[w];
-  const int sexp = f2g_f16_scale_exp(m);
-  const float s = __uint_as_float((unsigned)(127 + sexp) << 23);
-  if (tid == 0) rscale[blockIdx.x] = __uint_as_float((unsigned)(127 - sexp) << 23);
+  float s, rs;
+  f2g_f16_scales(m, s, rs);
+  if (tid == 0) rscale[blockIdx.x] = rs;
   uint4* d4 = dst + (long long)blockIdx.x * (ld >> 2);
   for (int c = tid; c < n8; c += SEQ_THREADS) {
     const uint4 a = f2g_f16_split4(s4[2 * c], s), b = f2g_f16_split4(s4[2 * c + 1], s);     // (h01, h23, l01, l23)
@@ -96,12 +90,7 @@ __global__ __launch_bounds__(512, 1) void gemm_h3p_kernel(const f2g_gemm_desc d,
   tile_of_block(256, 128, m0, n0);
   const int mg = m0 + 128 * grp;                  // first row of this group's half of the tile
   f32x16 acc[2][2], acx[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) acc[i][j][e] = acx[i][j][e] = 0.f;
+  h3_zero<4>(acc[0], acx[0]);
   auto posrow = [&](int r) {
     const int sq = r / R.P0;
     return sq * R.HpIn + (r - sq * R.P0) + R.offpos;
@@ -202,27 +191,15 @@ __global__ __launch_bounds__(512, 1) void gemm_h3p_kernel(const f2g_gemm_desc d,
       }
       __builtin_amdgcn_s_setprio(1);
 #pragma unroll
-      for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-        for (int term = 0; term < 3; ++term)
-#pragma unroll
-          for (int mi = 0; mi < 2; ++mi)
-#pragma unroll
-            for (int ni = 0; ni < 2; ++ni) {
-              if (term == 0)
-                acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ks][0][mi], fb[ks][0][ni], acc[mi][ni], 0, 0, 0);
-              else
-                acx[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ks][term == 1 ? 0 : 1][mi],
-                                                                     fb[ks][term == 1 ? 1 : 0][ni], acx[mi][ni], 0, 0, 0);
-            }
+      for (int ks = 0; ks < 2; ++ks) h3_mfma12(acc, acx, fa[ks][0], fa[ks][1], fb[ks][0], fb[ks][1]);
       __builtin_amdgcn_s_setprio(0);
       // (group 1's last MFMA slot needs no barrier behind it: group 0 is in its epilogue by then, and that
       // slot touches no LDS -- both groups pass 1 + 2 * nsteps barriers)
       if (!(grp == 1 && step == nsteps - 1)) lds_barrier();
     }
   }
-  // v = (acc0 + 2^-11 acc1) / s_a[sequence of the row] / s_b[col], the reciprocals one after the other (their product
-  // may leave the float range).  The table lies behind everything the epilogue's patches overlay.
+  // v = (acc0 + 2^-11 acc1) / s_a[sequence of the row] / s_b[col] (gemm_f16_common.h: h3_value).  The table lies behind
+  // everything the epilogue's patches overlay.
   float sb[2];
 #pragma unroll
   for (int ni = 0; ni < 2; ++ni) {
@@ -235,8 +212,7 @@ __global__ __launch_bounds__(512, 1) void gemm_h3p_kernel(const f2g_gemm_desc d,
     for (int e = 0; e < 16; ++e) {
       const float sa = rstab[grp * 128 + wm * 64 + mi * 32 + (e & 3) + 8 * (e >> 2) + 4 * h];
 #pragma unroll
-      for (int ni = 0; ni < 2; ++ni)
-        acc[mi][ni][e] = (acc[mi][ni][e] + acx[mi][ni][e] * 0x1p-11f) * sa * sb[ni];
+      for (int ni = 0; ni < 2; ++ni) acc[mi][ni][e] = h3_value(acc[mi][ni][e], acx[mi][ni][e], sa, sb[ni]);
     }
   // every fragment read of the main loop is complete (the last ones were group 1's, before the barrier group 0
   // has just passed): the waves turn their tiles through private patches at the bottom of the LDS
@@ -265,8 +241,7 @@ int f2g_h3p_ok(const f2g_gemm_desc& d, int* taps_out) {
   if (E.prelu_slope && (E.accumulate || E.P0o > 0)) return 0;
   if (E.mask_src && E.accumulate) return 0;
   if (taps_out) *taps_out = taps;
-  if (A.split == 7 && B.split == 7) return A.rscale && B.rscale ? 1 : 0;
-  return A.split == 0 && B.split == 0 ? 2 : 0;
+  return f16_images_status(A, B, 7);
 }
 
 int f2g_launch_h3p(const f2g_gemm_desc& d, int taps, hipStream_t st) {

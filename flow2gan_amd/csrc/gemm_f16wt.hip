@@ -7,21 +7,9 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include "gemm_common.h"
+#include "gemm_f16_common.h"
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-
-// K-major fragment read (gemm_common.h: tr_frag) out of planes whose rows lie PITCH bytes apart
-template <int PITCH>
-__device__ __forceinline__ f16x8 tr_frag_f16(const unsigned char* p) {
-  typedef s16x4 __attribute__((address_space(3))) * lds_p;
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p + 4 * PITCH));
-  const s16x8 v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
-  return __builtin_bit_cast(f16x8, v);
-}
 
 // gemm_leanw6t_kernel's structure: a block owns a (co tile x ci tile x ALL taps) output, a slab stages 32 gradient
 // rows and the 32 + TAPS - 1 map rows they touch once (double-buffered, one barrier per slab), the taps walk by
@@ -98,10 +86,7 @@ __global__ __launch_bounds__(512, 1) void gemm_h3wt_kernel(const f2g_gemm_desc d
 #pragma unroll
   for (int t = 0; t < TAPS; ++t) rofB[t] = XOFF + (rrow + t) * XP + (((wq ^ (((rrow + t) >> 1) & 1))) << 6) + within;
   f32x16 acc[TAPS], acx[TAPS];
-#pragma unroll
-  for (int t = 0; t < TAPS; ++t)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[t][e] = acx[t][e] = 0.f;
+  h3_zero<TAPS>(acc, acx);
   u32x4 xg[2], xx[NXQ];
   auto gload = [&](int s) {       // slab s of this block's chunk (rows kbeg + 32 s ..); past the end: zeros
     const int kr = kbeg + 32 * s;
@@ -150,15 +135,13 @@ __global__ __launch_bounds__(512, 1) void gemm_h3wt_kernel(const f2g_gemm_desc d
       for (int t = 0; t < TAPS; ++t) {
         const f16x8 bh = tr_frag_f16<XP>(cur + ks * 16 * XP + rofB[t]);
         const f16x8 bl = tr_frag_f16<XP>(cur + ks * 16 * XP + XPL + rofB[t]);
-        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[t], 0, 0, 0);
-        acx[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acx[t], 0, 0, 0);
-        acx[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acx[t], 0, 0, 0);
+        h3_product(acc[t], acx[t], ah, al, bh, bl);
       }
     }
     lds_barrier();
   }
-  // gw[co][t * Cin + ci] += (acc + 2^-11 acx) / s_g[co] / s_x[ci] (the reciprocals one after the other: their
-  // product may leave the float range): rows m0 + wm * 32 + (MFMA row), columns t * Cin + c0 + wq * 32 + li
+  // gw[co][t * Cin + ci] += (acc + 2^-11 acx) / s_g[co] / s_x[ci] (gemm_f16_common.h: h3_value): rows m0 + wm * 32 +
+  // (MFMA row), columns t * Cin + c0 + wq * 32 + li
   float* C0 = d.E.C;
   const int ci = c0 + wq * 32 + li;
   const float sb = d.B.rscale[ci];
@@ -168,7 +151,7 @@ __global__ __launch_bounds__(512, 1) void gemm_h3wt_kernel(const f2g_gemm_desc d
     const float sa = d.A.rscale[row];
     float* crow = C0 + (long long)row * d.E.ldc + ci;
 #pragma unroll
-    for (int t = 0; t < TAPS; ++t) atomicAdd(crow + t * Cin, (acc[t][e] + acx[t][e] * 0x1p-11f) * sa * sb);
+    for (int t = 0; t < TAPS; ++t) atomicAdd(crow + t * Cin, h3_value(acc[t][e], acx[t][e], sa, sb));
   }
 }
 
@@ -199,8 +182,7 @@ int f2g_h3wt_ok(const f2g_gemm_desc& d) {
   if (B.seq_stride != (long long)B.P0 * B.unit) return 0;     // (one flat row index for the whole buffer)
   const long long xrows = (long long)(B.rows / B.P0) * B.P0;
   if (xrows * B.unit * 4 >= 0x7ff00000ll || (long long)A.rows * A.seq_stride * 4 >= 0x7ff00000ll) return 0;
-  if (A.split == 6 && B.split == 6) return A.rscale && B.rscale ? 1 : 0;
-  return A.split == 0 && B.split == 0 ? 2 : 0;
+  return f16_images_status(A, B, 6);
 }
 
 int f2g_launch_h3wt(const f2g_gemm_desc& d, hipStream_t st) {

@@ -1,6 +1,7 @@
-// Row routine of f2g_split_f16x2 (gemm_f16.hip) and of its f2g_multi entry (multi.hip: weight images rebuilt in
-// one batched launch): the two-piece fp16 image of fp32 rows and their reciprocal scales.  f2g_split_f16x2_cols
-// (gemm_f16.hip: the K-major operands of a weight gradient, one scale per COLUMN) shares the arithmetic below.
+// The image side of fp16x3 (gemm_f16_common.h: the GEMM side).  Row routine of f2g_split_f16x2 (gemm_f16.hip) and of
+// its f2g_multi entry (multi.hip: weight images rebuilt in one batched launch): the two-piece fp16 image of fp32 rows
+// and their reciprocal scales.  f2g_split_f16x2_cols (gemm_f16.hip: K-major operands, one scale per COLUMN) and
+// f2g_split_f16x2_seq (gemm_f16p.hip: one scale per sequence of a halo map) share the arithmetic below.
 #pragma once
 #include "common.h"
 
@@ -49,11 +50,23 @@ __device__ __forceinline__ uint4 f2g_f16_split4(const float4& v, const float4& s
   return make_uint4(h01, h23, l01, l23);
 }
 
-// Exponent of the scale s = 2^sexp of a row (or column) whose largest sign-less bit pattern is m
-__device__ __forceinline__ int f2g_f16_scale_exp(unsigned m) {
+// The scale s = 2^sexp of a row (column, sequence) whose largest sign-less bit pattern is m, and its reciprocal rs
+__device__ __forceinline__ void f2g_f16_scales(unsigned m, float& s, float& rs) {
   int sexp = 14 - ((int)(m >> 23) - 127);          // (a subnormal amax: beyond the clamp either way)
   sexp = sexp > 126 ? 126 : (sexp < -126 ? -126 : sexp);
-  return (m == 0u || m >= 0x7f800000u) ? 0 : sexp;
+  sexp = (m == 0u || m >= 0x7f800000u) ? 0 : sexp;
+  s = __uint_as_float((unsigned)(127 + sexp) << 23);
+  rs = __uint_as_float((unsigned)(127 - sexp) << 23);
+}
+
+// Largest m of a wave's 64 lanes, in every lane (a fixed butterfly, no atomics)
+__device__ __forceinline__ unsigned f2g_wave_max(unsigned m) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned t = (unsigned)__shfl_xor((int)m, o);
+    m = m > t ? m : t;
+  }
+  return m;
 }
 
 // One wave per row: its largest magnitude is the integer maximum of the sign-less bit patterns (the same order as
@@ -82,14 +95,9 @@ __device__ __forceinline__ void f2g_split_f16x2_rows(float* dst, float* __restri
     } else {
       for (int c = lane; c < K4; c += 64) m = f2g_f16_amax4(s4[c], m);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const unsigned t = (unsigned)__shfl_xor((int)m, o);
-      m = m > t ? m : t;
-    }
-    const int sexp = f2g_f16_scale_exp(m);
-    const float s = __uint_as_float((unsigned)(127 + sexp) << 23);
-    if (lane == 0) rscale[r] = __uint_as_float((unsigned)(127 - sexp) << 23);
+    float s, rs;
+    f2g_f16_scales(f2g_wave_max(m), s, rs);
+    if (lane == 0) rscale[r] = rs;
     uint4* d4 = reinterpret_cast<uint4*>(dst + r * ld);
     if constexpr (KEEP) {
 #pragma unroll

@@ -463,7 +463,6 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
     padded to whole K slabs): what bench.py's FLOP count uses; the launch itself ignores them.
     split_k: 0 = let the library decide (forms 0/1: split-K onto a zeroed output when the tile
     grid would leave most of the last wave of CUs idle), 1 = off, > 1 = as given."""
-    global FP16X3_LAUNCHES, FP16X3_WGRAD_LAUNCHES, FP16X3_TAP_LAUNCHES, FP16X3_TAPW_LAUNCHES
     if form == 1:
         # data gradient C[r,n] = sum_k A[r,k] W[k,n] as a forward GEMM against the cached transpose
         # W^T [n][k]: same products in the same order, and the lean forward kernel applies
@@ -517,63 +516,7 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
                 split_k = split_for(A.rows, tiles, True)
     d.split_k = split_k
     d.precision = GEMM_PRECISION
-    f16 = False
-    if GEMM_PRECISION == 3 and FP16X3 and form == 0 and A.split == 0 and Bm.split == 0 and A.P0 == 1 and A.P1 == 1 \
-            and A.cols >= FP16X3_MIN_K and Bm.rows >= FP16X3_MIN_N and split_k <= 1 and out.dtype == torch.float32:
-        # fp16x3: two plain matrices (a data gradient arrives here as form 0 over the cached transpose) as
-        # f2g_split_f16x2 images -- the weight's from the derived-weight cache, the activation's made here.  The
-        # library is asked first, with the descriptor as it will be launched; what it declines goes the bf16x6 way
-        d.precision = 4
-        if L.lib.f2g_gemm_f16_ok(C.byref(d)) == 2:
-            d.A, d.B = _f16_operand(A), _f16_operand(Bm)
-            f16 = True
-            FP16X3_LAUNCHES += 1
-    if GEMM_PRECISION == 3 and FP16X3 and form == 2 and atomic and A.split == 0 and Bm.split == 0 \
-            and A.lrelu_src is None and A.rows >= FP16X3_WGRAD_MIN_ROWS and out.dtype == torch.float32 \
-            and Bm.P0 == 1 and Bm.P1 == 1:
-        # fp16x3 weight gradient: both operands are PLAIN activation matrices, K-major -- their f2g_split_f16x2_cols
-        # images (one scale per column) are made here, per call; what the library declines goes the bf16x6 way
-        d.precision = 4
-        if L.lib.f2g_gemm_f16_ok(C.byref(d)) == 2:
-            d.A, d.B = _f16_cols_operand(A), _f16_cols_operand(Bm)
-            f16 = True
-            FP16X3_WGRAD_LAUNCHES += 1
-    if GEMM_PRECISION == 3 and FP16X3 and form == 2 and atomic and A.split == 0 and Bm.split == 0 \
-            and A.lrelu_src is None and A.P0 == 1 and A.P1 == 1 and Bm.P1 == 1 and Bm.P0 > 1 and Bm.step0 == 1 \
-            and Bm.unbounded and Bm.cols == 5 * Bm.unit and A.rows >= FP16X3_TAPW_MIN_ROWS \
-            and out.dtype == torch.float32 and _f16_cols_window_ok(Bm):
-        # fp16x3 tap-walking weight gradient (the MPD's stride-1 1024-channel layer): the gradient as a plain K-major
-        # matrix, the map under unbounded stride-1 windows of five positions.  The taps shift ROWS of the map, so one
-        # scale per COLUMN of the whole map serves every tap: both f2g_split_f16x2_cols images are made here, per
-        # call (the gradient's into a buffer of its own -- the data gradient reads the fp32 values again); what the
-        # library declines goes the bf16x6 way
-        d.precision = 4
-        if L.lib.f2g_gemm_f16_ok(C.byref(d)) == 2:
-            d.A, d.B = _f16_cols_operand(A), _f16_cols_window_operand(Bm)
-            f16 = True
-            FP16X3_TAPW_LAUNCHES += 1
-    if GEMM_PRECISION == 3 and FP16X3 and form == 0 and A.split == 0 and Bm.split == 0 and A.P1 == 1 and A.P0 > 1 \
-            and A.step0 == 1 and A.cols in (5 * A.unit, 2 * A.unit) and A.rows >= FP16X3_TAP_MIN_ROWS \
-            and A.cols >= X6_MIN_K \
-            and not atomic and split_k <= 1 and out.dtype == torch.float32 and _f16_seq_window_ok(A):
-        # fp16x3 over stride-1 windows of 5 or 2 positions of a contiguous halo map (the MPD's 1024-channel layer, its
-        # data gradient, the residue data gradients of the stride-3 layers): f2g_split_f16x2_seq images, one scale per
-        # sequence -- the map's made here, per call, the weight's from the derived-weight cache.  Reductions from
-        # X6_MIN_K on: the launches the bf16x6 mode gives to its image kernels (a shorter one reads the fp32 map as
-        # it is there, without any image pass).  The kernel has the
-        # bf16x6 kernels' wide epilogue, so the output's three-piece image is written as there (its consumers stay
-        # the bf16x6 kernels).  What the library declines goes the bf16x6 way
-        d.precision = 4
-        how = _ask_with_x3_out(d, out, out_offset, x3_out, prelu_out,
-                               lambda: L.lib.f2g_gemm_f16_ok(C.byref(d)) == 2)
-        if how:
-            d.A, d.B = _f16_seq_operand(A), _f16_seq_operand(Bm)
-            f16 = True
-            FP16X3_TAP_LAUNCHES += 1
-            if x3_out and d.E.x3_out:
-                out._f2g_x3 = out._f2g_x3_buf
-        else:
-            d.E.x3_out = None
+    f16 = _fp16x3_gemm(d, A, Bm, out, form, atomic, split_k, out_offset, x3_out, prelu_out)
     if GEMM_PRECISION == 3 and f16:
         if x3_out and not d.E.x3_out:
             out._f2g_x3_bad = True     # (no image from this kernel: the next consumer builds its own)
@@ -962,6 +905,18 @@ def _split_operand(o: Operand) -> Operand:
     return n
 
 
+def _image_operand(o: Operand, buf, scale_offset: int, split: int) -> Operand:
+    """Copy of `o` over its fp16 image at the start of `buf` (same addressing: all other fields stay), the reciprocal
+    scales `scale_offset` floats into the same allocation; split: 5 one scale per row, 6 per column, 7 per sequence."""
+    n = Operand()
+    C.memmove(C.byref(n), C.byref(o), C.sizeof(Operand))
+    n.base = ptr(buf)
+    n.rscale = ptr(buf) + 4 * scale_offset
+    n.split = split
+    n._keep = (buf,) + tuple(o._keep)
+    return n
+
+
 def _f16_operand(o: Operand) -> Operand:
     """Copy of a plain fp32 matrix operand over its two-piece fp16 image (f2g_split_f16x2: same addressing, the
     reciprocal row scales behind the image in the same allocation): cached for weights and cached re-layouts of
@@ -980,13 +935,7 @@ def _f16_operand(o: Operand) -> Operand:
             call("f2g_split_f16x2", ptr(buf), ptr(buf) + 4 * soff, ptr(tt) + off, ld, rows, K)
         return buf
     buf = derived(t, ("f16x2", off, rows, K, ld), build) if _is_const(t) else build(t)
-    n = Operand()
-    C.memmove(C.byref(n), C.byref(o), C.sizeof(Operand))
-    n.base = ptr(buf)
-    n.rscale = ptr(buf) + 4 * soff
-    n.split = 5
-    n._keep = (buf,) + tuple(o._keep)
-    return n
+    return _image_operand(o, buf, soff, 5)
 
 
 def split_f16_seq(t, nseq: int, seq_floats: int, ld: Optional[int] = None, offset: int = 0):
@@ -1026,13 +975,7 @@ def _f16_seq_operand(o: Operand) -> Operand:
     else:
         nseq, ld = o.rows // o.P0, o.seq_stride
         buf = split_f16_seq(t, nseq, ld, ld, off)
-    n = Operand()
-    C.memmove(C.byref(n), C.byref(o), C.sizeof(Operand))
-    n.base = ptr(buf)
-    n.rscale = ptr(buf) + 4 * nseq * ld
-    n.split = 7
-    n._keep = (buf,) + tuple(o._keep)
-    return n
+    return _image_operand(o, buf, nseq * ld, 7)
 
 
 def _f16_cols_operand(o: Operand) -> Operand:
@@ -1044,13 +987,7 @@ def _f16_cols_operand(o: Operand) -> Operand:
     buf = torch.empty(rows * ld + 2 * cols, device=o._keep[0].device, dtype=torch.float32)
     call("f2g_split_f16x2_cols", ptr(buf), ptr(buf) + 4 * rows * ld, ptr(buf) + 4 * (rows * ld + cols), o.base, ld,
          rows, cols)
-    n = Operand()
-    C.memmove(C.byref(n), C.byref(o), C.sizeof(Operand))
-    n.base = ptr(buf)
-    n.rscale = ptr(buf) + 4 * rows * ld
-    n.split = 6
-    n._keep = (buf,) + tuple(o._keep)
-    return n
+    return _image_operand(o, buf, rows * ld, 6)
 
 
 def _f16_cols_window_ok(o: Operand) -> bool:
@@ -1075,13 +1012,65 @@ def _f16_cols_window_operand(o: Operand) -> Operand:
     buf = torch.empty(xrows * Cin + 2 * Cin, device=o._keep[0].device, dtype=torch.float32)
     call("f2g_split_f16x2_cols", ptr(buf), ptr(buf) + 4 * xrows * Cin, ptr(buf) + 4 * (xrows * Cin + Cin), o.base, Cin,
          xrows, Cin)
-    n = Operand()
-    C.memmove(C.byref(n), C.byref(o), C.sizeof(Operand))
-    n.base = ptr(buf)
-    n.rscale = ptr(buf) + 4 * xrows * Cin
-    n.split = 6
-    n._keep = (buf,) + tuple(o._keep)
-    return n
+    return _image_operand(o, buf, xrows * Cin, 6)
+
+
+def _fp16x3_gemm(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offset: int, x3_out: bool,
+                 prelu_out) -> bool:
+    """The fp16x3 routes of gemm(), tried in order: each states what the Python side requires of the call, then asks
+    the library about `d` as it will be launched (d.precision = 4; f2g_gemm_f16_ok decides which kernel that is).
+    True: one took the launch -- d.A / d.B are its images, its counter went up.  False: the launch goes the bf16x6
+    way (d.precision may be left at 4: gemm() sets it)."""
+    global FP16X3_LAUNCHES, FP16X3_WGRAD_LAUNCHES, FP16X3_TAP_LAUNCHES, FP16X3_TAPW_LAUNCHES
+    if not (GEMM_PRECISION == 3 and FP16X3) or A.split != 0 or Bm.split != 0 or out.dtype != torch.float32:
+        return False
+
+    def takes():
+        d.precision = 4
+        return L.lib.f2g_gemm_f16_ok(C.byref(d)) == 2
+    a_plain, b_plain = A.P0 == 1 and A.P1 == 1, Bm.P0 == 1 and Bm.P1 == 1
+    wgrad = form == 2 and atomic and A.lrelu_src is None
+    if form == 0 and a_plain and A.cols >= FP16X3_MIN_K and Bm.rows >= FP16X3_MIN_N and split_k <= 1 and takes():
+        # fp16x3: two plain matrices (a data gradient arrives here as form 0 over the cached transpose) as
+        # f2g_split_f16x2 images -- the weight's from the derived-weight cache, the activation's made here.  The
+        # library is asked first, with the descriptor as it will be launched; what it declines goes the bf16x6 way
+        d.A, d.B = _f16_operand(A), _f16_operand(Bm)
+        FP16X3_LAUNCHES += 1
+        return True
+    if wgrad and b_plain and A.rows >= FP16X3_WGRAD_MIN_ROWS and takes():
+        # fp16x3 weight gradient: both operands are PLAIN activation matrices, K-major -- their f2g_split_f16x2_cols
+        # images (one scale per column) are made here, per call; what the library declines goes the bf16x6 way
+        d.A, d.B = _f16_cols_operand(A), _f16_cols_operand(Bm)
+        FP16X3_WGRAD_LAUNCHES += 1
+        return True
+    if wgrad and a_plain and Bm.P1 == 1 and Bm.P0 > 1 and Bm.step0 == 1 and Bm.unbounded \
+            and Bm.cols == 5 * Bm.unit and A.rows >= FP16X3_TAPW_MIN_ROWS and _f16_cols_window_ok(Bm) and takes():
+        # fp16x3 tap-walking weight gradient (the MPD's stride-1 1024-channel layer): the gradient as a plain K-major
+        # matrix, the map under unbounded stride-1 windows of five positions.  The taps shift ROWS of the map, so one
+        # scale per COLUMN of the whole map serves every tap: both f2g_split_f16x2_cols images are made here, per
+        # call (the gradient's into a buffer of its own -- the data gradient reads the fp32 values again); what the
+        # library declines goes the bf16x6 way
+        d.A, d.B = _f16_cols_operand(A), _f16_cols_window_operand(Bm)
+        FP16X3_TAPW_LAUNCHES += 1
+        return True
+    if form == 0 and A.P1 == 1 and A.P0 > 1 and A.step0 == 1 and A.cols in (5 * A.unit, 2 * A.unit) \
+            and A.rows >= FP16X3_TAP_MIN_ROWS and A.cols >= X6_MIN_K and not atomic and split_k <= 1 \
+            and _f16_seq_window_ok(A):
+        # fp16x3 over stride-1 windows of 5 or 2 positions of a contiguous halo map (the MPD's 1024-channel layer, its
+        # data gradient, the residue data gradients of the stride-3 layers): f2g_split_f16x2_seq images, one scale per
+        # sequence -- the map's made here, per call, the weight's from the derived-weight cache.  Reductions from
+        # X6_MIN_K on: the launches the bf16x6 mode gives to its image kernels (a shorter one reads the fp32 map as
+        # it is there, without any image pass).  The kernel has the bf16x6 kernels' wide epilogue, so the output's
+        # three-piece image is written as there (its consumers stay the bf16x6 kernels).  What the library declines
+        # goes the bf16x6 way
+        if _ask_with_x3_out(d, out, out_offset, x3_out, prelu_out, takes):
+            d.A, d.B = _f16_seq_operand(A), _f16_seq_operand(Bm)
+            FP16X3_TAP_LAUNCHES += 1
+            if x3_out and d.E.x3_out:
+                out._f2g_x3 = out._f2g_x3_buf
+            return True
+        d.E.x3_out = None
+    return False
 
 
 CONV32_X6 = opt("conv32_x6", True)    # bf16x6 mode: fp32-class direct MRD convs (bench.py reads it)

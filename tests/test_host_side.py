@@ -525,6 +525,10 @@ def test_makefile_builds_and_digests_every_source():
     builds and runs, only counters recorded with one build could then be attributed to another"""
     csrc = os.path.join(ROOT, "flow2gan_amd", "csrc")
     mk = open(os.path.join(csrc, "Makefile")).read()
+    # (the header list is ONE variable, written out once: the three places below name it, so read them expanded)
+    hdrs = re.search(r"^HDRS\s*=\s*(.+)$", mk, re.M).group(1)
+    assert mk.count("$(HDRS)") == 3, mk.count("$(HDRS)")
+    mk = mk.replace("$(HDRS)", hdrs)
     srcs = re.search(r"^SRCS\s*=\s*(.+)$", mk, re.M).group(1).split()
     hips = sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
     headers = sorted(f for f in os.listdir(csrc) if f.endswith(".h") and f != "version_gen.h")
