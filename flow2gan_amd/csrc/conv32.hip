@@ -11,16 +11,12 @@
 // patch at tap-shifted addresses: global traffic per output tile drops from 27 x 16 KB to 50 KB.
 #include <stdlib.h>
 
-#include "common.h"
+#include "conv32_common.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
 constexpr int TH = 8, TW = 16;          // output tile (rows x columns) = 128 pixels = 4 x 32 (x 2 tap halves = 8 waves)
-constexpr int C = 32;                   // channels in = out
 constexpr int PITCH = 36;               // floats per staged pixel (conflict-free ds_read_b128)
-constexpr int KH = 3, KW = 9;
 constexpr int IW = TW + (KW - 1) / 2;   // staged columns per parity: 16 + 4 = 20
 constexpr int IH = TH + KH - 1;         // staged rows: 10
 constexpr int SUB = IH * IW * PITCH + 16;   // floats of one parity sub-tile (+64 B: the 8-byte stores of
@@ -29,17 +25,12 @@ constexpr int SUB = IH * IW * PITCH + 16;   // floats of one parity sub-tile (+6
 constexpr int WB = C * PITCH;           // floats of one weight tile
 constexpr int TG = 2;                   // taps per barrier (weights double-buffered per group)
 
-__device__ __attribute__((aligned(16))) float c32_zero[4] = {0.f, 0.f, 0.f, 0.f};
-
-// ---- split-bf16 variants (P3; f2g_conv32_desc.precision = 1) -----------------------------------
-// Same tiling; every product is lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16 (6 MFMAs of 32
+// ---- split-bf16 kernels (f2g_conv32_desc.precision = 1) ------------------------------------------
+// Every product is lo*hi + hi*lo + hi*hi on v_mfma_f32_32x32x16_bf16 (6 MFMAs of 32
 // cycles per tap and wave instead of 16 of 64).  A staged pixel keeps its 144-byte pitch as
 // [32 hi | 32 lo | pad]: the patch is split ONCE per block while it is staged (each element then
 // feeds 27 taps x 32 outputs), the weight tiles arrive pre-split (f2g_split_bf16 image of the same
 // packed matrix, same addressing) and go to LDS as two 8-byte halves.
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-
 __device__ __forceinline__ unsigned pack_bf16(float a, float b, float& ra, float& rb) {
   const __bf16 ha = (__bf16)a, hb = (__bf16)b;
   ra = a - (float)ha;
@@ -82,7 +73,8 @@ __device__ __forceinline__ void tap_mfma3(const float* Ab, const float* Bb, int 
   acc2 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[1], bh[1], acc2, 0, 0, 0);
 }
 
-template <bool P3>
+constexpr size_t FWD_SMEM = (size_t)(2 * SUB + 2 * TG * WB) * sizeof(float);
+
 __global__ __launch_bounds__(512, 2) void conv32_s2_fwd_kernel(const f2g_conv32_desc d) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* At = sm;                 // [2 parities][IH][IW][PITCH]
@@ -105,16 +97,12 @@ __global__ __launch_bounds__(512, 2) void conv32_s2_fwd_kernel(const f2g_conv32_
     const bool ok = h >= 0 && h < d.H && x >= 0 && x < d.Win;
     const float* p = ok ? xs + (long long)h * d.x_line + (long long)x * C + c4 * 4 : c32_zero;
     const float4 v = *reinterpret_cast<const float4*>(p);
-    if constexpr (P3) store_split4(At + (xr & 1) * SUB + (r * IW + (xr >> 1)) * PITCH + c4 * 2, v);
-    else *reinterpret_cast<float4*>(At + (xr & 1) * SUB + (r * IW + (xr >> 1)) * PITCH + c4 * 4) = v;
+    store_split4(At + (xr & 1) * SUB + (r * IW + (xr >> 1)) * PITCH + c4 * 2, v);
   }
   // weights: thread = (tap of the group, co, 4 input channels); group 0 -> buffer 0
   const int wu = tid >> 8, wco = (tid & 255) >> 3, wc4 = tid & 7;
   const float* wrow = d.w + (long long)wco * (KH * KW * C) + wc4 * 4;
-  if constexpr (P3) store_presplit4(Bt + wu * WB + wco * PITCH + wc4 * 2,
-                                    *reinterpret_cast<const float4*>(wrow + wu * C));
-  else *reinterpret_cast<float4*>(Bt + wu * WB + wco * PITCH + wc4 * 4) =
-      *reinterpret_cast<const float4*>(wrow + wu * C);
+  store_presplit4(Bt + wu * WB + wco * PITCH + wc4 * 2, *reinterpret_cast<const float4*>(wrow + wu * C));
   __syncthreads();
 
   f32x16 acc, acc2;
@@ -124,7 +112,6 @@ __global__ __launch_bounds__(512, 2) void conv32_s2_fwd_kernel(const f2g_conv32_
   const int pg = wave & 3, myu = wave >> 2;
   const int p = pg * 32 + li;             // this lane's output pixel inside the tile
   const int ph = p >> 4, pw = p & 15;
-  const int kk0 = hh * 16;                // lane halves split the 32 input channels
 
   // taps are processed in groups of TG per barrier (weights double-buffered per group); two
   // accumulators alternate so that consecutive MFMAs never wait for each other
@@ -139,23 +126,12 @@ __global__ __launch_bounds__(512, 2) void conv32_s2_fwd_kernel(const f2g_conv32_
       const int t = gidx * TG + u;
       if (t < KH * KW) {
         const int dh = t / KW, j = t - dh * KW;
-        const float* Ab = At + (j & 1) * SUB + ((ph + dh) * IW + pw + (j >> 1)) * PITCH + (P3 ? 0 : kk0);
-        const float* Bb = Bt + (cur * TG + u) * WB + li * PITCH + (P3 ? 0 : kk0);
-        if constexpr (P3) tap_mfma3(Ab, Bb, hh, acc, acc2);
-        else
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-          const float4 a = *reinterpret_cast<const float4*>(Ab + s4 * 4);
-          const float4 b = *reinterpret_cast<const float4*>(Bb + s4 * 4);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-          acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc2, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-          acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc2, 0, 0, 0);
-        }
+        const float* Ab = At + (j & 1) * SUB + ((ph + dh) * IW + pw + (j >> 1)) * PITCH;
+        const float* Bb = Bt + (cur * TG + u) * WB + li * PITCH;
+        tap_mfma3(Ab, Bb, hh, acc, acc2);
       }
     }
-    if constexpr (P3) store_presplit4(Bt + ((cur ^ 1) * TG + wu) * WB + wco * PITCH + wc4 * 2, wn);
-    else *reinterpret_cast<float4*>(Bt + ((cur ^ 1) * TG + wu) * WB + wco * PITCH + wc4 * 4) = wn;
+    store_presplit4(Bt + ((cur ^ 1) * TG + wu) * WB + wco * PITCH + wc4 * 2, wn);
     __syncthreads();
   }
 #pragma unroll
@@ -171,11 +147,11 @@ __global__ __launch_bounds__(512, 2) void conv32_s2_fwd_kernel(const f2g_conv32_
 #pragma unroll
   for (int e = 0; e < 16; ++e) acc[e] += red[(pg * 16 + e) * 64 + lane];
 
-  // ---- epilogue: bias + leaky ReLU; accumulator element e sits on pixel row (e&3)+8*(e>>2)+4*hh
+  // ---- epilogue: bias + leaky ReLU
   const float bias = d.bias ? d.bias[li] : 0.f;
 #pragma unroll
   for (int e = 0; e < 16; ++e) {
-    const int q = pg * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+    const int q = pg * 32 + acc_row(e) + 4 * hh;
     const int oh = h0 + (q >> 4), ow = w0 + (q & 15);
     if (oh < d.H && ow < d.Wout) {
       float v = acc[e] + bias;
@@ -186,7 +162,7 @@ __global__ __launch_bounds__(512, 2) void conv32_s2_fwd_kernel(const f2g_conv32_
 }
 
 // ---- persistent forward kernel (round 3; exact fp32) -------------------------------------------
-// The kernel above spends 30 % of a block's life outside the MFMAs (70 % of the fp32 rate on the
+// On the tiling above (one tile per block, two tap halves) exact fp32 spent 30 % of a block's life outside the MFMAs (70 % of the fp32 rate on the
 // largest band, less on bands whose width wastes tile columns): every block stages its patch with
 // nothing to overlap it but the CU's second block -- which was launched in the same phase --, half
 // of the waves idle through a cross-wave reduction at the end, and a barrier separates every 16
@@ -202,7 +178,10 @@ __global__ __launch_bounds__(512, 2) void conv32_s2_fwd_kernel(const f2g_conv32_
 //     columns of the band (widths 13 ... 129: 20 -> 24 instead of 32, 51 -> 56 instead of 64, ...).
 // (register arrays of native vectors: arrays of HIP's float4 STRUCT are filled through memcpy
 // intrinsics, which kept them in scratch memory)
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+template <int TH_, int TW_>
+constexpr size_t fwd_p_smem() {   // the patch's two column parities + the weight double buffer
+  return (size_t)(2 * ((TH_ + KH - 1) * (TW_ + (KW - 1) / 2) * PITCH + 16) + 2 * TG * WB) * sizeof(float);
+}
 
 template <int TH_, int TW_>
 __global__ __launch_bounds__(256, 2) void conv32_s2_fwd_p_kernel(const f2g_conv32_desc d, int tiles_w,
@@ -357,13 +336,13 @@ __global__ __launch_bounds__(256, 2) void conv32_s2_fwd_p_kernel(const f2g_conv3
 #undef F2G_C32_TAP
 #undef F2G_C32_PF
     static_assert(NG == 14, "the call list above is the tap-group loop");
-    // ---- epilogue: bias + leaky ReLU; accumulator element e = pixel (e&3) + 8 (e>>2) + 4 hh of the wave
+    // ---- epilogue: bias + leaky ReLU
     int sq, h0, w0;
     tile_pos(tile, sq, h0, w0);
     float* ys = d.y + (long long)sq * d.y_seq;
 #pragma unroll
     for (int e = 0; e < 16; ++e) {
-      const int q = wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+      const int q = wave * 32 + acc_row(e) + 4 * hh;
       const int oh = h0 + q / TW_, ow = w0 + q % TW_;
       if (oh < d.H && ow < d.Wout) {
         float v = acc[e] + acc2[e] + bias;
@@ -391,8 +370,8 @@ __global__ __launch_bounds__(256, 2) void conv32_s2_fwd_p_kernel(const f2g_conv3
 // d.x = g (S, H, Wout, 32), d.y = gx (S, H, Win, 32), d.w = wT[27 taps][ci][co].
 constexpr int GW = TW + 4;               // staged gradient columns
 constexpr int GSUB = IH * GW * PITCH;
+constexpr size_t DGRAD_SMEM = (size_t)(GSUB + 2 * TG * WB) * sizeof(float);
 
-template <bool P3>
 __global__ __launch_bounds__(512, 2) void conv32_s2_dgrad_kernel(const f2g_conv32_desc d) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   float* At = sm;                 // [IH][GW][PITCH]
@@ -410,15 +389,14 @@ __global__ __launch_bounds__(512, 2) void conv32_s2_dgrad_kernel(const f2g_conv3
   for (int i = tid; i < IH * GW * (C / 4); i += 512) {
     const int c4 = i & 7;
     int px = i >> 3;
-    // (split-bf16: 8-byte stores, two pixels per 16-lane group: pair pixels p and p+4, whose 144-byte
-    // pitch puts them on disjoint banks; IH*GW is a multiple of 8)
-    if constexpr (P3) px = (px & ~7) | ((px & 1) << 2) | ((px & 7) >> 1);
+    // (8-byte stores, two pixels per 16-lane group: pair pixels p and p+4, whose 144-byte pitch puts
+    // them on disjoint banks; IH*GW is a multiple of 8)
+    px = (px & ~7) | ((px & 1) << 2) | ((px & 7) >> 1);
     const int r = px / GW, xc = px - r * GW;
     const int h = h0 - 1 + r, c = m0 - 2 + xc;
     const bool ok = h >= 0 && h < d.H && c >= 0 && c < d.Wout;
     const float* p = ok ? gs + (long long)h * d.x_line + (long long)c * C + c4 * 4 : c32_zero;
-    if constexpr (P3) store_split4(At + (r * GW + xc) * PITCH + c4 * 2, *reinterpret_cast<const float4*>(p));
-    else *reinterpret_cast<float4*>(At + (r * GW + xc) * PITCH + c4 * 4) = *reinterpret_cast<const float4*>(p);
+    store_split4(At + (r * GW + xc) * PITCH + c4 * 2, *reinterpret_cast<const float4*>(p));
   }
   const int nu = e ? 4 : 5, NT = KH * nu;
   // weights: thread = (tap of the group, ci, 4 output channels of the forward conv)
@@ -428,10 +406,7 @@ __global__ __launch_bounds__(512, 2) void conv32_s2_dgrad_kernel(const f2g_conv3
     const int dh = ti / nu, u = ti - dh * nu;
     return d.w + (long long)(dh * KW + e + 2 * u) * (C * C) + wci * C + wc4 * 4;
   };
-  if constexpr (P3) store_presplit4(Bt + wu * WB + wci * PITCH + wc4 * 2,
-                                    *reinterpret_cast<const float4*>(wsrc(wu)));
-  else *reinterpret_cast<float4*>(Bt + wu * WB + wci * PITCH + wc4 * 4) =
-      *reinterpret_cast<const float4*>(wsrc(wu));
+  store_presplit4(Bt + wu * WB + wci * PITCH + wc4 * 2, *reinterpret_cast<const float4*>(wsrc(wu)));
   __syncthreads();
 
   f32x16 acc, acc2;
@@ -440,7 +415,6 @@ __global__ __launch_bounds__(512, 2) void conv32_s2_dgrad_kernel(const f2g_conv3
   const int pg = wave & 3, myu = wave >> 2;
   const int p = pg * 32 + li;
   const int ph = p >> 4, pw = p & 15;
-  const int kk0 = hh * 16;
   const int NG = (NT + TG - 1) / TG;
   for (int gidx = 0; gidx < NG; ++gidx) {
     const int cur = gidx & 1;
@@ -449,23 +423,12 @@ __global__ __launch_bounds__(512, 2) void conv32_s2_dgrad_kernel(const f2g_conv3
       const int ti = gidx * TG + myu;
       if (ti < NT) {
         const int dh = ti / nu, u = ti - dh * nu;
-        const float* Ab = At + ((ph + 2 - dh) * GW + pw + 4 - u) * PITCH + (P3 ? 0 : kk0);
-        const float* Bb = Bt + (cur * TG + myu) * WB + li * PITCH + (P3 ? 0 : kk0);
-        if constexpr (P3) tap_mfma3(Ab, Bb, hh, acc, acc2);
-        else
-#pragma unroll
-        for (int s4 = 0; s4 < 4; ++s4) {
-          const float4 a = *reinterpret_cast<const float4*>(Ab + s4 * 4);
-          const float4 b = *reinterpret_cast<const float4*>(Bb + s4 * 4);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.x, b.x, acc, 0, 0, 0);
-          acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.y, b.y, acc2, 0, 0, 0);
-          acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a.z, b.z, acc, 0, 0, 0);
-          acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(a.w, b.w, acc2, 0, 0, 0);
-        }
+        const float* Ab = At + ((ph + 2 - dh) * GW + pw + 4 - u) * PITCH;
+        const float* Bb = Bt + (cur * TG + myu) * WB + li * PITCH;
+        tap_mfma3(Ab, Bb, hh, acc, acc2);
       }
     }
-    if constexpr (P3) store_presplit4(Bt + ((cur ^ 1) * TG + wu) * WB + wci * PITCH + wc4 * 2, wn);
-    else *reinterpret_cast<float4*>(Bt + ((cur ^ 1) * TG + wu) * WB + wci * PITCH + wc4 * 4) = wn;
+    store_presplit4(Bt + ((cur ^ 1) * TG + wu) * WB + wci * PITCH + wc4 * 2, wn);
     __syncthreads();
   }
 #pragma unroll
@@ -486,19 +449,12 @@ __global__ __launch_bounds__(512, 2) void conv32_s2_dgrad_kernel(const f2g_conv3
   float cs = 0.f;
 #pragma unroll
   for (int q = 0; q < 16; ++q) {
-    const int px = pg * 32 + (q & 3) + 8 * (q >> 2) + 4 * hh;
+    const int px = pg * 32 + acc_row(q) + 4 * hh;
     const int oh = h0 + (px >> 4), ox = 2 * (m0 + (px & 15)) + e;
     if (oh < d.H && ox < d.Win) {
       const long long off = (long long)s * d.y_seq + (long long)oh * d.y_line + (long long)ox * C + li;
       float v = acc[q];
-      if (msk) {
-        const float y = d.mask_src[off];
-        if (fm) {
-          const float dl = y - d.fm_ref[off];
-          v += fmw * (dl > 0.f ? 1.f : (dl < 0.f ? -1.f : 0.f));
-        }
-        v *= y > 0.f ? 1.f : d.mask_slope;
-      }
+      if (msk) v = c32_mask_fm(v, d.mask_src[off], fm, [&] { return d.fm_ref[off]; }, fmw, d.mask_slope);
       cs += v;
       d.y[off] = v;
     }
@@ -633,19 +589,12 @@ __device__ __forceinline__ void conv32_dgrad_p_body(const f2g_conv32_desc& d, fl
     tile_pos(tile, sq, h0, m0);
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
-      const int px = wave * 32 + (q & 3) + 8 * (q >> 2) + 4 * hh;
+      const int px = wave * 32 + acc_row(q) + 4 * hh;
       const int oh = h0 + px / TW_, om = m0 + px % TW_;
       if (oh < d.H && om < Wp) {
         const long long off = (long long)sq * d.y_seq + (long long)oh * d.y_line + (long long)(2 * om + E) * C + li;
         float v = acc[q] + acc2[q];
-        if (msk) {
-          const float y = d.mask_src[off];
-          if (fm) {
-            const float dl = y - d.fm_ref[off];
-            v += fmw * (dl > 0.f ? 1.f : (dl < 0.f ? -1.f : 0.f));
-          }
-          v *= y > 0.f ? 1.f : d.mask_slope;
-        }
+        if (msk) v = c32_mask_fm(v, d.mask_src[off], fm, [&] { return d.fm_ref[off]; }, fmw, d.mask_slope);
         cs += v;
         d.y[off] = v;
       }
@@ -665,6 +614,11 @@ __device__ __forceinline__ void conv32_dgrad_p_body(const f2g_conv32_desc& d, fl
 }
 
 template <int TH_, int TW_>
+constexpr size_t dgrad_p_smem() {   // the gradient patch + the weight double buffer
+  return (size_t)((TH_ + KH - 1) * (TW_ + 4) * PITCH + 2 * TG * WB) * sizeof(float);
+}
+
+template <int TH_, int TW_>
 __global__ __launch_bounds__(256, 2) void conv32_s2_dgrad_p_kernel(const f2g_conv32_desc d, int tiles_w0,
                                                                   int tiles_w1, int tiles_h) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
@@ -674,138 +628,29 @@ __global__ __launch_bounds__(256, 2) void conv32_s2_dgrad_p_kernel(const f2g_con
 
 // ---- weight gradient of the same layer ---------------------------------------------------------
 // gw[co][tap][ci] += sum_px g[px][co] * x[px -> tap][ci].  MFMA rows = co, columns = ci, reduction =
-// the pixels of an 8 x 16 output tile; a block walks many tiles with the 27 (32 x 32) accumulator
+// the 128 pixels of an output tile; a block walks many tiles with the 27 (32 x 32) accumulator
 // tiles spread over its 8 waves (wave w owns taps w, w+8, w+16 over all 128 pixels and pixels
-// [16w, 16w+16) of taps 24..26) and leaves with one atomic per (block, element).  Both fragments are
-// single-float LDS reads at per-lane base + immediate offsets (the tile's pixels are walked in a
-// fully unrolled loop): no address arithmetic next to the MFMAs.  The implicit GEMM (M = 32,
-// windows re-gathered per tap) ran this at 57-61 TFLOP/s.
+// [16w, 16w+16) of taps 24..26) and leaves with one atomic per (block, element): c32_wgrad_flush.
+// The implicit GEMM (M = 32, windows re-gathered per tap) ran this at 57-61 TFLOP/s.
 // d.x = layer input (S, H, Win, 32), d.y = gradient of the pre-activation (S, H, Wout, 32) (read),
-// d.w is unused, d.gw = (32, 27*32) accumulated atomically.
+// d.w is unused, gw = (32, 27*32) accumulated atomically.
 constexpr int GT = TH * TW * C;          // floats of the staged gradient tile [px][co]
 
-__device__ __forceinline__ int px_off(int px) { return ((px >> 4) * IW + (px & 15)) * PITCH; }
-
-__global__ __launch_bounds__(512, 2) void conv32_s2_wgrad_kernel(const f2g_conv32_desc d, float* gw,
-                                                                 int tiles_h, int tiles_w,
-                                                                 int tiles_per_block) {
-  extern __shared__ __attribute__((aligned(16))) float sm[];
-  float* At = sm;                 // x patch [2 parities][IH][IW][PITCH]
-  float* Gt = sm + 2 * SUB;       // g tile [128 px][32 co]
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int li = lane & 31, hh = lane >> 5;
-  const int ntiles = d.S * tiles_h * tiles_w;
-  f32x16 acc[6];
-#pragma unroll
-  for (int a = 0; a < 6; ++a)
-#pragma unroll
-    for (int e = 0; e < 16; ++e) acc[a][e] = 0.f;
-  // per-lane bases: tap t -> patch offset; k slot hh = pixel parity inside a k step
-  int tb[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const int t = wave + 8 * a;
-    const int dh = t / KW, j = t - dh * KW;
-    tb[a] = (j & 1) * SUB + (dh * IW + (j >> 1)) * PITCH + li + hh * PITCH;
-  }
-  int ts[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    const int t = 24 + a;
-    const int dh = t / KW, j = t - dh * KW;
-    ts[a] = (j & 1) * SUB + (dh * IW + (j >> 1)) * PITCH + li + hh * PITCH;
-  }
-  const int gb = hh * C + li;
-  const int t0 = blockIdx.x * tiles_per_block;
-  for (int ti = t0; ti < t0 + tiles_per_block && ti < ntiles; ++ti) {
-    const int s = ti / (tiles_h * tiles_w), rem = ti - s * (tiles_h * tiles_w);
-    const int th = rem / tiles_w, tw = rem - th * tiles_w;
-    const int h0 = th * TH, w0 = tw * TW;
-    const float* xs = d.x + (long long)s * d.x_seq;
-    const float* gs = d.y + (long long)s * d.y_seq;
-    __syncthreads();   // the previous tile's readers are done
-    const int x0 = 2 * w0 - (KW - 1) / 2;
-    for (int i = tid; i < IH * (2 * IW - 1) * (C / 4); i += 512) {
-      const int c4 = i & 7;
-      const int px = i >> 3;
-      const int r = px / (2 * IW - 1), xr = px - r * (2 * IW - 1);
-      const int h = h0 - 1 + r, x = x0 + xr;
-      const bool ok = h >= 0 && h < d.H && x >= 0 && x < d.Win;
-      const float* p = ok ? xs + (long long)h * d.x_line + (long long)x * C + c4 * 4 : c32_zero;
-      *reinterpret_cast<float4*>(At + (xr & 1) * SUB + (r * IW + (xr >> 1)) * PITCH + c4 * 4) =
-          *reinterpret_cast<const float4*>(p);
-    }
-    for (int i = tid; i < TH * TW * (C / 4); i += 512) {
-      const int c4 = i & 7, px = i >> 3;
-      const int h = h0 + (px >> 4), w = w0 + (px & 15);
-      const bool ok = h < d.H && w < d.Wout;
-      const float* p = ok ? gs + (long long)h * d.y_line + (long long)w * C + c4 * 4 : c32_zero;
-      *reinterpret_cast<float4*>(Gt + px * C + c4 * 4) = *reinterpret_cast<const float4*>(p);
-    }
-    __syncthreads();
-    // taps owned over the whole tile: 64 k steps of two pixels
-#pragma unroll
-    for (int st = 0; st < TH * TW / 2; ++st) {
-      const float a = Gt[gb + st * 2 * C];
-      const int po = px_off(2 * st);
-#pragma unroll
-      for (int q = 0; q < 3; ++q)
-        acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, At[tb[q] + po], acc[q], 0, 0, 0);
-    }
-    // taps 24..26: this wave's 16 pixels (8 k steps); pixel index = 16*wave + 2*st + hh
-    {
-      const float* Gw = Gt + gb + wave * 16 * C;
-      const int pbase = ((wave)*IW) * PITCH;   // pixel row = wave (16 pixels per tile row)
-#pragma unroll
-      for (int st = 0; st < 8; ++st) {
-        const float a = Gw[st * 2 * C];
-        const int po = pbase + (2 * st) * PITCH;
-#pragma unroll
-        for (int q = 0; q < 3; ++q)
-          acc[3 + q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, At[ts[q] + po], acc[3 + q], 0, 0, 0);
-      }
-    }
-  }
-  // ---- flush: taps owned by one wave go straight out; the three shared taps are summed over the
-  // waves through LDS first
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const int t = wave + 8 * q;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int co = (e & 3) + 8 * (e >> 2) + 4 * hh;
-      atomicAdd(gw + co * (KH * KW * C) + t * C + li, acc[q][e]);
-    }
-  }
-  float* red = sm;   // [8 waves][16][64]
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 16; ++e) red[(wave * 16 + e) * 64 + lane] = acc[3 + q][e];
-    __syncthreads();
-    if (wave == q) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        float v = 0.f;
-#pragma unroll
-        for (int w8 = 0; w8 < 8; ++w8) v += red[(w8 * 16 + e) * 64 + lane];
-        const int co = (e & 3) + 8 * (e >> 2) + 4 * hh;
-        atomicAdd(gw + co * (KH * KW * C) + (24 + q) * C + li, v);
-      }
-    }
-  }
+// ---- weight gradient, double-buffered (round 4; exact fp32) ----------------------------------------
+// Both fragments are single-float LDS reads at per-lane base + immediate offsets (the tile's pixels are
+// walked in a fully unrolled loop): no address arithmetic next to the MFMAs.  With one staged tile and two
+// blocks per CU this kept the matrix pipe 64 % busy (PMC, profiles/r04_pmc_lean_fp32.txt): a block staged
+// a tile with nothing to overlap it but the CU's other block -- launched in the same phase -- and two
+// barriers bracketed every tile.  So ONE block of 8 waves per CU with TWO staged tiles in its 147 KB of
+// LDS: the next tile's rows (9 x 16 bytes per thread) are requested before the current tile's 216 MFMAs
+// per wave and stored into the other buffer behind them; one barrier per tile.  (Four waves with seven
+// taps each and two blocks per CU -- no shared taps at all -- need 112 accumulator + 68 staging
+// registers: spills.)
+template <int TH_, int TW_>
+constexpr size_t wgrad_p_smem() {   // two staged tiles: the patch's two column parities + the gradient tile
+  return (size_t)2 * (2 * ((TH_ + KH - 1) * (TW_ + (KW - 1) / 2) * PITCH + 16) + GT) * sizeof(float);
 }
 
-// ---- weight gradient, double-buffered (round 4; exact fp32) ----------------------------------------
-// conv32_s2_wgrad_kernel above keeps the matrix pipe 64 % busy (PMC, profiles/r04_pmc_lean_fp32.txt):
-// a block stages a tile with nothing to overlap it but the CU's other block -- launched in the same
-// phase -- and two barriers bracket every tile.  Same decomposition here (wave w owns taps w, w + 8,
-// w + 16 over the whole tile and tile row w of taps 24..26; single-float fragment reads at per-lane bases +
-// immediate offsets), but ONE block of 8 waves per CU with TWO staged tiles in its 147 KB of LDS: the
-// next tile's rows (9 x 16 bytes per thread) are requested before the current tile's 216 MFMAs per wave
-// and stored into the other buffer behind them; one barrier per tile.  (Four waves with seven taps each
-// and two blocks per CU -- no shared taps at all -- need 112 accumulator + 68 staging registers: spills.)
 template <int TH_, int TW_>
 __global__ __launch_bounds__(512, 1) void conv32_s2_wgrad_p_kernel(const f2g_conv32_desc d, float* gw,
                                                                    int tiles_h, int tiles_w,
@@ -926,57 +771,19 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_wgrad_p_kernel(const f2g_con
     __syncthreads();
     cur ^= 1;
   }
-  // ---- flush: taps owned by one wave go straight out; the three shared taps are summed over the
-  // waves through LDS first
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const int t = wave + 8 * q;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int co = (e & 3) + 8 * (e >> 2) + 4 * hh;
-      atomicAdd(gw + co * (KH * KW * C) + t * C + li, acc[q][e]);
-    }
-  }
-  float* red = sm;   // [8 waves][16][64]
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 16; ++e) red[(wave * 16 + e) * 64 + lane] = acc[3 + q][e];
-    __syncthreads();
-    if (wave == q) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        float v = 0.f;
-#pragma unroll
-        for (int w8 = 0; w8 < 8; ++w8) v += red[(w8 * 16 + e) * 64 + lane];
-        const int co = (e & 3) + 8 * (e >> 2) + 4 * hh;
-        atomicAdd(gw + co * (KH * KW * C) + (24 + q) * C + li, v);
-      }
-    }
-  }
+  c32_wgrad_flush<KH * KW, 3>(gw, sm, acc, wave, lane, li, hh);
 }
 
 // ---- weight gradient, split-bf16 ---------------------------------------------------------------
-// Same decomposition as conv32_s2_wgrad_kernel (MFMA rows = co, columns = ci, reduction = the pixels
-// of an 8 x 16 output tile; wave w owns taps w, w+8, w+16 over the whole tile and tile row w of taps
+// The decomposition of conv32_s2_wgrad_p_kernel on 8 x 16 tiles (MFMA rows = co, columns = ci, reduction =
+// the pixels of the tile; wave w owns taps w, w+8, w+16 over the whole tile and tile row w of taps
 // 24..26), but a bf16 MFMA wants 8 CONSECUTIVE k per lane and k = pixels is the slow axis of both
 // staged operands ([pixel][channel]).  The tile is therefore staged as bf16 planes with 64-byte
 // pixels (hi and lo of the gradient tile and of the two column parities of the input patch, split
-// once while they are staged) and the fragments come from ds_read_b64_tr_b16: a 16-lane group reads
-// 4 pixels x 16 channels and every lane receives the 4 pixels of its channel; two reads = the 8 k of
-// a lane half, a tile row of 16 pixels = one k step.  The four pixels of a read are consecutive
-// columns = 256 contiguous bytes: conflict-free without padding.
-typedef short s16x4 __attribute__((ext_vector_type(4)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-
-__device__ __forceinline__ bf16x8 tr_pix8(const unsigned char* p) {   // pixels +0..3 and +4..7
-  typedef s16x4 __attribute__((address_space(3))) * lds_p;
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p + 4 * 64));
-  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
-}
-
+// once while they are staged) and the fragments come from ds_read_b64_tr_b16 (tr_pix8): a 16-lane group
+// reads 4 pixels x 16 channels and every lane receives the 4 pixels of its channel; two reads = the 8 k
+// of a lane half, a tile row of 16 pixels = one k step.  The four pixels of a read are consecutive
+// columns = 256 contiguous bytes: conflict-free without padding.  One staged tile, two blocks per CU.
 __device__ __forceinline__ void store_split_planes(unsigned char* hi, unsigned char* lo, const float4 v) {
   float r0, r1, r2, r3, z0, z1;
   u32x2 h, l;
@@ -991,6 +798,8 @@ __device__ __forceinline__ void store_split_planes(unsigned char* hi, unsigned c
 constexpr int XPAR = IH * IW * 64 + 64;  // bytes of one parity of a plane (+64: see SUB)
 constexpr int XPL = 2 * XPAR;           // bytes of one plane of the input patch (both parities)
 constexpr int GPL = TH * TW * 64;       // bytes of one plane of the gradient tile
+constexpr size_t WGRAD3_SMEM = 2 * XPL + 2 * GPL;
+static_assert(WGRAD3_SMEM >= (size_t)8 * 16 * 64 * 4, "the flush reuses the planes as its reduction buffer");
 
 __global__ __launch_bounds__(512, 2) void conv32_s2_wgrad3_kernel(const f2g_conv32_desc d, float* gw,
                                                                   int tiles_h, int tiles_w,
@@ -1083,34 +892,7 @@ __global__ __launch_bounds__(512, 2) void conv32_s2_wgrad3_kernel(const f2g_conv
       }
     }
   }
-  // ---- flush (as the fp32 kernel)
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const int t = wave + 8 * q;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int co = (e & 3) + 8 * (e >> 2) + 4 * hh;
-      atomicAdd(gw + co * (KH * KW * C) + t * C + li, acc[q][e]);
-    }
-  }
-  float* red = smf;   // [8 waves][16][64]
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 16; ++e) red[(wave * 16 + e) * 64 + lane] = acc[3 + q][e];
-    __syncthreads();
-    if (wave == q) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        float v = 0.f;
-#pragma unroll
-        for (int w8 = 0; w8 < 8; ++w8) v += red[(w8 * 16 + e) * 64 + lane];
-        const int co = (e & 3) + 8 * (e >> 2) + 4 * hh;
-        atomicAdd(gw + co * (KH * KW * C) + (24 + q) * C + li, v);
-      }
-    }
-  }
+  c32_wgrad_flush<KH * KW, 3>(gw, smf, acc, wave, lane, li, hh);
 }
 
 }  // namespace
@@ -1119,6 +901,23 @@ __global__ __launch_bounds__(512, 2) void conv32_s2_wgrad3_kernel(const f2g_conv
 int f2g_conv32_fwd6_launch(const f2g_conv32_desc* d, hipStream_t st);
 int f2g_conv32_dgrad6_launch(const f2g_conv32_desc* d, hipStream_t st);
 int f2g_conv32_wgrad6_launch(const f2g_conv32_desc* d, float* gw, hipStream_t st);
+
+
+namespace {
+
+// The exact-fp32 kernels (precision 0) address a map's rows with 32-bit offsets and count their tiles in an int.
+// (Descriptors past these limits used to fall back to exact-fp32 instances of the non-persistent kernels, which
+// nothing ever ran: no wrapper, band width or test reaches 2^24 floats per line -- 524288 columns -- or 2^30
+// tiles -- 17 TB of output --, and the fp32-class launchers refuse the same descriptors.)
+bool fp32_limits_ok(const char* fn, const f2g_conv32_desc* d, long long ntiles) {
+  if (d->x_line < (1ll << 24) && ntiles < (1ll << 30)) return true;
+  char msg[160];
+  snprintf(msg, sizeof msg, "%s: precision 0 needs x_line < 2^24 floats and fewer than 2^30 tiles", fn);
+  f2g_set_error(msg);
+  return false;
+}
+
+}  // namespace
 
 extern "C" int f2g_conv32_s2_fwd(const f2g_conv32_desc* d, f2g_stream_t stream) {
   if (!d || !d->x || !d->w || !d->y) return F2G_EINVAL;
@@ -1131,53 +930,19 @@ extern "C" int f2g_conv32_s2_fwd(const f2g_conv32_desc* d, f2g_stream_t stream) 
     if (!al(d->y) || (d->y_line & 3) || (d->y_seq & 3)) return F2G_EINVAL;
     return f2g_conv32_fwd6_launch(d, (hipStream_t)stream);
   }
-  const size_t smem = (size_t)(2 * SUB + 2 * TG * WB) * sizeof(float);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_fwd_kernel<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_fwd_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_done = true;
+  if (d->precision == 1) {   // w = the f2g_split_bf16 image of the packed weights
+    const int tiles = ((d->H + TH - 1) / TH) * ((d->Wout + TW - 1) / TW);
+    c32_lds_once<conv32_s2_fwd_kernel>(FWD_SMEM);
+    hipLaunchKernelGGL(conv32_s2_fwd_kernel, dim3(tiles, d->S), dim3(512), FWD_SMEM, (hipStream_t)stream, *d);
+    return f2g_check_launch();
   }
-  const int tiles = ((d->H + TH - 1) / TH) * ((d->Wout + TW - 1) / TW);
-  if (d->precision == 0 && d->x_line < (1ll << 24)) {
-    // tile shape: fewer wasted output pixels wins (8 x 16 on a tie)
-    auto waste = [&](int th, int tw) {
-      return (long long)((d->H + th - 1) / th * th) * ((d->Wout + tw - 1) / tw * tw);
-    };
-    const bool tall = waste(16, 8) < waste(8, 16);
-    const int th = tall ? 16 : 8, tw = tall ? 8 : 16;
-    const int tiles_h = (d->H + th - 1) / th, tiles_w = (d->Wout + tw - 1) / tw;
-    const long long nt = (long long)tiles_h * tiles_w * d->S;
-    if (nt < (1ll << 30)) {
-      const size_t sm8 = (size_t)(2 * ((8 + 2) * (16 + 4) * PITCH + 16) + 2 * TG * WB) * sizeof(float);
-      const size_t sm16 = (size_t)(2 * ((16 + 2) * (8 + 4) * PITCH + 16) + 2 * TG * WB) * sizeof(float);
-      static bool attr2 = false;
-      if (!attr2) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_fwd_p_kernel<8, 16>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm8);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_fwd_p_kernel<16, 8>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm16);
-        attr2 = true;
-      }
-      const int grid = (int)(nt < 512 ? nt : 512);     // 256 CUs x 2 resident blocks
-      if (tall)
-        hipLaunchKernelGGL((conv32_s2_fwd_p_kernel<16, 8>), dim3(grid), dim3(256), sm16,
-                           (hipStream_t)stream, *d, tiles_w, tiles_h, (int)nt);
-      else
-        hipLaunchKernelGGL((conv32_s2_fwd_p_kernel<8, 16>), dim3(grid), dim3(256), sm8,
-                           (hipStream_t)stream, *d, tiles_w, tiles_h, (int)nt);
-      return f2g_check_launch();
-    }
-  }
-  if (d->precision == 1)   // w = the f2g_split_bf16 image of the packed weights
-    hipLaunchKernelGGL(conv32_s2_fwd_kernel<true>, dim3(tiles, d->S), dim3(512), smem,
-                       (hipStream_t)stream, *d);
-  else
-    hipLaunchKernelGGL(conv32_s2_fwd_kernel<false>, dim3(tiles, d->S), dim3(512), smem,
-                       (hipStream_t)stream, *d);
-  return f2g_check_launch();
+  const c32_tiling t = c32_pick_tiles(d->H, d->Wout);
+  const long long nt = (long long)t.tiles_h * t.tiles_w * d->S;
+  if (!fp32_limits_ok("f2g_conv32_s2_fwd", d, nt)) return F2G_EINVAL;
+  const int grid = (int)(nt < 512 ? nt : 512);     // 256 CUs x 2 resident blocks
+  return c32_launch_shape<conv32_s2_fwd_p_kernel<8, 16>, conv32_s2_fwd_p_kernel<16, 8>>(
+      t.tall, fwd_p_smem<8, 16>(), fwd_p_smem<16, 8>(), dim3(grid), dim3(256), (hipStream_t)stream, *d, t.tiles_w,
+      t.tiles_h, (int)nt);
 }
 
 extern "C" int f2g_conv32_s2_dgrad(const f2g_conv32_desc* d, f2g_stream_t stream) {
@@ -1191,53 +956,20 @@ extern "C" int f2g_conv32_s2_dgrad(const f2g_conv32_desc* d, f2g_stream_t stream
     if (!al(d->y) || (d->y_line & 3) || (d->y_seq & 3) || !al(d->mask_src) || !al(d->fm_ref)) return F2G_EINVAL;
     return f2g_conv32_dgrad6_launch(d, (hipStream_t)stream);
   }
-  const size_t smem = (size_t)(GSUB + 2 * TG * WB) * sizeof(float);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_dgrad_kernel<false>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_dgrad_kernel<true>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_done = true;
+  if (d->precision == 1) {   // w = the f2g_split_bf16 image of the transposed tiles
+    const int tiles = ((d->H + TH - 1) / TH) * (((d->Win + 1) / 2 + TW - 1) / TW);
+    c32_lds_once<conv32_s2_dgrad_kernel>(DGRAD_SMEM);
+    hipLaunchKernelGGL(conv32_s2_dgrad_kernel, dim3(tiles, d->S, 2), dim3(512), DGRAD_SMEM, (hipStream_t)stream, *d);
+    return f2g_check_launch();
   }
-  const int tiles = ((d->H + TH - 1) / TH) * (((d->Win + 1) / 2 + TW - 1) / TW);
-  if (d->precision == 0 && d->x_line < (1ll << 24)) {
-    const int Wp0 = (d->Win + 1) / 2, Wp1 = d->Win / 2;
-    auto waste = [&](int th, int tw) {
-      return (long long)((d->H + th - 1) / th * th) * ((Wp0 + tw - 1) / tw * tw + (Wp1 + tw - 1) / tw * tw);
-    };
-    const bool tall = waste(16, 8) < waste(8, 16);
-    const int th = tall ? 16 : 8, tw = tall ? 8 : 16;
-    const int tiles_h = (d->H + th - 1) / th, tw0 = (Wp0 + tw - 1) / tw, tw1 = (Wp1 + tw - 1) / tw;
-    const long long nt0 = (long long)tiles_h * tw0 * d->S;
-    if (nt0 < (1ll << 30)) {
-      const size_t sm8 = (size_t)((8 + 2) * (16 + 4) * PITCH + 2 * TG * WB) * sizeof(float);
-      const size_t sm16 = (size_t)((16 + 2) * (8 + 4) * PITCH + 2 * TG * WB) * sizeof(float);
-      static bool attr2 = false;
-      if (!attr2) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_dgrad_p_kernel<8, 16>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm8);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_dgrad_p_kernel<16, 8>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm16);
-        attr2 = true;
-      }
-      const int grid = (int)(nt0 < 256 ? nt0 : 256);   // per parity: 256 CUs x 2 resident blocks in all
-      if (tall)
-        hipLaunchKernelGGL((conv32_s2_dgrad_p_kernel<16, 8>), dim3(grid, 2), dim3(256), sm16,
-                           (hipStream_t)stream, *d, tw0, tw1, tiles_h);
-      else
-        hipLaunchKernelGGL((conv32_s2_dgrad_p_kernel<8, 16>), dim3(grid, 2), dim3(256), sm8,
-                           (hipStream_t)stream, *d, tw0, tw1, tiles_h);
-      return f2g_check_launch();
-    }
-  }
-  if (d->precision == 1)   // w = the f2g_split_bf16 image of the transposed tiles
-    hipLaunchKernelGGL(conv32_s2_dgrad_kernel<true>, dim3(tiles, d->S, 2), dim3(512), smem,
-                       (hipStream_t)stream, *d);
-  else
-    hipLaunchKernelGGL(conv32_s2_dgrad_kernel<false>, dim3(tiles, d->S, 2), dim3(512), smem,
-                       (hipStream_t)stream, *d);
-  return f2g_check_launch();
+  // columns of the even / odd parity: one block row of the grid each, both weighed in the pick
+  const c32_tiling t = c32_pick_tiles(d->H, (d->Win + 1) / 2, d->Win / 2);
+  const long long nt0 = (long long)t.tiles_h * t.tiles_w * d->S;
+  if (!fp32_limits_ok("f2g_conv32_s2_dgrad", d, nt0)) return F2G_EINVAL;
+  const int grid = (int)(nt0 < 256 ? nt0 : 256);   // per parity: 256 CUs x 2 resident blocks in all
+  return c32_launch_shape<conv32_s2_dgrad_p_kernel<8, 16>, conv32_s2_dgrad_p_kernel<16, 8>>(
+      t.tall, dgrad_p_smem<8, 16>(), dgrad_p_smem<16, 8>(), dim3(grid, 2), dim3(256), (hipStream_t)stream, *d,
+      t.tiles_w, t.tiles_w_also, t.tiles_h);
 }
 
 extern "C" int f2g_conv32_s2_wgrad(const f2g_conv32_desc* d, float* gw, f2g_stream_t stream) {
@@ -1248,62 +980,23 @@ extern "C" int f2g_conv32_s2_wgrad(const f2g_conv32_desc* d, float* gw, f2g_stre
   if (!al(d->x) || !al(d->y) || (d->x_line & 3) || (d->x_seq & 3) || (d->y_line & 3) || (d->y_seq & 3))
     return F2G_EINVAL;
   if (d->precision == 3) return f2g_conv32_wgrad6_launch(d, gw, (hipStream_t)stream);   // operands split while staged
-  const int tiles_h = (d->H + TH - 1) / TH, tiles_w = (d->Wout + TW - 1) / TW;
-  const int ntiles = d->S * tiles_h * tiles_w;
-  int per = (ntiles + 511) / 512;   // <= 512 blocks (two per CU): bounds the atomics
-  if (per < 1) per = 1;
   if (d->precision == 1) {   // split-bf16 (the operands are split while they are staged)
-    const size_t smem3 = (size_t)(2 * XPL + 2 * GPL) > (size_t)8 * 16 * 64 * 4 ? (size_t)(2 * XPL + 2 * GPL)
-                                                                              : (size_t)8 * 16 * 64 * 4;
-    static bool attr3 = false;
-    if (!attr3) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_wgrad3_kernel),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem3);
-      attr3 = true;
-    }
-    hipLaunchKernelGGL(conv32_s2_wgrad3_kernel, dim3((ntiles + per - 1) / per), dim3(512), smem3,
+    const int tiles_h = (d->H + TH - 1) / TH, tiles_w = (d->Wout + TW - 1) / TW;
+    const int ntiles = d->S * tiles_h * tiles_w;
+    int per = (ntiles + 511) / 512;   // <= 512 blocks (two per CU): bounds the atomics
+    if (per < 1) per = 1;
+    c32_lds_once<conv32_s2_wgrad3_kernel>(WGRAD3_SMEM);
+    hipLaunchKernelGGL(conv32_s2_wgrad3_kernel, dim3((ntiles + per - 1) / per), dim3(512), WGRAD3_SMEM,
                        (hipStream_t)stream, *d, gw, tiles_h, tiles_w, per);
     return f2g_check_launch();
   }
-  const size_t smem = (size_t)(2 * SUB + GT) * sizeof(float);
-  static bool attr_done = false;
-  if (!attr_done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_wgrad_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr_done = true;
-  }
-  if (d->x_line < (1ll << 24)) {
-    auto waste = [&](int th, int tw) {
-      return (long long)((d->H + th - 1) / th * th) * ((d->Wout + tw - 1) / tw * tw);
-    };
-    const bool tall = waste(16, 8) < waste(8, 16);
-    const int th = tall ? 16 : 8, tw = tall ? 8 : 16;
-    const int th_n = (d->H + th - 1) / th, tw_n = (d->Wout + tw - 1) / tw;
-    const long long nt = (long long)d->S * th_n * tw_n;
-    if (nt < (1ll << 30)) {
-      int per1 = (int)((nt + 255) / 256);          // <= 256 blocks: one per CU
-      if (per1 < 1) per1 = 1;
-      const size_t sm8 = (size_t)2 * (2 * ((8 + 2) * (16 + 4) * PITCH + 16) + GT) * sizeof(float);
-      const size_t sm16 = (size_t)2 * (2 * ((16 + 2) * (8 + 4) * PITCH + 16) + GT) * sizeof(float);
-      static bool attr2 = false;
-      if (!attr2) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_wgrad_p_kernel<8, 16>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm8);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_wgrad_p_kernel<16, 8>),
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm16);
-        attr2 = true;
-      }
-      const unsigned grid = (unsigned)((nt + per1 - 1) / per1);
-      if (tall)
-        hipLaunchKernelGGL((conv32_s2_wgrad_p_kernel<16, 8>), dim3(grid), dim3(512), sm16, (hipStream_t)stream,
-                           *d, gw, th_n, tw_n, per1);
-      else
-        hipLaunchKernelGGL((conv32_s2_wgrad_p_kernel<8, 16>), dim3(grid), dim3(512), sm8, (hipStream_t)stream,
-                           *d, gw, th_n, tw_n, per1);
-      return f2g_check_launch();
-    }
-  }
-  hipLaunchKernelGGL(conv32_s2_wgrad_kernel, dim3((ntiles + per - 1) / per), dim3(512), smem,
-                     (hipStream_t)stream, *d, gw, tiles_h, tiles_w, per);
-  return f2g_check_launch();
+  const c32_tiling t = c32_pick_tiles(d->H, d->Wout);
+  const long long nt = (long long)d->S * t.tiles_h * t.tiles_w;
+  if (!fp32_limits_ok("f2g_conv32_s2_wgrad", d, nt)) return F2G_EINVAL;
+  int per = (int)((nt + 255) / 256);          // <= 256 blocks: one per CU
+  if (per < 1) per = 1;
+  const unsigned grid = (unsigned)((nt + per - 1) / per);
+  return c32_launch_shape<conv32_s2_wgrad_p_kernel<8, 16>, conv32_s2_wgrad_p_kernel<16, 8>>(
+      t.tall, wgrad_p_smem<8, 16>(), wgrad_p_smem<16, 8>(), dim3(grid), dim3(512), (hipStream_t)stream, *d, gw,
+      t.tiles_h, t.tiles_w, per);
 }

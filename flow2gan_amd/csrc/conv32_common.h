@@ -1,0 +1,120 @@
+// What the direct MRD band convolutions share (conv32.hip: exact fp32 and split-bf16; conv32x6.hip: fp32 class):
+// the vector types and layer constants, the accumulator-row map, the transposed fragment read of the weight
+// gradients, the pick between the two tile shapes and their launch, the store expression of the data gradients and
+// the flush of the weight gradients.  What a kernel stages and how it walks its taps stay with the kernel.
+// Internal linkage throughout.
+#pragma once
+#include "common.h"
+
+namespace {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+
+constexpr int C = 32;                   // channels in = out
+constexpr int KH = 3, KW = 9;           // the (3, 9) layer's taps
+
+// source of every staged chunk that lies outside the map
+__device__ __attribute__((aligned(16))) float c32_zero[4] = {0.f, 0.f, 0.f, 0.f};
+
+// element e of a 32 x 32 MFMA accumulator sits on tile row (e & 3) + 8 (e >> 2) + 4 hh of lane half hh
+__device__ __forceinline__ constexpr int acc_row(int e) { return (e & 3) + 8 * (e >> 2); }
+
+// K-major fragment out of bf16 planes with 64-byte pixels (ds_read_b64_tr_b16): pixels +0..3 and +4..7
+__device__ __forceinline__ bf16x8 tr_pix8(const unsigned char* p) {
+  typedef s16x4 __attribute__((address_space(3))) * lds_p;
+  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p));
+  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p + 4 * 64));
+  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+// ---- tile shape: 8 x 16 or 16 x 8 output pixels, whichever wastes fewer pixels of the map, 8 x 16 on a tie.
+// W = the columns to tile (Wout; per-parity column counts in the data gradients).  W_also > 0: a second column
+// count tiled beside W whose waste counts too -- the exact-fp32 data gradient walks both column parities on the
+// picked shape and weighs both, the fp32-class one (one tile = both parities) weighs the even parity alone.
+struct c32_tiling {
+  bool tall;                            // 16 x 8
+  int tiles_h, tiles_w, tiles_w_also;
+};
+inline c32_tiling c32_pick_tiles(int H, int W, int W_also = 0) {
+  auto waste = [&](int th, int tw) {
+    return (long long)((H + th - 1) / th * th) * ((W + tw - 1) / tw * tw + (W_also + tw - 1) / tw * tw);
+  };
+  const bool tall = waste(16, 8) < waste(8, 16);
+  const int th = tall ? 16 : 8, tw = tall ? 8 : 16;
+  return {tall, (H + th - 1) / th, (W + tw - 1) / tw, (W_also + tw - 1) / tw};
+}
+
+// a kernel instance's dynamic LDS limit, raised once per process (thread-safe: a function-local static)
+template <auto KERNEL>
+inline void c32_lds_once(size_t smem) {
+  static const hipError_t done = [&] {
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize,
+                               (int)smem);
+  }();
+  (void)done;
+}
+
+// launch of the shape c32_pick_tiles chose out of a kernel's <8, 16> and <16, 8> instances
+template <auto K8x16, auto K16x8, typename... Args>
+inline int c32_launch_shape(bool tall, size_t smem8x16, size_t smem16x8, dim3 grid, dim3 block, hipStream_t st,
+                            Args... args) {
+  c32_lds_once<K8x16>(smem8x16);
+  c32_lds_once<K16x8>(smem16x8);
+  if (tall) hipLaunchKernelGGL(K16x8, grid, block, smem16x8, st, args...);
+  else hipLaunchKernelGGL(K8x16, grid, block, smem8x16, st, args...);
+  return f2g_check_launch();
+}
+
+// ---- store expression of the data gradients: the feature-matching sign term against the reference map (fm; ref()
+// reads its value and is called only then), then the leaky-ReLU backward of the layer below, whose output was y
+template <typename REF>
+__device__ __forceinline__ float c32_mask_fm(float v, float y, bool fm, REF ref, float fmw, float mask_slope) {
+  if (fm) {
+    const float dl = y - ref();
+    v += fmw * (dl > 0.f ? 1.f : (dl < 0.f ? -1.f : 0.f));
+  }
+  return v * (y > 0.f ? 1.f : mask_slope);
+}
+
+// ---- flush of a weight gradient: gw (32, NT * 32) [co][tap][ci] += the block's NT accumulator tiles (rows = co,
+// columns = ci).  Wave w of 8 owns the taps w + 8 q, q < OWN, over all pixels (acc[q]): they go straight out as
+// atomics.  Of the other NT - 8 * OWN taps every wave holds a partial tile (acc[OWN + q]): they are summed over
+// the waves through LDS (red: [8 waves][16][64 lanes] floats, anything of the block's that is dead by now), one
+// tap at a time, and leave as one atomic per output and block.  wave, lane = the thread's; li = lane & 31, hh =
+// lane >> 5.  (The kernel's own values and the LDS address space spelled out: with the roles recomputed here, or
+// red left a generic pointer until it is inlined, the compiler pairs fewer of the reduction's LDS reads and
+// conv32_s2_wgrad_p_kernel changes a register count -- profiles/conv32_shared_isa.txt.)
+template <int NT, int OWN>
+__device__ __forceinline__ void c32_wgrad_flush(float* gw, float* red_, const f32x16 (&acc)[OWN + NT - 8 * OWN],
+                                                int wave, int lane, int li, int hh) {
+  typedef float __attribute__((address_space(3))) * lds_f;
+  const lds_f red = (lds_f)red_;
+#pragma unroll
+  for (int q = 0; q < OWN; ++q) {
+    const int t = wave + 8 * q;
+#pragma unroll
+    for (int e = 0; e < 16; ++e) atomicAdd(gw + (acc_row(e) + 4 * hh) * (NT * C) + t * C + li, acc[q][e]);
+  }
+#pragma unroll
+  for (int q = 0; q < NT - 8 * OWN; ++q) {
+    __syncthreads();
+#pragma unroll
+    for (int e = 0; e < 16; ++e) red[(wave * 16 + e) * 64 + lane] = acc[OWN + q][e];
+    __syncthreads();
+    if (wave == (q & 7)) {
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        float v = 0.f;
+#pragma unroll
+        for (int w8 = 0; w8 < 8; ++w8) v += red[(w8 * 16 + e) * 64 + lane];
+        atomicAdd(gw + (acc_row(e) + 4 * hh) * (NT * C) + (8 * OWN + q) * C + li, v);
+      }
+    }
+  }
+}
+
+}  // namespace

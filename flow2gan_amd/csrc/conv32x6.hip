@@ -16,21 +16,14 @@
 // block's life (no weight ever passes through LDS); the (3, 3) layer keeps its nine weight tiles in LDS.
 #include <stdlib.h>
 
-#include "common.h"
-
+#include "conv32_common.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int C = 32, KH = 3, KW = 9, NTAP = KH * KW;
+constexpr int NTAP = KH * KW;
 constexpr int PB = 208;            // bytes of a staged pixel / weight row
-
-__device__ __attribute__((aligned(16))) float c6_zero[4] = {0.f, 0.f, 0.f, 0.f};
 
 // three bf16 pieces of four floats (common.h: f2g_split3_pair, round to nearest even at every step)
 __device__ __forceinline__ void split3(const f32x4 v, u32x2& p0, u32x2& p1, u32x2& p2) {
@@ -78,6 +71,16 @@ __device__ __forceinline__ void tap6(const unsigned char* Ab, const unsigned cha
   ld6(a, Ab);
   ld6(b, Bb);
   mm6(a, b, acc0, acc1);
+}
+
+// one product in the fp32 class: the six MFMAs with i + j <= 2 of the pieces a[i], b[j], smallest terms first
+__device__ __forceinline__ void mfma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16& c) {
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
+  c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
 }
 
 // x / D for 0 <= x < 512 and the staged widths that occur (39, 23: forward patch columns; 20, 12: gradient patch)
@@ -157,7 +160,7 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_fwd6_kernel(const f2g_conv32
       const int r = div_small<XW>(px), xr = px - r * XW;
       const int h = h0 - 1 + r, x = x0 + xr;
       const bool ok = px < IHv * XW && h >= 0 && h < d.H && x >= 0 && x < d.Win;
-      pf[q] = *reinterpret_cast<const f32x4*>(ok ? org + (r * xl + xr * C) : c6_zero);
+      pf[q] = *reinterpret_cast<const f32x4*>(ok ? org + (r * xl + xr * C) : c32_zero);
     }
   };
   auto store_patch = [&](const f32x4 (&pf)[NCHK]) {
@@ -227,9 +230,7 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_fwd6_kernel(const f2g_conv32
       }
       __builtin_amdgcn_sched_barrier(0);
       if (j < KPW - 1 || seven) {
-#define F2G_X6_ONE(I, J) acc[g4] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[u & 1][I], wf[j][J], acc[g4], 0, 0, 0);
-        F2G_X6_ONE(2, 0) F2G_X6_ONE(1, 1) F2G_X6_ONE(0, 2) F2G_X6_ONE(1, 0) F2G_X6_ONE(0, 1) F2G_X6_ONE(0, 0)
-#undef F2G_X6_ONE
+        mfma6(a[u & 1], wf[j], acc[g4]);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -244,7 +245,7 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_fwd6_kernel(const f2g_conv32
       for (int g2 = 0; g2 < 2; ++g2)
 #pragma unroll
         for (int e = 0; e < 16; ++e)
-          red[((wave * 2 + g2) * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh) * 32 + li] = acc[2 * p2 + g2][e];
+          red[((wave * 2 + g2) * 32 + acc_row(e) + 4 * hh) * 32 + li] = acc[2 * p2 + g2][e];
       __syncthreads();                            // (phase 0: every wave is also done with this tile's patch)
       f32x4 s = *reinterpret_cast<const f32x4*>(red + (((wave >> 2)) * 32 + orow) * 32 + och);
 #pragma unroll
@@ -322,7 +323,7 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_dgrad6_kernel(const f2g_conv
       const int r = div_small<GWv>(px), xc = px - r * GWv;
       const int h = h0 - 1 + r, c = m0 - 2 + xc;
       const bool ok = px < IHv * GWv && h >= 0 && h < d.H && c >= 0 && c < d.Wout;
-      pf[q] = *reinterpret_cast<const f32x4*>(ok ? org + (r * xl + xc * C) : c6_zero);
+      pf[q] = *reinterpret_cast<const f32x4*>(ok ? org + (r * xl + xc * C) : c32_zero);
     }
   };
   auto store_patch = [&](const f32x4 (&pf)[NCHK]) {
@@ -417,9 +418,7 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_dgrad6_kernel(const f2g_conv
       }
       __builtin_amdgcn_sched_barrier(0);
       if (j < 6 || j < nk) {
-#define F2G_X6_ONE(I, J) acc[g4] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[u & 1][I], wf[j][J], acc[g4], 0, 0, 0);
-        F2G_X6_ONE(2, 0) F2G_X6_ONE(1, 1) F2G_X6_ONE(0, 2) F2G_X6_ONE(1, 0) F2G_X6_ONE(0, 1) F2G_X6_ONE(0, 0)
-#undef F2G_X6_ONE
+        mfma6(a[u & 1], wf[j], acc[g4]);
       }
       __builtin_amdgcn_sched_barrier(0);
     }
@@ -443,7 +442,7 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_dgrad6_kernel(const f2g_conv
       for (int g2 = 0; g2 < 2; ++g2)
 #pragma unroll
         for (int e = 0; e < 16; ++e)
-          red[((wave * 2 + g2) * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh) * 32 + li] = acc[2 * p2 + g2][e];
+          red[((wave * 2 + g2) * 32 + acc_row(e) + 4 * hh) * 32 + li] = acc[2 * p2 + g2][e];
       __syncthreads();                            // (phase 0: every wave is also done with this tile's patch)
       // ---- epilogue: optional leaky-ReLU backward of the layer below (+ feature-matching term), column sums.
       // Three separate paths, so that the plain and the mask path carry no wait of the path with two maps.
@@ -463,15 +462,11 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_dgrad6_kernel(const f2g_conv
         if (msk && !fm) {
           const float y[4] = {my[jj].x, my[jj].y, my[jj].z, my[jj].w};
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] *= y[e] > 0.f ? 1.f : d.mask_slope;
+          for (int e = 0; e < 4; ++e) v[e] = c32_mask_fm(v[e], y[e], false, [] { return 0.f; }, 0.f, d.mask_slope);
         } else if (msk) {
           const float y[4] = {my[jj].x, my[jj].y, my[jj].z, my[jj].w}, f[4] = {fv[i2].x, fv[i2].y, fv[i2].z, fv[i2].w};
 #pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            const float dl = y[e] - f[e];
-            v[e] += fmw * (dl > 0.f ? 1.f : (dl < 0.f ? -1.f : 0.f));
-            v[e] *= y[e] > 0.f ? 1.f : d.mask_slope;
-          }
+          for (int e = 0; e < 4; ++e) v[e] = c32_mask_fm(v[e], y[e], true, [&] { return f[e]; }, fmw, d.mask_slope);
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) cs[e] += v[e];
@@ -512,15 +507,12 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_dgrad6_kernel(const f2g_conv
 // w, w + 8, w + 16 over the whole tile and tile row w of taps 24..26.  77 + 25 KB of planes = one block per
 // CU, so the block requests the next tile's rows into registers before it computes the current one and
 // splits them chunk by chunk under the MFMAs of the tile's rows.
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 constexpr int GPL = 128 * 64;            // bytes of one plane of the gradient tile
 constexpr int GCH = 128 * (C / 4) / 512; // gradient chunks per thread: 2
 
-__device__ __forceinline__ bf16x8 tr_pix8(const unsigned char* p) {   // pixels +0..3 and +4..7
-  typedef s16x4 __attribute__((address_space(3))) * lds_p;
-  const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p + 4 * 64));
-  return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
+template <int TH, int TW>
+constexpr size_t wgrad6_smem() {   // three planes of the patch's two column parities and of the gradient tile
+  return (size_t)3 * 2 * ((TH + KH - 1) * (TW + (KW - 1) / 2) * 64 + 64) + 3 * GPL;
 }
 
 template <int TH, int TW>
@@ -592,7 +584,7 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_wgrad6_kernel(const f2g_conv
       const int r = div_small<XW>(px), xr = px - r * XW;
       const int h = h0 - 1 + r, x = x0 + xr;
       const bool ok = px < IH * XW && h >= 0 && h < d.H && x >= 0 && x < d.Win;
-      px_[q] = *reinterpret_cast<const f32x4*>(ok ? org + (long long)r * d.x_line + xr * C : c6_zero);
+      px_[q] = *reinterpret_cast<const f32x4*>(ok ? org + (long long)r * d.x_line + xr * C : c32_zero);
     }
     const float* gs = d.y + (long long)s * d.y_seq;
 #pragma unroll
@@ -600,20 +592,12 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_wgrad6_kernel(const f2g_conv
       const int px = (tid >> 3) + 64 * q;
       const int h = h0 + px / TW, w = w0 + px % TW;
       const bool ok = h < d.H && w < d.Wout;
-      pg_[q] = *reinterpret_cast<const f32x4*>(ok ? gs + (long long)h * d.y_line + (long long)w * C + c4 * 4 : c6_zero);
+      pg_[q] = *reinterpret_cast<const f32x4*>(ok ? gs + (long long)h * d.y_line + (long long)w * C + c4 * 4 : c32_zero);
     }
   };
   auto put3 = [&](unsigned char* base, int plane_bytes, int off, const u32x2 (&pk)[3]) {
 #pragma unroll
     for (int q = 0; q < 3; ++q) *reinterpret_cast<u32x2*>(base + q * plane_bytes + off) = pk[q];
-  };
-  auto mfma6 = [&](const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16& c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
   };
   const int t0 = blockIdx.x * tiles_per_block;
   int tend = t0 + tiles_per_block;
@@ -690,35 +674,8 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_wgrad6_kernel(const f2g_conv
     }
     __syncthreads();
   }
-  // ---- flush: taps owned by one wave go straight out; the three shared taps are summed over the
-  // waves through LDS first
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    const int t = wave + 8 * q;
-#pragma unroll
-    for (int e = 0; e < 16; ++e) {
-      const int co = (e & 3) + 8 * (e >> 2) + 4 * hh;
-      atomicAdd(gw + co * (NTAP * C) + t * C + li, acc[q][e]);
-    }
-  }
-  float* red = reinterpret_cast<float*>(smb);   // [8 waves][16][64]
-#pragma unroll
-  for (int q = 0; q < 3; ++q) {
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 16; ++e) red[(wave * 16 + e) * 64 + lane] = acc[3 + q][e];
-    __syncthreads();
-    if (wave == q) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        float v = 0.f;
-#pragma unroll
-        for (int w8 = 0; w8 < 8; ++w8) v += red[(w8 * 16 + e) * 64 + lane];
-        const int co = (e & 3) + 8 * (e >> 2) + 4 * hh;
-        atomicAdd(gw + co * (NTAP * C) + (24 + q) * C + li, v);
-      }
-    }
-  }
+  static_assert(wgrad6_smem<TH, TW>() >= (size_t)8 * 16 * 64 * 4, "the flush reuses the planes as its reduction buffer");
+  c32_wgrad_flush<NTAP, 3>(gw, reinterpret_cast<float*>(smb), acc, wave, lane, li, hh);
 }
 
 // ---- the fifth layer of a band stack: Conv2d(32, 32, (3, 3), padding (1, 1)), stride 1 (round 5) -------
@@ -771,7 +728,7 @@ __global__ __launch_bounds__(512, 1) void conv33_x6_kernel(const f2g_conv32_desc
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
       const int h = h0 - 1 + prow[q];
-      pf[q] = *reinterpret_cast<const f32x4*>((h >= 0 && h < d.H) ? org + poff[q] : c6_zero);
+      pf[q] = *reinterpret_cast<const f32x4*>((h >= 0 && h < d.H) ? org + poff[q] : c32_zero);
     }
   };
   auto store_patch = [&](const f32x4 (&pf)[NQ]) {
@@ -806,7 +763,7 @@ __global__ __launch_bounds__(512, 1) void conv33_x6_kernel(const f2g_conv32_desc
     if (d.mask_src) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int p = wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+        const int p = wave * 32 + acc_row(e) + 4 * hh;
         const int r = fast_div(p, W, mgW), c = p - r * W;
         my[e] = (p < tpx && h0 + r < d.H) ? d.mask_src[ybase + (long long)r * d.y_line + c * C + li] : 1.f;
       }
@@ -821,7 +778,7 @@ __global__ __launch_bounds__(512, 1) void conv33_x6_kernel(const f2g_conv32_desc
       float* ys = d.y + ybase;
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
-        const int p = wave * 32 + (e & 3) + 8 * (e >> 2) + 4 * hh;
+        const int p = wave * 32 + acc_row(e) + 4 * hh;
         const int r = fast_div(p, W, mgW), c = p - r * W;
         if (p < tpx && h0 + r < d.H) {
           float v = acc0[e] + acc1[e] + bias;
@@ -904,14 +861,6 @@ __global__ __launch_bounds__(512, 1) void conv33_wgrad6_kernel(const f2g_conv32_
   for (int t = 0; t < T33; ++t)
 #pragma unroll
     for (int e = 0; e < 16; ++e) acc[t][e] = 0.f;
-  auto mfma6 = [&](const bf16x8 (&a)[3], const bf16x8 (&b)[3], f32x16& c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[2], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], b[0], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[1], c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
-  };
   __syncthreads();
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const int sq = tile / tiles_h, h0 = (tile - sq * tiles_h) * R;
@@ -921,8 +870,8 @@ __global__ __launch_bounds__(512, 1) void conv33_wgrad6_kernel(const f2g_conv32_
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
       const int hx = h0 + xrow[q], hg = h0 + grow[q];
-      px_[q] = *reinterpret_cast<const f32x4*>((xrow[q] > -(1 << 20) && hx >= 0 && hx < d.H) ? xs + xoff[q] : c6_zero);
-      pg_[q] = *reinterpret_cast<const f32x4*>((grow[q] > -(1 << 20) && hg < d.H) ? gs + goff[q] : c6_zero);
+      px_[q] = *reinterpret_cast<const f32x4*>((xrow[q] > -(1 << 20) && hx >= 0 && hx < d.H) ? xs + xoff[q] : c32_zero);
+      pg_[q] = *reinterpret_cast<const f32x4*>((grow[q] > -(1 << 20) && hg < d.H) ? gs + goff[q] : c32_zero);
     }
 #pragma unroll
     for (int q = 0; q < NQ; ++q) {
@@ -954,25 +903,8 @@ __global__ __launch_bounds__(512, 1) void conv33_wgrad6_kernel(const f2g_conv32_
     }
     __syncthreads();   // every wave is done with this tile's planes
   }
-  // ---- flush: the waves' partial tap tiles are summed through LDS, one tap at a time
-  float* red = reinterpret_cast<float*>(smb);   // [8 waves][16][64]
-#pragma unroll
-  for (int t = 0; t < T33; ++t) {
-    __syncthreads();
-#pragma unroll
-    for (int e = 0; e < 16; ++e) red[(wave * 16 + e) * 64 + lane] = acc[t][e];
-    __syncthreads();
-    if (wave == (t & 7)) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        float v = 0.f;
-#pragma unroll
-        for (int w8 = 0; w8 < 8; ++w8) v += red[(w8 * 16 + e) * 64 + lane];
-        const int co = (e & 3) + 8 * (e >> 2) + 4 * hh;
-        atomicAdd(gw + co * (T33 * C) + t * C + li, v);
-      }
-    }
-  }
+  // every wave holds a partial tile of all nine taps: none is owned
+  c32_wgrad_flush<T33, 0>(gw, reinterpret_cast<float*>(smb), acc, wave, lane, li, hh);
 }
 
 template <int TH_, int TW_>
@@ -988,89 +920,34 @@ constexpr size_t dgrad6_smem() {
 
 // precision-3 launchers, called from conv32.hip's entry points (arguments already checked there)
 int f2g_conv32_fwd6_launch(const f2g_conv32_desc* d, hipStream_t st) {
-  auto waste = [&](int th, int tw) {
-    return (long long)((d->H + th - 1) / th * th) * ((d->Wout + tw - 1) / tw * tw);
-  };
-  const bool tall = waste(16, 8) < waste(8, 16);
-  const int th = tall ? 16 : 8, tw = tall ? 8 : 16;
-  const int tiles_h = (d->H + th - 1) / th, tiles_w = (d->Wout + tw - 1) / tw;
-  const long long nt = (long long)tiles_h * tiles_w * d->S;
+  const c32_tiling t = c32_pick_tiles(d->H, d->Wout);
+  const long long nt = (long long)t.tiles_h * t.tiles_w * d->S;
   if (nt >= (1ll << 30) || d->x_line >= (1ll << 24)) return F2G_EINVAL;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_fwd6_kernel<8, 16>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fwd6_smem<8, 16>()));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_fwd6_kernel<16, 8>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(fwd6_smem<16, 8>()));
-    attr = true;
-  }
   const int grid = (int)(nt < 256 ? nt : 256);          // one resident block per CU
-  if (tall)
-    hipLaunchKernelGGL((conv32_s2_fwd6_kernel<16, 8>), dim3(grid), dim3(512), (fwd6_smem<16, 8>()), st, *d,
-                       tiles_w, tiles_h, (int)nt);
-  else
-    hipLaunchKernelGGL((conv32_s2_fwd6_kernel<8, 16>), dim3(grid), dim3(512), (fwd6_smem<8, 16>()), st, *d,
-                       tiles_w, tiles_h, (int)nt);
-  return f2g_check_launch();
+  return c32_launch_shape<conv32_s2_fwd6_kernel<8, 16>, conv32_s2_fwd6_kernel<16, 8>>(
+      t.tall, fwd6_smem<8, 16>(), fwd6_smem<16, 8>(), dim3(grid), dim3(512), st, *d, t.tiles_w, t.tiles_h, (int)nt);
 }
 
 int f2g_conv32_dgrad6_launch(const f2g_conv32_desc* d, hipStream_t st) {
-  const int Wp0 = (d->Win + 1) / 2;                     // positions m: the even parity has the most
-  auto waste = [&](int th, int tw) {
-    return (long long)((d->H + th - 1) / th * th) * ((Wp0 + tw - 1) / tw * tw);
-  };
-  const bool tall = waste(16, 8) < waste(8, 16);
-  const int th = tall ? 16 : 8, tw = tall ? 8 : 16;
-  const int tiles_h = (d->H + th - 1) / th, tiles_w = (Wp0 + tw - 1) / tw;
-  const long long nt = (long long)tiles_h * tiles_w * d->S;
+  const c32_tiling t = c32_pick_tiles(d->H, (d->Win + 1) / 2);   // positions m: the even parity has the most
+  const long long nt = (long long)t.tiles_h * t.tiles_w * d->S;
   if (nt >= (1ll << 30) || d->x_line >= (1ll << 24) || d->y_line >= (1ll << 24)) return F2G_EINVAL;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_dgrad6_kernel<8, 16>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(dgrad6_smem<8, 16>()));
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_dgrad6_kernel<16, 8>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)(dgrad6_smem<16, 8>()));
-    attr = true;
-  }
   const int grid = (int)(nt < 256 ? nt : 256);
-  if (tall)
-    hipLaunchKernelGGL((conv32_s2_dgrad6_kernel<16, 8>), dim3(grid), dim3(512), (dgrad6_smem<16, 8>()), st, *d,
-                       tiles_w, tiles_h, (int)nt);
-  else
-    hipLaunchKernelGGL((conv32_s2_dgrad6_kernel<8, 16>), dim3(grid), dim3(512), (dgrad6_smem<8, 16>()), st, *d,
-                       tiles_w, tiles_h, (int)nt);
-  return f2g_check_launch();
+  return c32_launch_shape<conv32_s2_dgrad6_kernel<8, 16>, conv32_s2_dgrad6_kernel<16, 8>>(
+      t.tall, dgrad6_smem<8, 16>(), dgrad6_smem<16, 8>(), dim3(grid), dim3(512), st, *d, t.tiles_w, t.tiles_h,
+      (int)nt);
 }
 
 int f2g_conv32_wgrad6_launch(const f2g_conv32_desc* d, float* gw, hipStream_t st) {
-  auto waste = [&](int th, int tw) {
-    return (long long)((d->H + th - 1) / th * th) * ((d->Wout + tw - 1) / tw * tw);
-  };
-  const bool tall = waste(16, 8) < waste(8, 16);
-  const int th = tall ? 16 : 8, tw = tall ? 8 : 16;
-  const int tiles_h = (d->H + th - 1) / th, tiles_w = (d->Wout + tw - 1) / tw;
-  const long long nt = (long long)d->S * tiles_h * tiles_w;
+  const c32_tiling t = c32_pick_tiles(d->H, d->Wout);
+  const long long nt = (long long)d->S * t.tiles_h * t.tiles_w;
   if (nt >= (1ll << 30) || d->x_line >= (1ll << 24)) return F2G_EINVAL;
   int per = (int)((nt + 255) / 256);        // <= 256 blocks (one per CU): bounds the atomics
   if (per < 1) per = 1;
-  constexpr size_t sm8 = (size_t)3 * 2 * ((8 + 2) * (16 + 4) * 64 + 64) + 3 * GPL;
-  constexpr size_t sm16 = (size_t)3 * 2 * ((16 + 2) * (8 + 4) * 64 + 64) + 3 * GPL;
-  static_assert(sm8 >= (size_t)8 * 16 * 64 * 4 && sm16 >= (size_t)8 * 16 * 64 * 4,
-                "the flush reuses the planes as its reduction buffer");
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_wgrad6_kernel<8, 16>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm8);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv32_s2_wgrad6_kernel<16, 8>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)sm16);
-    attr = true;
-  }
   const unsigned grid = (unsigned)((nt + per - 1) / per);
-  if (tall)
-    hipLaunchKernelGGL((conv32_s2_wgrad6_kernel<16, 8>), dim3(grid), dim3(512), sm16, st, *d, gw, tiles_h, tiles_w, per);
-  else
-    hipLaunchKernelGGL((conv32_s2_wgrad6_kernel<8, 16>), dim3(grid), dim3(512), sm8, st, *d, gw, tiles_h, tiles_w, per);
-  return f2g_check_launch();
+  return c32_launch_shape<conv32_s2_wgrad6_kernel<8, 16>, conv32_s2_wgrad6_kernel<16, 8>>(
+      t.tall, wgrad6_smem<8, 16>(), wgrad6_smem<16, 8>(), dim3(grid), dim3(512), st, *d, gw, t.tiles_h, t.tiles_w,
+      per);
 }
 
 // Conv2d(32, 32, (3, 3), padding (1, 1)) + bias + leaky ReLU, fp32 class (include/flow2gan_hip.h)
@@ -1096,12 +973,7 @@ extern "C" int f2g_conv33_fwd(const f2g_conv32_desc* d, f2g_stream_t stream) {
   const long long nt = (long long)tiles_h * d->S;
   if (nt >= (1ll << 30)) return F2G_EINVAL;
   constexpr size_t smem = (size_t)P33 * PB + (size_t)T33 * C * PB;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv33_x6_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr = true;
-  }
+  c32_lds_once<conv33_x6_kernel>(smem);
   const int grid = (int)(nt < 256 ? nt : 256);          // one resident block per CU
   hipLaunchKernelGGL(conv33_x6_kernel, dim3(grid), dim3(512), smem, (hipStream_t)stream, *d, R, tiles_h, (int)nt);
   return f2g_check_launch();
@@ -1130,12 +1002,7 @@ extern "C" int f2g_conv33_wgrad(const f2g_conv32_desc* d, float* gw, f2g_stream_
   static_assert(smem >= (size_t)8 * 16 * 64 * 4, "the flush reuses the planes as its reduction buffer");
   // (largest input position a fragment touches: (R + 2) * (W + 2) + 17; gradient positions: R * (W + 2) + 15)
   static_assert(P33 + 18 <= W33_XP && P33 <= W33_GP, "plane sizes");
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(conv33_wgrad6_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-    attr = true;
-  }
+  c32_lds_once<conv33_wgrad6_kernel>(smem);
   const int grid = (int)(nt < 256 ? nt : 256);          // one resident block per CU: 256 x 9216 atomics at most
   hipLaunchKernelGGL(conv33_wgrad6_kernel, dim3(grid), dim3(512), smem, (hipStream_t)stream, *d, gw, R, tiles_h,
                      (int)nt);

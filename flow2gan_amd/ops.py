@@ -1086,28 +1086,40 @@ def x3_image(t2d):
     return derived(t2d, "x3img", build) if _is_const(t2d) else build(t2d)
 
 
+def _timed_conv(name, flops, shape, *args):
+    """A direct band-conv launch, through GEMM_TIMER (bench.py's FLOP table: flops, (form, M, N, K)) when one is set."""
+    if GEMM_TIMER is not None:
+        GEMM_TIMER.time(lambda: call(name, *args), flops, shape)
+    else:
+        call(name, *args)
+
+
+def _conv32_operand(d, w, rows_k=None):
+    """Sets d.precision from the GEMM mode and returns the image of the (3, 9) layer's weights w that the kernels
+    of that precision read: the f2g_split_bf16 image (1), the three-piece image of w as a (rows, K) = rows_k matrix
+    (3: fp32-class products on the bf16 pipe, conv32x6.hip) or w itself (0, exact fp32).  w = None (weight
+    gradient): the precision alone."""
+    img = w
+    if GEMM_PRECISION == 1:
+        d.precision = 1
+        img = derived(w, "split", split_bf16) if w is not None else None
+    elif GEMM_PRECISION == 3 and CONV32_X6:
+        d.precision = 3
+        img = x3_image(w.view(rows_k) if rows_k else w) if w is not None else None
+    if img is not w:
+        d._keep = img
+    return img
+
+
 def conv32_s2_fwd(x, S: int, H: int, Win: int, Wout: int, w_packed, bias, slope: float, y):
     """Conv2d(32, 32, (3, 9), stride (1, 2), padding (1, 4)) + bias + leaky ReLU on channels-last
     images x (S*H*Win, 32) -> y (S*H*Wout, 32); w_packed = (32, 27*32) as pack_conv_weight gives."""
     d = L.Conv32Desc()
     d.x, d.x_seq, d.x_line = ptr(x), H * Win * 32, Win * 32
     d.S, d.H, d.Win, d.Wout = S, H, Win, Wout
-    if GEMM_PRECISION == 1:
-        w_packed = derived(w_packed, "split", split_bf16)
-        d.precision = 1
-        d._keep = w_packed
-    elif GEMM_PRECISION == 3 and CONV32_X6:
-        # fp32-class products on the bf16 pipe (conv32x6.hip): three-piece image of the packed weights
-        w_packed = x3_image(w_packed)
-        d.precision = 3
-        d._keep = w_packed
-    d.w, d.bias, d.lrelu_slope = ptr(w_packed), ptr(bias), slope
+    d.w, d.bias, d.lrelu_slope = ptr(_conv32_operand(d, w_packed)), ptr(bias), slope
     d.y, d.y_seq, d.y_line = ptr(y), H * Wout * 32, Wout * 32
-    if GEMM_TIMER is not None:
-        GEMM_TIMER.time(lambda: call("f2g_conv32_s2_fwd", C.byref(d)),
-                        2.0 * S * H * Wout * 32 * 27 * 32, (0, S * H * Wout, 32, 27 * 32))
-    else:
-        call("f2g_conv32_s2_fwd", C.byref(d))
+    _timed_conv("f2g_conv32_s2_fwd", 2.0 * S * H * Wout * 32 * 27 * 32, (0, S * H * Wout, 32, 27 * 32), C.byref(d))
     return y
 
 
@@ -1136,11 +1148,7 @@ def conv33(x, S: int, H: int, W: int, w_packed, bias, slope: float, y, x_off: in
         d.mask_src = ptr(mask[0]) + 4 * mask[1]
         d.mask_slope = float(mask[2])
     d.colsum = ptr(colsum)
-    if GEMM_TIMER is not None:
-        GEMM_TIMER.time(lambda: call("f2g_conv33_fwd", C.byref(d)),
-                        2.0 * S * H * W * 32 * 9 * 32, (form, S * H * W, 32, 9 * 32))
-    else:
-        call("f2g_conv33_fwd", C.byref(d))
+    _timed_conv("f2g_conv33_fwd", 2.0 * S * H * W * 32 * 9 * 32, (form, S * H * W, 32, 9 * 32), C.byref(d))
     return y
 
 
@@ -1155,11 +1163,7 @@ def conv33_wgrad(x, g, S: int, H: int, W: int, gw, g_off: int = 0, g_line=None, 
     d.y = ptr(g) + 4 * g_off
     d.y_line = g_line if g_line is not None else W * 32
     d.y_seq = g_seq if g_seq is not None else H * d.y_line
-    if GEMM_TIMER is not None:
-        GEMM_TIMER.time(lambda: call("f2g_conv33_wgrad", C.byref(d), ptr(gw)),
-                        2.0 * S * H * W * 32 * 9 * 32, (2, 32, 9 * 32, S * H * W))
-    else:
-        call("f2g_conv33_wgrad", C.byref(d), ptr(gw))
+    _timed_conv("f2g_conv33_wgrad", 2.0 * S * H * W * 32 * 9 * 32, (2, 32, 9 * 32, S * H * W), C.byref(d), ptr(gw))
     return gw
 
 
@@ -1172,14 +1176,7 @@ def conv32_s2_dgrad(g, S: int, H: int, Win: int, Wout: int, wT, gx, g_seq=None, 
     d.x_line = g_line if g_line is not None else Wout * 32
     d.x_seq = g_seq if g_seq is not None else H * d.x_line
     d.S, d.H, d.Win, d.Wout = S, H, Win, Wout
-    if GEMM_PRECISION == 1:
-        wT = derived(wT, "split", split_bf16)
-        d.precision = 1
-        d._keep = wT
-    elif GEMM_PRECISION == 3 and CONV32_X6:
-        wT = x3_image(wT.view(27 * 32, 32))      # rows (tap, ci), reduction over co
-        d.precision = 3
-        d._keep = wT
+    wT = _conv32_operand(d, wT, (27 * 32, 32))      # three-piece image: rows (tap, ci), reduction over co
     d.w, d.bias, d.lrelu_slope = ptr(wT), None, 0.0
     d.y, d.y_seq, d.y_line = ptr(gx), H * Win * 32, Win * 32
     if mask is not None:      # leaky-ReLU backward of the layer below fused into the store
@@ -1188,11 +1185,8 @@ def conv32_s2_dgrad(g, S: int, H: int, Win: int, Wout: int, wT, gx, g_seq=None, 
         if fm is not None:
             d.fm_ref, d.fm_w, d.fm_wdev = ptr(fm[0]) + 4 * fm[1], float(fm[2]), ptr(fm[3])
     d.colsum = ptr(colsum)
-    if GEMM_TIMER is not None:
-        GEMM_TIMER.time(lambda: call("f2g_conv32_s2_dgrad", C.byref(d)),
-                        2.0 * S * H * Wout * 32 * 27 * 32, (1, S * H * Win, 32, 27 * 32 // 2))
-    else:
-        call("f2g_conv32_s2_dgrad", C.byref(d))
+    _timed_conv("f2g_conv32_s2_dgrad", 2.0 * S * H * Wout * 32 * 27 * 32, (1, S * H * Win, 32, 27 * 32 // 2),
+                C.byref(d))
     return gx
 
 
@@ -1204,15 +1198,9 @@ def conv32_s2_wgrad(x, g, S: int, H: int, Win: int, Wout: int, gw):
     d.S, d.H, d.Win, d.Wout = S, H, Win, Wout
     d.w, d.bias, d.lrelu_slope = None, None, 0.0
     d.y, d.y_seq, d.y_line = ptr(g), H * Wout * 32, Wout * 32
-    if GEMM_PRECISION == 1:
-        d.precision = 1
-    elif GEMM_PRECISION == 3 and CONV32_X6:
-        d.precision = 3
-    if GEMM_TIMER is not None:
-        GEMM_TIMER.time(lambda: call("f2g_conv32_s2_wgrad", C.byref(d), ptr(gw)),
-                        2.0 * S * H * Wout * 32 * 27 * 32, (2, 32, 27 * 32, S * H * Wout))
-    else:
-        call("f2g_conv32_s2_wgrad", C.byref(d), ptr(gw))
+    _conv32_operand(d, None)
+    _timed_conv("f2g_conv32_s2_wgrad", 2.0 * S * H * Wout * 32 * 27 * 32, (2, 32, 27 * 32, S * H * Wout),
+                C.byref(d), ptr(gw))
     return gw
 
 

@@ -723,8 +723,9 @@ typedef struct {
   const float* w;
   const float* bias;  /* may be NULL */
   float lrelu_slope;  /* 0 = none */
-  /* fwd / dgrad: 0 = exact fp32 MFMA; 1 = split-bf16 (hi*hi + hi*lo + lo*hi, fp32 accumulation):
-   * `w` is then the f2g_split_bf16 image of the same weight matrix, the patch is split while it
+  /* fwd / dgrad: 0 = exact fp32 MFMA (persistent kernels with 32-bit row offsets: x_line < 2^24 floats and
+   * fewer than 2^30 tiles of 128 pixels, F2G_EINVAL otherwise, wgrad included -- precision 3 has the same
+   * limits); 1 = split-bf16 (hi*hi + hi*lo + lo*hi, fp32 accumulation): `w` is then the f2g_split_bf16 image of the same weight matrix, the patch is split while it
    * is staged in LDS; wgrad splits both staged operands (bf16 planes read with
    * ds_read_b64_tr_b16: its reduction runs over pixels).
    * 3 = fp32-CLASS products on the bf16 pipe (three bf16 pieces per value, six MFMAs per product, error

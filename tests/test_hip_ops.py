@@ -1160,6 +1160,34 @@ def test_direct_conv32_wgrad_matches_autograd(ops, S, H, Win):
     close(gw, w.grad.permute(0, 2, 3, 1).reshape(32, 27 * 32), rtol=1e-4, name="conv32 wgrad")
 
 
+@pytest.mark.parametrize("entry", ["f2g_conv32_s2_fwd", "f2g_conv32_s2_dgrad", "f2g_conv32_s2_wgrad"])
+def test_direct_conv32_exact_fp32_refuses_long_lines(ops, entry):
+    """conv32.hip: the exact-fp32 kernels address a map's rows with 32-bit offsets, so a precision-0 descriptor
+    whose x_line reaches 2^24 floats is refused (F2G_EINVAL, f2g_last_error names the limit) before anything is
+    launched: the output keeps its fill value."""
+    import ctypes as C
+    from flow2gan_amd import _lib as L
+    x, w = torch.zeros(64, device=DEV), torch.zeros(27 * 32 * 32, device=DEV)
+    out = torch.full((32 * 27 * 32,), 7.0, device=DEV)     # large enough for y, gx and gw of one pixel
+    d = L.Conv32Desc()
+    d.x, d.x_seq, d.x_line = L.ptr(x), 1 << 24, 1 << 24
+    d.S, d.H, d.Win, d.Wout = 1, 1, 2, 1
+    d.precision = 0
+    d.y, d.y_seq, d.y_line = L.ptr(out), 64, 64
+    args = [C.byref(d)]
+    if entry == "f2g_conv32_s2_wgrad":
+        d.y = L.ptr(x)                                      # (the gradient operand; gw is the output)
+        args.append(L.ptr(out))
+    else:
+        d.w = L.ptr(w)
+    with pytest.raises(L.F2GError):
+        L.call(entry, *args)
+    msg = L.lib.f2g_last_error().decode()
+    assert entry in msg and "2^24" in msg, msg
+    torch.cuda.synchronize()
+    assert bool((out == 7.0).all())
+
+
 @pytest.mark.parametrize("C,rows", [(768, 200), (512, 300), (384, 128 * 3), (512, 31)])
 def test_fused_mlp_matches_the_two_gemm_arithmetic(ops, C, rows):
     """csrc/fusedmlp.hip against a torch fp32 restatement of the same arithmetic (bf16 operands,
