@@ -901,6 +901,9 @@ __global__ __launch_bounds__(512, 2) void conv32_s2_wgrad3_kernel(const f2g_conv
 int f2g_conv32_fwd6_launch(const f2g_conv32_desc* d, hipStream_t st);
 int f2g_conv32_dgrad6_launch(const f2g_conv32_desc* d, hipStream_t st);
 int f2g_conv32_wgrad6_launch(const f2g_conv32_desc* d, float* gw, hipStream_t st);
+// precision 4 (fp16x3 products, the patch scaled per tile inside the kernel): conv32h3.hip
+int f2g_conv32_fwd3h_launch(const f2g_conv32_desc* d, hipStream_t st);
+int f2g_conv32_dgrad3h_launch(const f2g_conv32_desc* d, hipStream_t st);
 
 
 namespace {
@@ -923,12 +926,14 @@ extern "C" int f2g_conv32_s2_fwd(const f2g_conv32_desc* d, f2g_stream_t stream) 
   if (!d || !d->x || !d->w || !d->y) return F2G_EINVAL;
   if (d->S <= 0 || d->H <= 0 || d->Wout <= 0) return F2G_OK;
   if (d->Wout != (d->Win + 8 - 9) / 2 + 1) return F2G_EINVAL;
-  if (d->precision != 0 && d->precision != 1 && d->precision != 3) return F2G_EINVAL;
+  if (d->precision != 0 && d->precision != 1 && d->precision != 3 && d->precision != 4) return F2G_EINVAL;
   auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
   if (!al(d->x) || !al(d->w) || (d->x_line & 3) || (d->x_seq & 3)) return F2G_EINVAL;
-  if (d->precision == 3) {   // w = f2g_split_bf16x3 image; the output leaves as 16-byte row segments
+  if (d->precision >= 3) {   // w = f2g_split_bf16x3 image (3) / the one-run f2g_split_f16x2_seq image and its
+                             // reciprocal scale (4); the output leaves as 16-byte row segments
     if (!al(d->y) || (d->y_line & 3) || (d->y_seq & 3)) return F2G_EINVAL;
-    return f2g_conv32_fwd6_launch(d, (hipStream_t)stream);
+    return d->precision == 3 ? f2g_conv32_fwd6_launch(d, (hipStream_t)stream)
+                             : f2g_conv32_fwd3h_launch(d, (hipStream_t)stream);
   }
   if (d->precision == 1) {   // w = the f2g_split_bf16 image of the packed weights
     const int tiles = ((d->H + TH - 1) / TH) * ((d->Wout + TW - 1) / TW);
@@ -951,10 +956,12 @@ extern "C" int f2g_conv32_s2_dgrad(const f2g_conv32_desc* d, f2g_stream_t stream
   if (d->Wout != (d->Win + 8 - 9) / 2 + 1) return F2G_EINVAL;
   auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
   if (!al(d->x) || !al(d->w) || (d->x_line & 3) || (d->x_seq & 3)) return F2G_EINVAL;
-  if (d->precision != 0 && d->precision != 1 && d->precision != 3) return F2G_EINVAL;
-  if (d->precision == 3) {   // w = image of wT (864 x 32); output, mask and reference map as 16-byte row segments
+  if (d->precision != 0 && d->precision != 1 && d->precision != 3 && d->precision != 4) return F2G_EINVAL;
+  if (d->precision >= 3) {   // w = image of wT (864 x 32; 3: three bf16 pieces, 4: two scaled fp16 pieces and the
+                             // reciprocal scale); output, mask and reference map as 16-byte row segments
     if (!al(d->y) || (d->y_line & 3) || (d->y_seq & 3) || !al(d->mask_src) || !al(d->fm_ref)) return F2G_EINVAL;
-    return f2g_conv32_dgrad6_launch(d, (hipStream_t)stream);
+    return d->precision == 3 ? f2g_conv32_dgrad6_launch(d, (hipStream_t)stream)
+                             : f2g_conv32_dgrad3h_launch(d, (hipStream_t)stream);
   }
   if (d->precision == 1) {   // w = the f2g_split_bf16 image of the transposed tiles
     const int tiles = ((d->H + TH - 1) / TH) * (((d->Win + 1) / 2 + TW - 1) / TW);
@@ -979,6 +986,7 @@ extern "C" int f2g_conv32_s2_wgrad(const f2g_conv32_desc* d, float* gw, f2g_stre
   auto al = [](const void* p) { return (((uintptr_t)p) & 15) == 0; };
   if (!al(d->x) || !al(d->y) || (d->x_line & 3) || (d->x_seq & 3) || (d->y_line & 3) || (d->y_seq & 3))
     return F2G_EINVAL;
+  if (d->precision != 0 && d->precision != 1 && d->precision != 3) return F2G_EINVAL;   // (4: forward and data gradient only)
   if (d->precision == 3) return f2g_conv32_wgrad6_launch(d, gw, (hipStream_t)stream);   // operands split while staged
   if (d->precision == 1) {   // split-bf16 (the operands are split while they are staged)
     const int tiles_h = (d->H + TH - 1) / TH, tiles_w = (d->Wout + TW - 1) / TW;

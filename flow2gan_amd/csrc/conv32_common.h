@@ -1,7 +1,8 @@
-// What the direct MRD band convolutions share (conv32.hip: exact fp32 and split-bf16; conv32x6.hip: fp32 class):
-// the vector types and layer constants, the accumulator-row map, the transposed fragment read of the weight
-// gradients, the pick between the two tile shapes and their launch, the store expression of the data gradients and
-// the flush of the weight gradients.  What a kernel stages and how it walks its taps stay with the kernel.
+// What the direct MRD band convolutions share (conv32.hip: exact fp32 and split-bf16; conv32x6.hip: fp32 class;
+// conv32h3.hip: fp16x3): the vector types and layer constants, the accumulator-row map, the map from MFMA rows to
+// tile pixels and the small divisions of the kernels that stage split pixels, the transposed fragment read of the
+// weight gradients, the pick between the two tile shapes and their launch, the store expression of the data
+// gradients and the flush of the weight gradients.  What a kernel stages and how it walks its taps stay with the kernel.
 // Internal linkage throughout.
 #pragma once
 #include "common.h"
@@ -29,6 +30,35 @@ __device__ __forceinline__ bf16x8 tr_pix8(const unsigned char* p) {
   const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p));
   const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p + 4 * 64));
   return __builtin_bit_cast(bf16x8, __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7));
+}
+
+// x / D for 0 <= x < 512 and the staged widths that occur (39, 23: forward patch columns; 20, 12: gradient patch)
+template <int D>
+__device__ __forceinline__ int div_small(int x) {
+  static_assert(D == 39 || D == 23 || D == 20 || D == 12, "magic constants below");
+  return (x * (D == 39 ? 1681 : D == 23 ? 2850 : D == 20 ? 3277 : 5462)) >> 16;
+}
+
+// MFMA row r (0..31) of pixel group pg -> pixel (row, column) of a TH x TW tile of the kernels that stage split
+// pixels (conv32x6.hip: 208-byte pixels, 52 dwords; conv32h3.hip: 144-byte pixels, 36 dwords).  16-wide tiles: the
+// wave's rows 16..31 are the next tile row, whose staged pixels sit (IW - 16) * 52 = 16 (mod 64) dwords further than
+// "16 lanes on" -- in ds_read_b128's lane groups {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} that puts four
+// lanes of the second row on the banks of the first (measured: 31 % of the LDS cycles were conflicts).
+// Rotating the second row's columns by 12 makes every group's sixteen 16-byte reads hit distinct banks.
+// (36-dword pixels: (IW - 16) * 36 = 16 (mod 64) as well, and 36 / 4 = 9 is odd like 52 / 4 = 13, so sixteen
+// consecutive columns cover the sixteen 16-byte bank groups once: the same rotation serves both pitches.
+// Enumerated over those lane groups, 8-wide tiles keep a two-way overlap at either pitch: their rows are 12 pixels
+// apart, so lanes 12-15 land on the banks of lanes 0-3; no rotation is applied there.)
+template <int TW_>
+__device__ __forceinline__ void px_of_row(int pg, int r, int& ph, int& pw) {
+  if (TW_ == 16) {
+    ph = 2 * pg + (r >> 4);
+    pw = (r + 12 * (r >> 4)) & 15;
+  } else {
+    const int p = pg * 32 + r;
+    ph = p / TW_;
+    pw = p % TW_;
+  }
 }
 
 // ---- tile shape: 8 x 16 or 16 x 8 output pixels, whichever wastes fewer pixels of the map, 8 x 16 on a tie.

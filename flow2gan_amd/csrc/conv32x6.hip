@@ -83,30 +83,6 @@ __device__ __forceinline__ void mfma6(const bf16x8 (&a)[3], const bf16x8 (&b)[3]
   c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], b[0], c, 0, 0, 0);
 }
 
-// x / D for 0 <= x < 512 and the staged widths that occur (39, 23: forward patch columns; 20, 12: gradient patch)
-template <int D>
-__device__ __forceinline__ int div_small(int x) {
-  static_assert(D == 39 || D == 23 || D == 20 || D == 12, "magic constants below");
-  return (x * (D == 39 ? 1681 : D == 23 ? 2850 : D == 20 ? 3277 : 5462)) >> 16;
-}
-
-// MFMA row r (0..31) of pixel group pg -> pixel (row, column) of a TH x TW tile.  16-wide tiles: the wave's
-// rows 16..31 are the next tile row, whose staged pixels sit (IW - 16) * 52 = 16 (mod 64) dwords further than
-// "16 lanes on" -- in ds_read_b128's lane groups {0-3, 12-15, 20-27} / {4-11, 16-19, 28-31} that puts four
-// lanes of the second row on the banks of the first (measured: 31 % of the LDS cycles were conflicts).
-// Rotating the second row's columns by 12 makes every group's sixteen 16-byte reads hit distinct banks.
-template <int TW_>
-__device__ __forceinline__ void px_of_row(int pg, int r, int& ph, int& pw) {
-  if (TW_ == 16) {
-    ph = 2 * pg + (r >> 4);
-    pw = (r + 12 * (r >> 4)) & 15;
-  } else {
-    const int p = pg * 32 + r;
-    ph = p / TW_;
-    pw = p % TW_;
-  }
-}
-
 // ---- forward ----------------------------------------------------------------------------------------
 // The reduction of a tile is 54 k steps of 16 (27 taps x the two halves of the input channels), split over
 // the block's 8 waves: waves 0..5 take seven consecutive k steps, waves 6 and 7 six.  A wave loads the B

@@ -1094,18 +1094,41 @@ def _timed_conv(name, flops, shape, *args):
         call(name, *args)
 
 
-def _conv32_operand(d, w, rows_k=None):
+# F2G_GEMM=fp16x3: the (3, 9) band layers' forward / data gradient on the fp16x3 kernels that scale every tile's patch
+# inside the kernel (conv32h3.hip, f2g_conv32_desc.precision = 4).  Off by default: the weight gradient, the (3, 3)
+# layer and the first layer stay on their precision-3 kernels either way (tests and tools/conv32_probe.py flip them)
+FP16X3_CONV32_FWD = opt("fp16x3_conv32_fwd", False)
+FP16X3_CONV32_DGRAD = opt("fp16x3_conv32_dgrad", False)
+FP16X3_CONV32_FWD_LAUNCHES = 0      # launches conv32_s2_fwd3h_kernel took (tests and tools)
+FP16X3_CONV32_DGRAD_LAUNCHES = 0    # launches conv32_s2_dgrad3h_kernel took
+
+
+def conv32_f16_image(w):
+    """The image the precision-4 band convolutions read: ONE f2g_split_f16x2_seq run over the whole contiguous
+    weight matrix (27648 floats) with its reciprocal scale behind it (cached for weights and cached re-layouts of
+    weights, as _f16_seq_operand's)."""
+    n = w.numel()
+    tag = ("f16x2seq", 0, 1, n, n)
+    return derived(w, tag, lambda t: split_f16_seq(t, 1, n)) if _is_const(w) else split_f16_seq(w, 1, n)
+
+
+def _conv32_operand(d, w, rows_k=None, h3: bool = False):
     """Sets d.precision from the GEMM mode and returns the image of the (3, 9) layer's weights w that the kernels
     of that precision read: the f2g_split_bf16 image (1), the three-piece image of w as a (rows, K) = rows_k matrix
-    (3: fp32-class products on the bf16 pipe, conv32x6.hip) or w itself (0, exact fp32).  w = None (weight
-    gradient): the precision alone."""
+    (3: fp32-class products on the bf16 pipe, conv32x6.hip), the one-run two-piece fp16 image (4: h3 = the call's
+    fp16x3 tunable, in the fp16x3 mode; conv32h3.hip) or w itself (0, exact fp32).  w = None (weight gradient): the
+    precision alone."""
     img = w
     if GEMM_PRECISION == 1:
         d.precision = 1
         img = derived(w, "split", split_bf16) if w is not None else None
     elif GEMM_PRECISION == 3 and CONV32_X6:
-        d.precision = 3
-        img = x3_image(w.view(rows_k) if rows_k else w) if w is not None else None
+        if h3 and FP16X3 and w is not None:
+            d.precision = 4
+            img = conv32_f16_image(w)
+        else:
+            d.precision = 3
+            img = x3_image(w.view(rows_k) if rows_k else w) if w is not None else None
     if img is not w:
         d._keep = img
     return img
@@ -1114,10 +1137,12 @@ def _conv32_operand(d, w, rows_k=None):
 def conv32_s2_fwd(x, S: int, H: int, Win: int, Wout: int, w_packed, bias, slope: float, y):
     """Conv2d(32, 32, (3, 9), stride (1, 2), padding (1, 4)) + bias + leaky ReLU on channels-last
     images x (S*H*Win, 32) -> y (S*H*Wout, 32); w_packed = (32, 27*32) as pack_conv_weight gives."""
+    global FP16X3_CONV32_FWD_LAUNCHES
     d = L.Conv32Desc()
     d.x, d.x_seq, d.x_line = ptr(x), H * Win * 32, Win * 32
     d.S, d.H, d.Win, d.Wout = S, H, Win, Wout
-    d.w, d.bias, d.lrelu_slope = ptr(_conv32_operand(d, w_packed)), ptr(bias), slope
+    d.w, d.bias, d.lrelu_slope = ptr(_conv32_operand(d, w_packed, h3=FP16X3_CONV32_FWD)), ptr(bias), slope
+    FP16X3_CONV32_FWD_LAUNCHES += d.precision == 4
     d.y, d.y_seq, d.y_line = ptr(y), H * Wout * 32, Wout * 32
     _timed_conv("f2g_conv32_s2_fwd", 2.0 * S * H * Wout * 32 * 27 * 32, (0, S * H * Wout, 32, 27 * 32), C.byref(d))
     return y
@@ -1171,12 +1196,14 @@ def conv32_s2_dgrad(g, S: int, H: int, Win: int, Wout: int, wT, gx, g_seq=None, 
                     g_off: int = 0, mask=None, fm=None, colsum=None):
     """Data gradient of Conv2d(32, 32, (3, 9), stride (1, 2), padding (1, 4)): g (S, H, Wout, 32)
     (optionally strided / offset) -> gx (S*H*Win, 32); wT = (27, 32, 32) tiles [tap][ci][co]."""
+    global FP16X3_CONV32_DGRAD_LAUNCHES
     d = L.Conv32Desc()
     d.x = ptr(g) + 4 * g_off
     d.x_line = g_line if g_line is not None else Wout * 32
     d.x_seq = g_seq if g_seq is not None else H * d.x_line
     d.S, d.H, d.Win, d.Wout = S, H, Win, Wout
-    wT = _conv32_operand(d, wT, (27 * 32, 32))      # three-piece image: rows (tap, ci), reduction over co
+    wT = _conv32_operand(d, wT, (27 * 32, 32), h3=FP16X3_CONV32_DGRAD)   # image rows (tap, ci), reduction over co
+    FP16X3_CONV32_DGRAD_LAUNCHES += d.precision == 4
     d.w, d.bias, d.lrelu_slope = ptr(wT), None, 0.0
     d.y, d.y_seq, d.y_line = ptr(gx), H * Win * 32, Win * 32
     if mask is not None:      # leaky-ReLU backward of the layer below fused into the store

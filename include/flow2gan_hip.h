@@ -732,7 +732,15 @@ typedef struct {
    * <= ~2^-23 per product: f2g_gemm_desc.precision 3; conv32x6.hip): `w` is the f2g_split_bf16x3 image
    * of the weight matrix -- fwd: of the packed (32, 27*32) matrix (ld = K = 864); dgrad: of the 27
    * transposed tiles as an (864, 32) matrix (ld = K = 32) --, patch / gradient tiles are split while they
-   * are staged; wgrad takes the fp32 operands as they are. */
+   * are staged; wgrad takes the fp32 operands as they are.
+   * 4 = fp16x3 products (two scaled fp16 pieces per value, three MFMAs per product: f2g_gemm_desc.precision 4;
+   * conv32h3.hip), fwd and dgrad only (wgrad, f2g_conv33_* and f2g_conv2ch_* refuse it): `w` is ONE
+   * f2g_split_f16x2_seq run (nseq = 1, seq_floats = 27648) over the same matrix as for 3 -- 128 bytes per 32-float
+   * row segment: 32 hi halves, then 32 lo halves -- with its one reciprocal scale at float 27648 of `w`.  The
+   * patch / gradient tile is scaled inside the kernel while it is staged: one power of two per tile and launch,
+   * from the largest magnitude of the tile's staged patch (halo pixels included, nothing outside the map).  Per
+   * output: |error| <= 3 * 2^-22 sum |a||w| + 2^-28 (amax_patch sum_k |w_k| + wmax sum_k |a_k|).  A patch that holds
+   * an inf or a NaN is staged unscaled.  Alignment and size limits as for 3. */
   int32_t precision;
   float* y;
   int64_t y_seq, y_line;
