@@ -1095,12 +1095,15 @@ def _timed_conv(name, flops, shape, *args):
 
 
 # F2G_GEMM=fp16x3: the (3, 9) band layers' forward / data gradient on the fp16x3 kernels that scale every tile's patch
-# inside the kernel (conv32h3.hip, f2g_conv32_desc.precision = 4).  Off by default: the weight gradient, the (3, 3)
-# layer and the first layer stay on their precision-3 kernels either way (tests and tools/conv32_probe.py flip them)
+# inside the kernel (conv32h3.hip, f2g_conv32_desc.precision = 4), their weight gradient on the kernel that keeps one
+# running scale per operand and block (conv32h3w.hip, f2g_conv32_s2_wgrad_h3).  Off by default: the (3, 3) layer and
+# the first layer stay on their precision-3 kernels either way (tests and tools/conv32_probe.py flip them)
 FP16X3_CONV32_FWD = opt("fp16x3_conv32_fwd", False)
 FP16X3_CONV32_DGRAD = opt("fp16x3_conv32_dgrad", False)
+FP16X3_CONV32_WGRAD = opt("fp16x3_conv32_wgrad", False)
 FP16X3_CONV32_FWD_LAUNCHES = 0      # launches conv32_s2_fwd3h_kernel took (tests and tools)
 FP16X3_CONV32_DGRAD_LAUNCHES = 0    # launches conv32_s2_dgrad3h_kernel took
+FP16X3_CONV32_WGRAD_LAUNCHES = 0    # launches conv32_s2_wgrad3h_kernel took
 
 
 def conv32_f16_image(w):
@@ -1219,15 +1222,21 @@ def conv32_s2_dgrad(g, S: int, H: int, Win: int, Wout: int, wT, gx, g_seq=None, 
 
 def conv32_s2_wgrad(x, g, S: int, H: int, Win: int, Wout: int, gw):
     """gw (32, 27*32) += weight gradient of Conv2d(32, 32, (3, 9), stride (1, 2), padding (1, 4));
-    x (S*H*Win, 32) layer input, g (S*H*Wout, 32) gradient of the pre-activation."""
+    x (S*H*Win, 32) layer input, g (S*H*Wout, 32) gradient of the pre-activation.  In the fp16x3 mode with the
+    fp16x3_conv32_wgrad tunable on: the fp16x3 kernel (f2g_conv32_s2_wgrad_h3, precision 4)."""
+    global FP16X3_CONV32_WGRAD_LAUNCHES
     d = L.Conv32Desc()
     d.x, d.x_seq, d.x_line = ptr(x), H * Win * 32, Win * 32
     d.S, d.H, d.Win, d.Wout = S, H, Win, Wout
     d.w, d.bias, d.lrelu_slope = None, None, 0.0
     d.y, d.y_seq, d.y_line = ptr(g), H * Wout * 32, Wout * 32
     _conv32_operand(d, None)
-    _timed_conv("f2g_conv32_s2_wgrad", 2.0 * S * H * Wout * 32 * 27 * 32, (2, 32, 27 * 32, S * H * Wout),
-                C.byref(d), ptr(gw))
+    name = "f2g_conv32_s2_wgrad"
+    if FP16X3 and GEMM_PRECISION == 3 and CONV32_X6 and FP16X3_CONV32_WGRAD:
+        d.precision = 4
+        name = "f2g_conv32_s2_wgrad_h3"
+        FP16X3_CONV32_WGRAD_LAUNCHES += 1
+    _timed_conv(name, 2.0 * S * H * Wout * 32 * 27 * 32, (2, 32, 27 * 32, S * H * Wout), C.byref(d), ptr(gw))
     return gw
 
 

@@ -762,6 +762,15 @@ int f2g_conv32_s2_dgrad(const f2g_conv32_desc* d, f2g_stream_t stream);
 /* Weight gradient of that layer: x = layer input (S, H, Win, 32), y = gradient of the
  * pre-activation (S, H, Wout, 32) (read), gw (32, 27*32) [co][tap][ci] accumulated atomically. */
 int f2g_conv32_s2_wgrad(const f2g_conv32_desc* d, float* gw, f2g_stream_t stream);
+/* The same weight gradient on fp16x3 products (conv32h3w.hip): precision must be 4 (F2G_EINVAL otherwise); roles,
+ * alignment, strides and size limits as f2g_conv32_s2_wgrad at precision 3 (x and y optionally strided through
+ * *_line / *_seq), w unused.  Both operands are split inside the kernel under ONE MONOTONE RUNNING SCALE per
+ * operand and block: the largest magnitude met so far in the block's walk over its consecutive tiles (x: every
+ * float of a tile's staged patch, halo included; y: the gradient tile; a zero or non-finite tile leaves it alone),
+ * the stored sums rescaled when it moves.  Per output: |error| <= 3 * 2^-22 sum |g||x| + 2^-28 sum_T (xrun_T
+ * sum_{px in T} |g| + grun_T sum_{px in T} |x|), xrun_T / grun_T the running maxima in force at tile T.  A separate
+ * symbol, so that f2g_conv32_s2_wgrad keeps refusing precision 4; a later change may fold the two. */
+int f2g_conv32_s2_wgrad_h3(const f2g_conv32_desc* d, float* gw, f2g_stream_t stream);
 /* Fifth layer of a band stack, Conv2d(32, 32, (3, 3), padding (1, 1)), stride 1 (discriminators.py:171-181,
  * last entry) as a direct kernel, fp32 class only (precision must be 3; the exact-fp32 step keeps the
  * implicit GEMM): x (S, H, W, 32) and y (S, H, W, 32) with explicit sequence / line strides (Win == Wout

@@ -6,7 +6,10 @@ AB=1: the precision-4 leg.  The same library's precision-3 launch (conv32x6.hip)
 (conv32h3.hip: fp16x3, the patch scaled per tile inside the kernel) in F2G_GEMM=fp16x3, one process on one box, legs
 alternating (p3 1, p4 1, p3 2, ...), three runs each, weight images cached in both legs as in the step: the 45
 forward shapes, the plain data gradient (S = 64), the masked data gradient + column sums (S = 128); then the stage-2
-step, tunables off against on, in three alternating pairs.  OUT=path: the report is written there as well."""
+step, tunables off against on, in three alternating pairs.  ONLY=wgrad: the weight gradient instead (S = 128), the
+precision-3 f2g_conv32_s2_wgrad launch against f2g_conv32_s2_wgrad_h3 (conv32h3w.hip), then the stage-2 step with
+fp16x3_conv32_wgrad alone differing between the legs and the other two band-conv tunables as shipped.  OUT=path: the
+report is written there as well."""
 import os, sys, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -47,16 +50,22 @@ def ab_main():
     wT = torch.nn.Parameter(torch.randn(27, 32, 32, device=dev) * 0.05)
     bb = torch.randn(32, device=dev)
 
+    WG = ONLY == "wgrad"                       # the weight-gradient tunable alone differs between the legs
+
     def leg(on):
-        ops.FP16X3_CONV32_FWD = ops.FP16X3_CONV32_DGRAD = on
+        if WG:
+            ops.FP16X3_CONV32_WGRAD = on
+        else:
+            ops.FP16X3_CONV32_FWD = ops.FP16X3_CONV32_DGRAD = on
 
     say(f"# tools/conv32_probe.py AB=1  {L.version()}  {torch.cuda.get_device_name(0)}")
-    say("# p3 = f2g_conv32_desc.precision 3 (conv32x6.hip), p4 = precision 4 (conv32h3.hip), the same library, "
-        "F2G_GEMM=fp16x3,")
+    say("# p3 = f2g_conv32_desc.precision 3 (conv32x6.hip), p4 = precision 4 (conv32h3.hip; weight gradient: "
+        "conv32h3w.hip), the same library, F2G_GEMM=fp16x3,")
     say("# one process, legs alternating p3 1, p4 1, p3 2, p4 2, p3 3, p4 3; us per launch (10 launches after 3)")
     for title, S, kind in (("forward", 128, "fwd"), ("plain data gradient (S = 64)", 64, "dgrad"),
-                           ("masked data gradient + column sums (S = 128)", 128, "mask")):
-        if ONLY and not kind.startswith(ONLY) and not (ONLY == "dgrad" and kind == "mask"):
+                           ("masked data gradient + column sums (S = 128)", 128, "mask"),
+                           ("weight gradient (S = 128)", 128, "wgrad")):
+        if (kind == "wgrad") != WG or (ONLY and not kind.startswith(ONLY) and not (ONLY == "dgrad" and kind == "mask")):
             continue
         runs = {False: [], True: []}
         for rep in range(3):
@@ -68,6 +77,11 @@ def ab_main():
                         x = torch.randn(S * H * Win, 32, device=dev)
                         y = torch.empty(S * H * Wout, 32, device=dev)
                         ts.append(timeit(lambda: ops.conv32_s2_fwd(x, S, H, Win, Wout, w, bb, 0.1, y)))
+                    elif kind == "wgrad":
+                        x = torch.randn(S * H * Win, 32, device=dev)
+                        gy = torch.randn(S * H * Wout, 32, device=dev)
+                        gw = torch.zeros(32, 27 * 32, device=dev)
+                        ts.append(timeit(lambda: ops.conv32_s2_wgrad(x, gy, S, H, Win, Wout, gw)))
                     else:
                         gy = torch.randn(S * H * Wout, 32, device=dev)
                         gx = torch.empty(S * H * Win, 32, device=dev)
@@ -93,7 +107,7 @@ def ab_main():
         say("total of the 45 launches (ms): p3 " + " ".join(f"{t:.2f}" for t in ta) + "   p4 "
             + " ".join(f"{t:.2f}" for t in tb) + f"   ranges {max(ta) - min(ta):.2f} / {max(tb) - min(tb):.2f}"
             + f"   medians {statistics.median(ta):.2f} -> {statistics.median(tb):.2f}")
-    if not ONLY:
+    if not ONLY or WG:
         import flow2gan_amd
         from flow2gan_amd import harness
         from flow2gan_amd.models.config import get_gan_config, get_generator_config
@@ -129,7 +143,7 @@ def ab_main():
         for rep in range(3):
             for on in (False, True):
                 leg(on)
-                n0 = ops.FP16X3_CONV32_FWD_LAUNCHES, ops.FP16X3_CONV32_DGRAD_LAUNCHES
+                n0 = ops.FP16X3_CONV32_FWD_LAUNCHES, ops.FP16X3_CONV32_DGRAD_LAUNCHES, ops.FP16X3_CONV32_WGRAD_LAUNCHES
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(nsteps):
@@ -137,15 +151,18 @@ def ab_main():
                 torch.cuda.synchronize()
                 per[on].append((time.perf_counter() - t0) * 1e3 / nsteps)
                 counts[on] = ((ops.FP16X3_CONV32_FWD_LAUNCHES - n0[0]) // nsteps,
-                              (ops.FP16X3_CONV32_DGRAD_LAUNCHES - n0[1]) // nsteps)
-        say(f"\n== the stage-2 step (B = {Bn}, F2G_GEMM=fp16x3), tunables off against on: ms per step, blocks of "
+                              (ops.FP16X3_CONV32_DGRAD_LAUNCHES - n0[1]) // nsteps,
+                              (ops.FP16X3_CONV32_WGRAD_LAUNCHES - n0[2]) // nsteps)
+        what = "fp16x3_conv32_wgrad alone off against on, the other band-conv tunables as shipped" if WG \
+            else "tunables off against on"
+        say(f"\n== the stage-2 step (B = {Bn}, F2G_GEMM=fp16x3), {what}: ms per step, blocks of "
             f"{nsteps} steps, three alternating pairs")
         for rep in range(3):
             say(f"pair {rep + 1}: off {per[False][rep]:.2f}   on {per[True][rep]:.2f}")
         mo, mn = statistics.median(per[False]), statistics.median(per[True])
         say(f"medians {mo:.2f} -> {mn:.2f} (ratio {mn / mo:.3f}); within-leg ranges "
             f"{max(per[False]) - min(per[False]):.2f} / {max(per[True]) - min(per[True]):.2f}; precision-4 launches per "
-            f"step: off {counts[False]}, on {counts[True]} (forward, data gradient)")
+            f"step: off {counts[False]}, on {counts[True]} (forward, data gradient, weight gradient)")
     leg(False)
     if os.environ.get("OUT"):
         os.makedirs(os.path.dirname(os.path.abspath(os.environ["OUT"])), exist_ok=True)
