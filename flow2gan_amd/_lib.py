@@ -244,7 +244,7 @@ _SIGS = {
     "f2g_multi": [C.POINTER(MultiDesc)],
 }
 EXPORTS = sorted(list(_SIGS) + ["f2g_version", "f2g_last_error", "f2g_gemm_last_path", "f2g_gemm_last_kernel",
-                                 "f2g_fused_last_launch",
+                                 "f2g_fused_last_launch", "f2g_convnext_last_launch",
                                  "f2g_gemm_lean_ok", "f2g_gemm_wgrad_lean", "f2g_fused_mlp_ok",
                                  "f2g_dwnorm_bwd_workspace", "f2g_split_bf16x3_bytes", "f2g_gemm_x6_ok",
                                  "f2g_gemm_colsum_part_rows", "f2g_gemm_f16_ok", "f2g_set_option", "f2g_get_option",
@@ -295,6 +295,8 @@ def _load():
     lib.f2g_gemm_last_kernel.restype = C.c_char_p
     lib.f2g_fused_last_launch.argtypes = []
     lib.f2g_fused_last_launch.restype = C.c_char_p
+    lib.f2g_convnext_last_launch.argtypes = []
+    lib.f2g_convnext_last_launch.restype = C.c_char_p
     return lib
 
 

@@ -136,8 +136,10 @@ __global__ __launch_bounds__(256) void dwnorm_kernel(const f2g_dwnorm_bwd_desc D
 #pragma unroll
         for (int k = 0; k < CPL; ++k) {
           const int c = lane + 64 * k;
-          if (k < nk && c < C && has_cp)
-            D.g_cproj[((long long)b * P.Fc + fc) * P.ldcp + c] += gcp[k];
+          if (k < nk && c < C && has_cp) {
+            float* o = D.g_cproj + ((long long)b * P.Fc + fc) * P.ldcp + c;
+            *o = D.g_cproj_store ? gcp[k] : *o + gcp[k];
+          }
           gcp[k] = 0.f;
         }
       }
@@ -827,6 +829,9 @@ bool vec4_ok(const f2g_dwnorm_bwd_desc& d, bool bwd) {
   return ok;
 }
 
+// which kernel instance the last launch of this file ran (f2g_convnext_last_launch): host side only
+const char* g_cn_last = "";
+
 template <bool BWD>
 int launch_dwnorm(const f2g_dwnorm_bwd_desc& d, hipStream_t st) {
   const f2g_dwnorm_fwd_desc& f = d.f;
@@ -852,17 +857,30 @@ int launch_dwnorm(const f2g_dwnorm_bwd_desc& d, hipStream_t st) {
   if (vec4_ok(d, BWD)) {
     const size_t smem = (size_t)9 * f.C * sizeof(float);
     const int nch = (f.C + 255) / 256;
-#define F2G_DW4(FWV, NCHV) \
-  hipLaunchKernelGGL((dwnorm4_kernel<BWD, FWV, NCHV>), grid, dim3(256), smem, st, d)
+#define F2G_DW4(FWV, NCHV, FWD_NAME, BWD_NAME)                                            \
+  do {                                                                                    \
+    g_cn_last = BWD ? BWD_NAME : FWD_NAME;                                                \
+    hipLaunchKernelGGL((dwnorm4_kernel<BWD, FWV, NCHV>), grid, dim3(256), smem, st, d);   \
+  } while (0)
     if (four) {
-      if (nch == 1) F2G_DW4(4, 1); else if (nch == 2) F2G_DW4(4, 2); else F2G_DW4(4, 3);
+      if (nch == 1) F2G_DW4(4, 1, "dwnorm4<bwd=0,fw=4,nch=1>", "dwnorm4<bwd=1,fw=4,nch=1>");
+      else if (nch == 2) F2G_DW4(4, 2, "dwnorm4<bwd=0,fw=4,nch=2>", "dwnorm4<bwd=1,fw=4,nch=2>");
+      else F2G_DW4(4, 3, "dwnorm4<bwd=0,fw=4,nch=3>", "dwnorm4<bwd=1,fw=4,nch=3>");
+    } else if constexpr (BWD) {
+      // 2 frames per wave on the vector route: the backward above 512 channels only, so always 3
+      // chunks.  (C <= 512 with C % 4 == 0 -- which vec4_ok demands -- makes `four` true; the
+      // forward's `four` IS C % 4 == 0, so it never gets here: no FW = 2 forward instance and no
+      // FW = 2 backward instance with 1 or 2 chunks exists.)
+      F2G_DW4(2, 3, "", "dwnorm4<bwd=1,fw=2,nch=3>");
     } else {
-      if (nch == 1) F2G_DW4(2, 1); else if (nch == 2) F2G_DW4(2, 2); else F2G_DW4(2, 3);
+      return F2G_EINVAL;   // unreachable (see above)
     }
 #undef F2G_DW4
   } else if (four) {
+    g_cn_last = BWD ? "dwnorm<bwd=1,fw=4>" : "dwnorm<bwd=0,fw=4>";
     hipLaunchKernelGGL((dwnorm_kernel<BWD, 4>), grid, dim3(256), 0, st, d);
   } else {
+    g_cn_last = BWD ? "dwnorm<bwd=1,fw=2>" : "dwnorm<bwd=0,fw=2>";
     hipLaunchKernelGGL((dwnorm_kernel<BWD, 2>), grid, dim3(256), 0, st, d);
   }
   int rc = f2g_check_launch();
@@ -915,8 +933,10 @@ extern "C" int f2g_dwconv_bwd(const f2g_dwconv_bwd_desc* d, f2g_stream_t stream)
   if (vec4) {
     const int strips = (d->F + DWS_STRIP - 1) / DWS_STRIP;
     grid.y = (strips + 3) / 4;
+    g_cn_last = "dwconv4_bwd";
     hipLaunchKernelGGL(dwconv4_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, *d);
   } else {
+    g_cn_last = "dwconv_bwd";
     hipLaunchKernelGGL(dwconv_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, *d);
   }
   int rc = f2g_check_launch();
@@ -933,6 +953,7 @@ extern "C" int f2g_biasnorm_fwd(const float* x, int64_t ldx, float* y, int64_t l
                                 f2g_stream_t stream) {
   if (!x || !y || !beta || !log_scale || C < 1) return F2G_EINVAL;
   if (rows <= 0) return F2G_OK;
+  g_cn_last = "biasnorm_fwd";
   hipLaunchKernelGGL(biasnorm_fwd_kernel, dim3((rows + 3) / 4), dim3(256), 0, (hipStream_t)stream,
                      x, (long long)ldx, y, (long long)ldy, rows, C, beta, log_scale);
   return f2g_check_launch();
@@ -945,8 +966,14 @@ extern "C" int f2g_biasnorm_bwd(const float* x, int64_t ldx, const float* gy, in
   if (!x || !gy || !gx || !beta || !log_scale || C < 1 || C > 64 * CPL) return F2G_EINVAL;
   if (rows <= 0) return F2G_OK;
   int per_block = 4 * BN_ROWS;
+  g_cn_last = "biasnorm_bwd";
   hipLaunchKernelGGL(biasnorm_bwd_kernel, dim3((rows + per_block - 1) / per_block), dim3(256), 0,
                      (hipStream_t)stream, x, (long long)ldx, gy, (long long)ldgy, gx,
                      (long long)ldgx, rows, C, beta, log_scale, g_beta, g_log_scale);
   return f2g_check_launch();
 }
+
+// "dwnorm4<bwd=1,fw=4,nch=2>", "dwnorm<bwd=0,fw=2>", "dwconv4_bwd", "dwconv_bwd", "biasnorm_fwd" or
+// "biasnorm_bwd": the kernel instance the last f2g_dwnorm_* / f2g_dwconv_bwd / f2g_biasnorm_* call
+// launched (the second-stage reductions are not reported); "" before the first launch
+extern "C" const char* f2g_convnext_last_launch(void) { return g_cn_last; }

@@ -1737,9 +1737,11 @@ def dwnorm_fwd(x, z, B, F, Cc, K, lens, w_dw, b_dw, beta, log_scale, cproj=None,
 
 def dwnorm_bwd(x, gz, du, B, F, Cc, K, lens, w_dw, b_dw, beta, log_scale, cproj=None, ldcp=0,
                Fc=0, up=1, cp_off=0, te=None, ldte=0, te_off=0, g_cproj=None, g_te=None,
-               g_beta=None, g_log_scale=None, g_cproj_store=False):
+               g_beta=None, g_log_scale=None, g_cproj_store=False, partials=True):
     """g_cproj_store: the caller zero-filled g_cproj's columns [cp_off, cp_off + Cc) and nothing else
-    adds to them -- the kernel then stores the condition gradient instead of read-modify-writing it."""
+    adds to them -- the kernel then stores the condition gradient instead of read-modify-writing it.
+    partials=False: no workspace, the kernel adds its parameter gradients atomically (the C ABI's other
+    epilogue; the package always passes the workspace)."""
     d = DwnormBwd()
     d.f = _dw_desc(x, x.stride(0), None, 0, B, F, Cc, K, lens, w_dw, b_dw, beta, log_scale, cproj,
                    ldcp, Fc, up, cp_off, te, ldte, te_off, None)
@@ -1749,9 +1751,10 @@ def dwnorm_bwd(x, gz, du, B, F, Cc, K, lens, w_dw, b_dw, beta, log_scale, cproj=
     d.g_cproj_store = 1 if (g_cproj_store and g_cproj is not None) else 0
     d.g_te = None if g_te is None else ptr(g_te) + 4 * te_off
     d.g_beta, d.g_log_scale = ptr(g_beta), ptr(g_log_scale)
-    ws = torch.empty(L.lib.f2g_dwnorm_bwd_workspace(B, F, Cc, up if cproj is not None else 1),
-                     device=x.device, dtype=torch.float32)
-    d.partials = ptr(ws)
+    if partials:
+        ws = torch.empty(L.lib.f2g_dwnorm_bwd_workspace(B, F, Cc, up if cproj is not None else 1),
+                         device=x.device, dtype=torch.float32)
+        d.partials = ptr(ws)
     if GEMM_TIMER is not None:
         # algorithmic bytes: read x and gz, write du; with a condition input its rows are read and its
         # gradient rows written once per `up` frames (the gradient is consumed by the condition path's
@@ -1765,7 +1768,8 @@ def dwnorm_bwd(x, gz, du, B, F, Cc, K, lens, w_dw, b_dw, beta, log_scale, cproj=
 
 
 def dwconv_bwd(du, x, gx, B, F, Cc, K, lens, w_dw, gres=None, gamma=None, g_w=None, g_b=None,
-               g_gamma=None):
+               g_gamma=None, partials=True):
+    """partials=False: no workspace, atomic parameter gradients (as dwnorm_bwd)."""
     d = DwconvBwd()
     d.du, d.lddu = ptr(du), du.stride(0)
     d.x, d.ldx = ptr(x), x.stride(0)
@@ -1777,9 +1781,10 @@ def dwconv_bwd(du, x, gx, B, F, Cc, K, lens, w_dw, gres=None, gamma=None, g_w=No
     d.ldgres = gres.stride(0) if gres is not None else 0
     d.gamma = ptr(gamma)
     d.g_w, d.g_b, d.g_gamma = ptr(g_w), ptr(g_b), ptr(g_gamma)
-    ws = torch.empty(L.lib.f2g_dwconv_bwd_workspace(B, F, Cc, K), device=x.device,
-                     dtype=torch.float32)
-    d.partials = ptr(ws)
+    if partials:
+        ws = torch.empty(L.lib.f2g_dwconv_bwd_workspace(B, F, Cc, K), device=x.device,
+                         dtype=torch.float32)
+        d.partials = ptr(ws)
     if GEMM_TIMER is not None:   # read du, x, gres; write gx
         GEMM_TIMER.time_hbm(lambda: call("f2g_dwconv_bwd", C.byref(d)), 16.0 * B * F * Cc, "dwconv_bwd")
     else:

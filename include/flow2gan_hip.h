@@ -930,6 +930,12 @@ int f2g_fused_block_multi(const f2g_dwnorm_fwd_desc* dw, const f2g_fused_mlp_des
  * along the hidden dimension) or "fused_block_multi<rt=R0,R1,...>" (rows / 32 per tile of each entry, in the
  * order handed over). */
 const char* f2g_fused_last_launch(void);
+/* The same for the HBM-bound ConvNeXt kernels (f2g_dwnorm_fwd / f2g_dwnorm_bwd / f2g_dwconv_bwd /
+ * f2g_biasnorm_fwd / f2g_biasnorm_bwd): the kernel instance the last of them launched, "" before the first.
+ * "dwnorm4<bwd=B,fw=W,nch=N>" (float4 rows: W frames per wave, N 256-channel chunks per lane),
+ * "dwnorm<bwd=B,fw=W>" (any C, any alignment), "dwconv4_bwd", "dwconv_bwd", "biasnorm_fwd", "biasnorm_bwd".
+ * A host-side static set where the kernel is launched; tests and diagnostics, not thread safe. */
+const char* f2g_convnext_last_launch(void);
 
 #ifdef __cplusplus
 }
