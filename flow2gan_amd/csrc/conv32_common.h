@@ -1,5 +1,5 @@
 // What the direct MRD band convolutions share (conv32.hip: exact fp32 and split-bf16; conv32x6.hip: fp32 class;
-// conv32h3.hip: fp16x3): the vector types and layer constants, the accumulator-row map, the map from MFMA rows to
+// conv32h3.hip, conv32h3w.hip, conv33h3.hip: fp16x3): the vector types and layer constants, the accumulator-row map, the map from MFMA rows to
 // tile pixels and the small divisions of the kernels that stage split pixels, the transposed fragment read of the
 // weight gradients, the pick between the two tile shapes and their launch, the store expression of the data
 // gradients and the flush of the weight gradients.  What a kernel stages and how it walks its taps stay with the kernel.
@@ -76,6 +76,19 @@ inline c32_tiling c32_pick_tiles(int H, int W, int W_also = 0) {
   const bool tall = waste(16, 8) < waste(8, 16);
   const int th = tall ? 16 : 8, tw = tall ? 8 : 16;
   return {tall, (H + th - 1) / th, (W + tw - 1) / tw, (W_also + tw - 1) / tw};
+}
+
+// ---- the (3, 3) fifth layer (conv32x6.hip: conv33_x6_kernel, conv33_wgrad6_kernel; conv33h3.hip: conv33_h3_kernel):
+// a tile is R WHOLE rows of a W-column band image, staged with a zero column on either side and a row above / below
+constexpr int P33 = 352;                 // staged pixels of a tile: (R + 2) * (W + 2) <= P33
+constexpr int T33 = 9;                   // taps
+
+// rows per tile: R * W <= 256 pixels where the staged patch allows it; 0 = not even one row fits (W > 112)
+inline int c33_pick_rows(int H, int W) {
+  int R = 256 / W;
+  if (R > H) R = H;
+  while (R > 1 && (R + 2) * (W + 2) > P33) --R;
+  return (R < 1 || (R + 2) * (W + 2) > P33) ? 0 : R;
 }
 
 // a kernel instance's dynamic LDS limit, raised once per process (thread-safe: a function-local static)

@@ -664,10 +664,8 @@ __global__ __launch_bounds__(512, 1) void conv32_s2_wgrad6_kernel(const f2g_conv
 // CU: all nine weight tiles (55 KB image, 208-byte rows) stay in LDS for the block's life, the next tile's
 // patch is requested before the current tile's 108 MFMAs per wave and split into its three pieces behind them.
 // The data gradient of a stride-1 conv is the same kernel over the gradient map with the taps flipped and the
-// channel matrix transposed (the host re-lays the weights once per version).
-constexpr int P33 = 352;                 // staged pixels of a tile: (R + 2) * (W + 2) <= P33
-constexpr int T33 = 9;
-
+// channel matrix transposed (the host re-lays the weights once per version).  (P33, T33 and the pick of R:
+// conv32_common.h, shared with the fp16x3 instance in conv33h3.hip.)
 __global__ __launch_bounds__(512, 1) void conv33_x6_kernel(const f2g_conv32_desc d, int R, int tiles_h, int ntiles) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smb[];
   unsigned char* At = smb;                       // [P33] staged pixels
@@ -926,9 +924,13 @@ int f2g_conv32_wgrad6_launch(const f2g_conv32_desc* d, float* gw, hipStream_t st
       per);
 }
 
-// Conv2d(32, 32, (3, 3), padding (1, 1)) + bias + leaky ReLU, fp32 class (include/flow2gan_hip.h)
+// precision 4 (fp16x3 products, the patch scaled per tile inside the kernel): conv33h3.hip
+int f2g_conv33_h3_launch(const f2g_conv32_desc* d, int R, int tiles_h, int ntiles, hipStream_t st);
+
+// Conv2d(32, 32, (3, 3), padding (1, 1)) + bias + leaky ReLU, fp32 class (3) or fp16x3 (4) (include/flow2gan_hip.h)
 extern "C" int f2g_conv33_fwd(const f2g_conv32_desc* d, f2g_stream_t stream) {
-  if (!d || !d->x || !d->w || !d->y || d->precision != 3 || d->Win != d->Wout || d->fm_ref) return F2G_EINVAL;
+  if (!d || !d->x || !d->w || !d->y || (d->precision != 3 && d->precision != 4) || d->Win != d->Wout || d->fm_ref)
+    return F2G_EINVAL;
   if ((((uintptr_t)d->x) & 15) || (((uintptr_t)d->w) & 15) || (d->x_line & 3) || (d->x_seq & 3)) return F2G_EINVAL;
   if (d->S <= 0 || d->H <= 0 || d->Win <= 0) return F2G_OK;
   const int W = d->Win;
@@ -941,13 +943,12 @@ extern "C" int f2g_conv33_fwd(const f2g_conv32_desc* d, f2g_stream_t stream) {
     f2g_set_error("f2g_conv33_fwd: mask_src (data-gradient role) excludes bias / lrelu_slope (forward role)");
     return F2G_EINVAL;
   }
-  int R = 256 / W;                                   // whole rows per tile
-  if (R > d->H) R = d->H;
-  while (R > 1 && (R + 2) * (W + 2) > P33) --R;
-  if (R < 1 || (R + 2) * (W + 2) > P33) return F2G_EINVAL;
+  const int R = c33_pick_rows(d->H, W);              // whole rows per tile
+  if (R < 1) return F2G_EINVAL;
   const int tiles_h = (d->H + R - 1) / R;
   const long long nt = (long long)tiles_h * d->S;
   if (nt >= (1ll << 30)) return F2G_EINVAL;
+  if (d->precision == 4) return f2g_conv33_h3_launch(d, R, tiles_h, (int)nt, (hipStream_t)stream);
   constexpr size_t smem = (size_t)P33 * PB + (size_t)T33 * C * PB;
   c32_lds_once<conv33_x6_kernel>(smem);
   const int grid = (int)(nt < 256 ? nt : 256);          // one resident block per CU
@@ -955,8 +956,9 @@ extern "C" int f2g_conv33_fwd(const f2g_conv32_desc* d, f2g_stream_t stream) {
   return f2g_check_launch();
 }
 
-// Weight gradient of that layer, fp32 class: x = the layer's input (S, H, W, 32), y = the gradient of its
-// pre-activation (S, H, W, 32; both optionally strided slices of wider maps), gw (32, 9 * 32) [co][tap][ci] +=.
+// Weight gradient of that layer, fp32 class (precision 4 is refused: conv33_wgrad6_kernel has no fp16x3 twin): x =
+// the layer's input (S, H, W, 32), y = the gradient of its pre-activation (S, H, W, 32; both optionally strided
+// slices of wider maps), gw (32, 9 * 32) [co][tap][ci] +=.
 extern "C" int f2g_conv33_wgrad(const f2g_conv32_desc* d, float* gw, f2g_stream_t stream) {
   if (!d || !d->x || !d->y || !gw || d->precision != 3 || d->Win != d->Wout) return F2G_EINVAL;
   if ((((uintptr_t)d->x) & 15) || (((uintptr_t)d->y) & 15) || (d->x_line & 3) || (d->x_seq & 3) || (d->y_line & 3) ||
@@ -967,10 +969,8 @@ extern "C" int f2g_conv33_wgrad(const f2g_conv32_desc* d, float* gw, f2g_stream_
   if (W > 112 || d->x_line >= (1ll << 24) || d->y_line >= (1ll << 24) || d->x_line < (long long)W * C ||
       d->y_line < (long long)W * C)
     return F2G_EINVAL;
-  int R = 256 / W;                                   // whole rows per tile (conv33_x6_kernel's rule)
-  if (R > d->H) R = d->H;
-  while (R > 1 && (R + 2) * (W + 2) > P33) --R;
-  if (R < 1 || (R + 2) * (W + 2) > P33) return F2G_EINVAL;
+  const int R = c33_pick_rows(d->H, W);              // whole rows per tile (conv33_x6_kernel's rule)
+  if (R < 1) return F2G_EINVAL;
   const int tiles_h = (d->H + R - 1) / R;
   const long long nt = (long long)tiles_h * d->S;
   if (nt >= (1ll << 30)) return F2G_EINVAL;

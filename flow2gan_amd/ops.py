@@ -1096,20 +1096,26 @@ def _timed_conv(name, flops, shape, *args):
 
 # F2G_GEMM=fp16x3: the (3, 9) band layers' forward / data gradient on the fp16x3 kernels that scale every tile's patch
 # inside the kernel (conv32h3.hip, f2g_conv32_desc.precision = 4), their weight gradient on the kernel that keeps one
-# running scale per operand and block (conv32h3w.hip, f2g_conv32_s2_wgrad_h3).  Off by default: the (3, 3) layer and
-# the first layer stay on their precision-3 kernels either way (tests and tools/conv32_probe.py flip them)
+# running scale per operand and block (conv32h3w.hip, f2g_conv32_s2_wgrad_h3); the (3, 3) fifth layer's forward /
+# data gradient on the fp16x3 twin of conv33_x6_kernel (conv33h3.hip, f2g_conv33_fwd at precision 4).  All off by
+# default; the (3, 3) layer's weight gradient and the first layer stay on their precision-3 kernels either way (tests
+# and tools/conv32_probe.py flip them)
 FP16X3_CONV32_FWD = opt("fp16x3_conv32_fwd", False)
 FP16X3_CONV32_DGRAD = opt("fp16x3_conv32_dgrad", False)
 FP16X3_CONV32_WGRAD = opt("fp16x3_conv32_wgrad", False)
+FP16X3_CONV33_FWD = opt("fp16x3_conv33_fwd", False)
+FP16X3_CONV33_DGRAD = opt("fp16x3_conv33_dgrad", False)
 FP16X3_CONV32_FWD_LAUNCHES = 0      # launches conv32_s2_fwd3h_kernel took (tests and tools)
 FP16X3_CONV32_DGRAD_LAUNCHES = 0    # launches conv32_s2_dgrad3h_kernel took
 FP16X3_CONV32_WGRAD_LAUNCHES = 0    # launches conv32_s2_wgrad3h_kernel took
+FP16X3_CONV33_FWD_LAUNCHES = 0      # launches conv33_h3_kernel took in the forward role (form 0)
+FP16X3_CONV33_DGRAD_LAUNCHES = 0    # ... in the data-gradient role (form 1)
 
 
 def conv32_f16_image(w):
     """The image the precision-4 band convolutions read: ONE f2g_split_f16x2_seq run over the whole contiguous
-    weight matrix (27648 floats) with its reciprocal scale behind it (cached for weights and cached re-layouts of
-    weights, as _f16_seq_operand's)."""
+    weight matrix (27648 floats; 9216 for the (3, 3) layer) with its reciprocal scale behind it (cached for weights and
+    cached re-layouts of weights, as _f16_seq_operand's)."""
     n = w.numel()
     tag = ("f16x2seq", 0, 1, n, n)
     return derived(w, tag, lambda t: split_f16_seq(t, 1, n)) if _is_const(w) else split_f16_seq(w, 1, n)
@@ -1159,14 +1165,25 @@ def conv33(x, S: int, H: int, W: int, w_packed, bias, slope: float, y, x_off: in
     """Conv2d(32, 32, (3, 3), padding (1, 1)) (+ bias + leaky ReLU) on channels-last images, fp32 class
     (conv32x6.hip: conv33_x6_kernel): x (S, H, W, 32) -> y (S, H, W, 32), both optionally strided slices of
     wider maps (floats); w_packed = (32, 9*32) [co][tap][ci] -- for the data gradient the caller passes the
-    gradient map and the flipped / transposed matrix [ci][8 - tap][co] (form = 1: bench.py's FLOP table)."""
+    gradient map and the flipped / transposed matrix [ci][8 - tap][co] (form = 1: bench.py's FLOP table).  In the
+    fp16x3 mode with the role's tunable on (form 0: fp16x3_conv33_fwd, form 1: fp16x3_conv33_dgrad): the fp16x3 kernel
+    (conv33h3.hip: conv33_h3_kernel, precision 4) over the one-run fp16 image of the same matrix."""
+    global FP16X3_CONV33_FWD_LAUNCHES, FP16X3_CONV33_DGRAD_LAUNCHES
     d = L.Conv32Desc()
     d.x = ptr(x) + 4 * x_off
     d.x_line = x_line if x_line is not None else W * 32
     d.x_seq = x_seq if x_seq is not None else H * d.x_line
     d.S, d.H, d.Win, d.Wout = S, H, W, W
-    img = x3_image(w_packed)
-    d.precision = 3
+    if FP16X3 and GEMM_PRECISION == 3 and CONV32_X6 and (FP16X3_CONV33_DGRAD if form == 1 else FP16X3_CONV33_FWD):
+        img = conv32_f16_image(w_packed)
+        d.precision = 4
+        if form == 1:
+            FP16X3_CONV33_DGRAD_LAUNCHES += 1
+        else:
+            FP16X3_CONV33_FWD_LAUNCHES += 1
+    else:
+        img = x3_image(w_packed)
+        d.precision = 3
     d._keep = img
     d.w, d.bias, d.lrelu_slope = ptr(img), ptr(bias), slope
     d.y = ptr(y) + 4 * y_off

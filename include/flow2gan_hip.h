@@ -734,7 +734,8 @@ typedef struct {
    * transposed tiles as an (864, 32) matrix (ld = K = 32) --, patch / gradient tiles are split while they
    * are staged; wgrad takes the fp32 operands as they are.
    * 4 = fp16x3 products (two scaled fp16 pieces per value, three MFMAs per product: f2g_gemm_desc.precision 4;
-   * conv32h3.hip), fwd and dgrad only (wgrad, f2g_conv33_* and f2g_conv2ch_* refuse it): `w` is ONE
+   * conv32h3.hip), fwd and dgrad only (wgrad, f2g_conv33_wgrad and f2g_conv2ch_* refuse it; f2g_conv33_fwd takes it
+   * over its own 9216-float matrix, see there): `w` is ONE
    * f2g_split_f16x2_seq run (nseq = 1, seq_floats = 27648) over the same matrix as for 3 -- 128 bytes per 32-float
    * row segment: 32 hi halves, then 32 lo halves -- with its one reciprocal scale at float 27648 of `w`.  The
    * patch / gradient tile is scaled inside the kernel while it is staged: one power of two per tile and launch,
@@ -772,16 +773,24 @@ int f2g_conv32_s2_wgrad(const f2g_conv32_desc* d, float* gw, f2g_stream_t stream
  * symbol, so that f2g_conv32_s2_wgrad keeps refusing precision 4; a later change may fold the two. */
 int f2g_conv32_s2_wgrad_h3(const f2g_conv32_desc* d, float* gw, f2g_stream_t stream);
 /* Fifth layer of a band stack, Conv2d(32, 32, (3, 3), padding (1, 1)), stride 1 (discriminators.py:171-181,
- * last entry) as a direct kernel, fp32 class only (precision must be 3; the exact-fp32 step keeps the
- * implicit GEMM): x (S, H, W, 32) and y (S, H, W, 32) with explicit sequence / line strides (Win == Wout
- * == W <= 112; the forward writes its band's slice of the concatenated map), w = the f2g_split_bf16x3 image of the
- * packed (32, 9*32) matrix [co][tap][ci], + bias + leaky ReLU.  The DATA GRADIENT of this layer is the same
- * call over the gradient map with w = the image of [ci][8 - tap][co] (taps flipped, channel matrix
- * transposed) and no bias / slope; there mask_src (+ mask_slope) / colsum apply the leaky-ReLU backward of
- * the layer below and leave the column sums of the stored gradient as in f2g_conv32_s2_dgrad (fm_ref must
- * be NULL). */
+ * last entry) as a direct kernel: precision 3 (fp32 class, conv32x6.hip) or 4 (fp16x3, conv33h3.hip), every other
+ * value is refused (the exact-fp32 step keeps the implicit GEMM): x (S, H, W, 32) and y (S, H, W, 32) with explicit
+ * sequence / line strides (Win == Wout == W <= 112; the forward writes its band's slice of the concatenated map),
+ * + bias + leaky ReLU.  The DATA GRADIENT of this layer is the same call over the gradient map with w = the image of
+ * [ci][8 - tap][co] (taps flipped, channel matrix transposed) and no bias / slope; there mask_src (+ mask_slope) /
+ * colsum apply the leaky-ReLU backward of the layer below and leave the column sums of the stored gradient as in
+ * f2g_conv32_s2_dgrad (mask_src excludes bias and slope; fm_ref must be NULL).  x, w, y and mask_src 16-byte
+ * aligned, the strides multiples of 4 floats, x_line < 2^24; a refused call writes nothing.
+ *   precision 3: w = the f2g_split_bf16x3 image of the packed (32, 9*32) matrix [co][tap][ci].
+ *   precision 4: w = ONE f2g_split_f16x2_seq run (nseq = 1, seq_floats = 9216) over that whole contiguous matrix --
+ *     128 bytes per 32-float row segment: 32 hi halves, then 32 lo halves -- with its one reciprocal scale at float
+ *     9216 of `w`.  A tile is R whole rows (R = min(256 / W, H), shrunk while (R + 2) * (W + 2) > 352); its staged
+ *     patch -- those rows, one halo row above and below, nothing outside the map -- is scaled inside the kernel by one
+ *     power of two per tile and launch, from the patch's largest magnitude.  Per output:
+ *     |error| <= 3 * 2^-22 sum |a||w| + 2^-28 (amax_patch sum_k |w_k| + wmax sum_k |a_k|).  A patch whose maximum is
+ *     zero or not finite is staged unscaled.  Apart from the colsum atomics the result is bit-reproducible. */
 int f2g_conv33_fwd(const f2g_conv32_desc* d, f2g_stream_t stream);
-/* Weight gradient of that layer (discriminators.py:171-181 backward), fp32 class (precision = 3): x = the layer's
+/* Weight gradient of that layer (discriminators.py:171-181 backward), fp32 class (precision = 3; 4 is refused): x = the layer's
  * input (S, H, W, 32), y = the gradient of its pre-activation (S, H, W, 32) -- both optionally strided slices of
  * wider maps through x_line / x_seq, y_line / y_seq --, gw (32, 9 * 32) [co][tap][ci] += sum over the pixels; W <= 112.
  * The caller zero-initialises gw (blocks accumulate atomically).  w / bias / slope / mask fields unused. */

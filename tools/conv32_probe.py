@@ -8,7 +8,11 @@ alternating (p3 1, p4 1, p3 2, ...), three runs each, weight images cached in bo
 forward shapes, the plain data gradient (S = 64), the masked data gradient + column sums (S = 128); then the stage-2
 step, tunables off against on, in three alternating pairs.  ONLY=wgrad: the weight gradient instead (S = 128), the
 precision-3 f2g_conv32_s2_wgrad launch against f2g_conv32_s2_wgrad_h3 (conv32h3w.hip), then the stage-2 step with
-fp16x3_conv32_wgrad alone differing between the legs and the other two band-conv tunables as shipped.  OUT=path: the
+fp16x3_conv32_wgrad alone differing between the legs and the other two band-conv tunables as shipped.  ONLY=conv33:
+the (3, 3) fifth layer instead -- every band width of the three resolutions after the three stride-2 layers, 15
+shapes: forward (S = 128), plain data gradient (S = 64), masked data gradient + column sums (S = 128) --, the
+precision-3 f2g_conv33_fwd launch (conv32x6.hip: conv33_x6_kernel) against its precision-4 launch (conv33h3.hip:
+conv33_h3_kernel), then the stage-2 step with fp16x3_conv33_fwd / fp16x3_conv33_dgrad alone differing.  OUT=path: the
 report is written there as well."""
 import os, sys, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -37,6 +41,13 @@ def band_shapes():
                 Win = (Win - 1) // 2 + 1
 
 
+def band33_shapes():
+    """(H, W, W) of the (3, 3) fifth layer: every third shape's output width"""
+    for i, (H, Win, Wout) in enumerate(band_shapes()):
+        if i % 3 == 2:
+            yield H, Wout, Wout
+
+
 def ab_main():
     import statistics, time
     lines = []
@@ -48,32 +59,50 @@ def ab_main():
     ops.set_gemm_precision("fp16x3")
     w = torch.nn.Parameter(torch.randn(32, 27 * 32, device=dev) * 0.05)       # (parameters: the images are cached)
     wT = torch.nn.Parameter(torch.randn(27, 32, 32, device=dev) * 0.05)
+    w33 = torch.nn.Parameter(torch.randn(32, 9 * 32, device=dev) * 0.05)     # [co][tap][ci] / [ci][8 - tap][co]
     bb = torch.randn(32, device=dev)
 
     WG = ONLY == "wgrad"                       # the weight-gradient tunable alone differs between the legs
+    C33 = ONLY == "conv33"                     # the (3, 3) layer's two tunables alone differ between the legs
+    only = "" if C33 else ONLY
+    shapes = list(band33_shapes() if C33 else band_shapes())
 
     def leg(on):
         if WG:
             ops.FP16X3_CONV32_WGRAD = on
+        elif C33:
+            ops.FP16X3_CONV33_FWD = ops.FP16X3_CONV33_DGRAD = on
         else:
             ops.FP16X3_CONV32_FWD = ops.FP16X3_CONV32_DGRAD = on
 
     say(f"# tools/conv32_probe.py AB=1  {L.version()}  {torch.cuda.get_device_name(0)}")
     say("# p3 = f2g_conv32_desc.precision 3 (conv32x6.hip), p4 = precision 4 (conv32h3.hip; weight gradient: "
-        "conv32h3w.hip), the same library, F2G_GEMM=fp16x3,")
+        "conv32h3w.hip; ONLY=conv33: conv33h3.hip), the same library, F2G_GEMM=fp16x3,")
     say("# one process, legs alternating p3 1, p4 1, p3 2, p4 2, p3 3, p4 3; us per launch (10 launches after 3)")
     for title, S, kind in (("forward", 128, "fwd"), ("plain data gradient (S = 64)", 64, "dgrad"),
                            ("masked data gradient + column sums (S = 128)", 128, "mask"),
                            ("weight gradient (S = 128)", 128, "wgrad")):
-        if (kind == "wgrad") != WG or (ONLY and not kind.startswith(ONLY) and not (ONLY == "dgrad" and kind == "mask")):
+        if (kind == "wgrad") != WG or (only and not kind.startswith(only) and not (only == "dgrad" and kind == "mask")):
             continue
         runs = {False: [], True: []}
         for rep in range(3):
             for on in (False, True):
                 leg(on)
                 ts = []
-                for H, Win, Wout in band_shapes():
-                    if kind == "fwd":
+                for H, Win, Wout in shapes:
+                    if C33:
+                        x = torch.randn(S * H * Win, 32, device=dev)
+                        y = torch.empty(S * H * Win, 32, device=dev)
+                        if kind == "fwd":
+                            ts.append(timeit(lambda: ops.conv33(x, S, H, Win, w33, bb, 0.1, y)))
+                        elif kind == "mask":
+                            ym = torch.randn(S * H * Win, 32, device=dev)
+                            csum = torch.zeros(32, device=dev)
+                            ts.append(timeit(lambda: ops.conv33(x, S, H, Win, w33, None, 0.0, y, form=1,
+                                                                mask=(ym, 0, 0.1), colsum=csum)))
+                        else:
+                            ts.append(timeit(lambda: ops.conv33(x, S, H, Win, w33, None, 0.0, y, form=1)))
+                    elif kind == "fwd":
                         x = torch.randn(S * H * Win, 32, device=dev)
                         y = torch.empty(S * H * Wout, 32, device=dev)
                         ts.append(timeit(lambda: ops.conv32_s2_fwd(x, S, H, Win, Wout, w, bb, 0.1, y)))
@@ -95,7 +124,7 @@ def ab_main():
                 runs[on].append(ts)
         say(f"\n== {title}: us per launch, three runs per leg; range = max - min of a leg's three runs")
         say("   H  Win |           p3            |           p4            |     medians     | ratio | verdict")
-        for i, (H, Win, Wout) in enumerate(band_shapes()):
+        for i, (H, Win, Wout) in enumerate(shapes):
             a = [r[i] * 1e6 for r in runs[False]]
             b = [r[i] * 1e6 for r in runs[True]]
             ma, mb = statistics.median(a), statistics.median(b)
@@ -104,10 +133,10 @@ def ab_main():
             say(f"{H:4d} {Win:4d} | {a[0]:7.1f} {a[1]:7.1f} {a[2]:7.1f} | {b[0]:7.1f} {b[1]:7.1f} {b[2]:7.1f} | "
                 f"{ma:7.1f} {mb:7.1f} | {mb / ma:.3f} | {verdict}")
         ta, tb = [sum(r) * 1e3 for r in runs[False]], [sum(r) * 1e3 for r in runs[True]]
-        say("total of the 45 launches (ms): p3 " + " ".join(f"{t:.2f}" for t in ta) + "   p4 "
+        say(f"total of the {len(shapes)} launches (ms): p3 " + " ".join(f"{t:.2f}" for t in ta) + "   p4 "
             + " ".join(f"{t:.2f}" for t in tb) + f"   ranges {max(ta) - min(ta):.2f} / {max(tb) - min(tb):.2f}"
             + f"   medians {statistics.median(ta):.2f} -> {statistics.median(tb):.2f}")
-    if not ONLY or WG:
+    if not ONLY or WG or C33:
         import flow2gan_amd
         from flow2gan_amd import harness
         from flow2gan_amd.models.config import get_gan_config, get_generator_config
@@ -143,18 +172,21 @@ def ab_main():
         for rep in range(3):
             for on in (False, True):
                 leg(on)
-                n0 = ops.FP16X3_CONV32_FWD_LAUNCHES, ops.FP16X3_CONV32_DGRAD_LAUNCHES, ops.FP16X3_CONV32_WGRAD_LAUNCHES
+                def launches():
+                    if C33:
+                        return ops.FP16X3_CONV33_FWD_LAUNCHES, ops.FP16X3_CONV33_DGRAD_LAUNCHES, 0
+                    return ops.FP16X3_CONV32_FWD_LAUNCHES, ops.FP16X3_CONV32_DGRAD_LAUNCHES, ops.FP16X3_CONV32_WGRAD_LAUNCHES
+                n0 = launches()
                 torch.cuda.synchronize()
                 t0 = time.perf_counter()
                 for _ in range(nsteps):
                     stage2()
                 torch.cuda.synchronize()
                 per[on].append((time.perf_counter() - t0) * 1e3 / nsteps)
-                counts[on] = ((ops.FP16X3_CONV32_FWD_LAUNCHES - n0[0]) // nsteps,
-                              (ops.FP16X3_CONV32_DGRAD_LAUNCHES - n0[1]) // nsteps,
-                              (ops.FP16X3_CONV32_WGRAD_LAUNCHES - n0[2]) // nsteps)
+                counts[on] = tuple((a - b) // nsteps for a, b in zip(launches(), n0))
         what = "fp16x3_conv32_wgrad alone off against on, the other band-conv tunables as shipped" if WG \
-            else "tunables off against on"
+            else ("fp16x3_conv33_fwd / fp16x3_conv33_dgrad alone off against on, the other band-conv tunables as "
+                  "shipped" if C33 else "tunables off against on")
         say(f"\n== the stage-2 step (B = {Bn}, F2G_GEMM=fp16x3), {what}: ms per step, blocks of "
             f"{nsteps} steps, three alternating pairs")
         for rep in range(3):
