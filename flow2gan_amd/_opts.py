@@ -22,7 +22,9 @@ fp16x3_conv32_fwd, fp16x3_conv32_dgrad (F2G_GEMM=fp16x3: the MRD (3, 9) band lay
 fp16x3 kernels that scale each tile's patch inside the kernel; both off by default), fp16x3_conv32_wgrad (the same
 layers' weight gradient on the fp16x3 kernel that keeps one running scale per operand and block; off by default),
 fp16x3_conv33_fwd, fp16x3_conv33_dgrad (F2G_GEMM=fp16x3: the MRD (3, 3) fifth layer's forward / data gradient on the
-fp16x3 kernel that scales each whole-row tile's patch inside the kernel, csrc/conv33h3.hip; both off by default).
+fp16x3 kernel that scales each whole-row tile's patch inside the kernel, csrc/conv33h3.hip; both off by default),
+fp16x3_conv33_wgrad (that layer's weight gradient on the fp16x3 kernel that keeps one running scale per operand and
+block over its walk of whole-row tiles, csrc/conv33h3w.hip; off by default).
 
 Environment switches that remain on their own (user-facing, or needed before anything is imported):
 F2G_GEMM (arithmetic of the GEMMs), F2G_STREAMS (launch lanes), F2G_DETERMINISTIC (no splits on the library's

@@ -82,6 +82,13 @@ inline c32_tiling c32_pick_tiles(int H, int W, int W_also = 0) {
 // a tile is R WHOLE rows of a W-column band image, staged with a zero column on either side and a row above / below
 constexpr int P33 = 352;                 // staged pixels of a tile: (R + 2) * (W + 2) <= P33
 constexpr int T33 = 9;                   // taps
+// its weight gradients (conv33_wgrad6_kernel, conv33h3w.hip: conv33_wgrad3h_kernel) stage patch and gradient rows in
+// one padded flat order, a k step = 16 consecutive flat positions
+constexpr int W33_GP = 352;      // gradient positions of a tile: R * (W + 2) rounded up to a k step
+constexpr int W33_XP = 384;      // input positions: 1 + (R + 2) * (W + 2) + the last k step's overhang
+constexpr int W33_GPL = W33_GP * 64, W33_XPL = W33_XP * 64;   // bytes of one plane of 64-byte pixels
+// (largest input position a fragment touches: (R + 2) * (W + 2) + 17; gradient positions: R * (W + 2) + 15)
+static_assert(P33 + 18 <= W33_XP && P33 <= W33_GP, "plane sizes");
 
 // rows per tile: R * W <= 256 pixels where the staged patch allows it; 0 = not even one row fits (W > 112)
 inline int c33_pick_rows(int H, int W) {

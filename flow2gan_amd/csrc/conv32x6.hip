@@ -786,11 +786,7 @@ __global__ __launch_bounds__(512, 1) void conv33_x6_kernel(const f2g_conv32_desc
 // ds_read_b64_tr_b16 (conv32_s2_wgrad6_kernel's scheme).  A k step = 16 consecutive flat positions; the block's
 // 8 waves take the k steps round-robin and keep all nine 32 x 32 tap tiles (144 accumulator registers) over ALL
 // tiles of their persistent block -- 3 gradient + 27 input fragments per 54 MFMAs -- and meet once at the end:
-// tap by tap through LDS, one atomic per output and block.
-constexpr int W33_GP = 352;      // gradient positions of a tile: R * (W + 2) rounded up to a k step
-constexpr int W33_XP = 384;      // input positions: 1 + (R + 2) * (W + 2) + the last k step's overhang
-constexpr int W33_GPL = W33_GP * 64, W33_XPL = W33_XP * 64;
-
+// tap by tap through LDS, one atomic per output and block.  (W33_GP, W33_XP: conv32_common.h.)
 __global__ __launch_bounds__(512, 1) void conv33_wgrad6_kernel(const f2g_conv32_desc d, float* gw, int R,
                                                                int tiles_h, int ntiles) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smb[];
@@ -956,7 +952,8 @@ extern "C" int f2g_conv33_fwd(const f2g_conv32_desc* d, f2g_stream_t stream) {
   return f2g_check_launch();
 }
 
-// Weight gradient of that layer, fp32 class (precision 4 is refused: conv33_wgrad6_kernel has no fp16x3 twin): x =
+// Weight gradient of that layer, fp32 class (precision 4 is refused here: the fp16x3 twin of conv33_wgrad6_kernel
+// has an entry point of its own, f2g_conv33_wgrad_h3 in conv33h3w.hip): x =
 // the layer's input (S, H, W, 32), y = the gradient of its pre-activation (S, H, W, 32; both optionally strided
 // slices of wider maps), gw (32, 9 * 32) [co][tap][ci] +=.
 extern "C" int f2g_conv33_wgrad(const f2g_conv32_desc* d, float* gw, f2g_stream_t stream) {
@@ -976,8 +973,6 @@ extern "C" int f2g_conv33_wgrad(const f2g_conv32_desc* d, float* gw, f2g_stream_
   if (nt >= (1ll << 30)) return F2G_EINVAL;
   constexpr size_t smem = (size_t)3 * (W33_XPL + W33_GPL);
   static_assert(smem >= (size_t)8 * 16 * 64 * 4, "the flush reuses the planes as its reduction buffer");
-  // (largest input position a fragment touches: (R + 2) * (W + 2) + 17; gradient positions: R * (W + 2) + 15)
-  static_assert(P33 + 18 <= W33_XP && P33 <= W33_GP, "plane sizes");
   c32_lds_once<conv33_wgrad6_kernel>(smem);
   const int grid = (int)(nt < 256 ? nt : 256);          // one resident block per CU: 256 x 9216 atomics at most
   hipLaunchKernelGGL(conv33_wgrad6_kernel, dim3(grid), dim3(512), smem, (hipStream_t)stream, *d, gw, R, tiles_h,

@@ -1097,19 +1097,21 @@ def _timed_conv(name, flops, shape, *args):
 # F2G_GEMM=fp16x3: the (3, 9) band layers' forward / data gradient on the fp16x3 kernels that scale every tile's patch
 # inside the kernel (conv32h3.hip, f2g_conv32_desc.precision = 4), their weight gradient on the kernel that keeps one
 # running scale per operand and block (conv32h3w.hip, f2g_conv32_s2_wgrad_h3); the (3, 3) fifth layer's forward /
-# data gradient on the fp16x3 twin of conv33_x6_kernel (conv33h3.hip, f2g_conv33_fwd at precision 4).  All off by
-# default; the (3, 3) layer's weight gradient and the first layer stay on their precision-3 kernels either way (tests
-# and tools/conv32_probe.py flip them)
+# data gradient on the fp16x3 twin of conv33_x6_kernel (conv33h3.hip, f2g_conv33_fwd at precision 4), its weight
+# gradient on the twin of conv33_wgrad6_kernel (conv33h3w.hip, f2g_conv33_wgrad_h3).  All off by default; the first
+# layer stays on its precision-3 kernels either way (tests and tools/conv32_probe.py flip them)
 FP16X3_CONV32_FWD = opt("fp16x3_conv32_fwd", False)
 FP16X3_CONV32_DGRAD = opt("fp16x3_conv32_dgrad", False)
 FP16X3_CONV32_WGRAD = opt("fp16x3_conv32_wgrad", False)
 FP16X3_CONV33_FWD = opt("fp16x3_conv33_fwd", False)
 FP16X3_CONV33_DGRAD = opt("fp16x3_conv33_dgrad", False)
+FP16X3_CONV33_WGRAD = opt("fp16x3_conv33_wgrad", False)
 FP16X3_CONV32_FWD_LAUNCHES = 0      # launches conv32_s2_fwd3h_kernel took (tests and tools)
 FP16X3_CONV32_DGRAD_LAUNCHES = 0    # launches conv32_s2_dgrad3h_kernel took
 FP16X3_CONV32_WGRAD_LAUNCHES = 0    # launches conv32_s2_wgrad3h_kernel took
 FP16X3_CONV33_FWD_LAUNCHES = 0      # launches conv33_h3_kernel took in the forward role (form 0)
 FP16X3_CONV33_DGRAD_LAUNCHES = 0    # ... in the data-gradient role (form 1)
+FP16X3_CONV33_WGRAD_LAUNCHES = 0    # launches conv33_wgrad3h_kernel took
 
 
 def conv32_f16_image(w):
@@ -1200,7 +1202,9 @@ def conv33(x, S: int, H: int, W: int, w_packed, bias, slope: float, y, x_off: in
 def conv33_wgrad(x, g, S: int, H: int, W: int, gw, g_off: int = 0, g_line=None, g_seq=None):
     """Weight gradient of the (3, 3) band layer, fp32 class (conv32x6.hip: conv33_wgrad6_kernel): x (S, H, W, 32)
     the layer's input, g the gradient of its pre-activation -- a band's slice of the concatenated gradient map
-    (g_off floats in, line / sequence strides in floats) --, gw (32, 9 * 32) [co][tap][ci] +=."""
+    (g_off floats in, line / sequence strides in floats) --, gw (32, 9 * 32) [co][tap][ci] +=.  In the fp16x3 mode with
+    the fp16x3_conv33_wgrad tunable on: the fp16x3 kernel (conv33h3w.hip: f2g_conv33_wgrad_h3, precision 4)."""
+    global FP16X3_CONV33_WGRAD_LAUNCHES
     d = L.Conv32Desc()
     d.x, d.x_line, d.x_seq = ptr(x), W * 32, H * W * 32
     d.S, d.H, d.Win, d.Wout = S, H, W, W
@@ -1208,7 +1212,12 @@ def conv33_wgrad(x, g, S: int, H: int, W: int, gw, g_off: int = 0, g_line=None, 
     d.y = ptr(g) + 4 * g_off
     d.y_line = g_line if g_line is not None else W * 32
     d.y_seq = g_seq if g_seq is not None else H * d.y_line
-    _timed_conv("f2g_conv33_wgrad", 2.0 * S * H * W * 32 * 9 * 32, (2, 32, 9 * 32, S * H * W), C.byref(d), ptr(gw))
+    name = "f2g_conv33_wgrad"
+    if FP16X3 and GEMM_PRECISION == 3 and CONV32_X6 and FP16X3_CONV33_WGRAD:
+        d.precision = 4
+        name = "f2g_conv33_wgrad_h3"
+        FP16X3_CONV33_WGRAD_LAUNCHES += 1
+    _timed_conv(name, 2.0 * S * H * W * 32 * 9 * 32, (2, 32, 9 * 32, S * H * W), C.byref(d), ptr(gw))
     return gw
 
 

@@ -734,8 +734,9 @@ typedef struct {
    * transposed tiles as an (864, 32) matrix (ld = K = 32) --, patch / gradient tiles are split while they
    * are staged; wgrad takes the fp32 operands as they are.
    * 4 = fp16x3 products (two scaled fp16 pieces per value, three MFMAs per product: f2g_gemm_desc.precision 4;
-   * conv32h3.hip), fwd and dgrad only (wgrad, f2g_conv33_wgrad and f2g_conv2ch_* refuse it; f2g_conv33_fwd takes it
-   * over its own 9216-float matrix, see there): `w` is ONE
+   * conv32h3.hip), fwd and dgrad only (wgrad, f2g_conv33_wgrad and f2g_conv2ch_* refuse it -- the two weight gradients have
+   * entry points of their own, f2g_conv32_s2_wgrad_h3 and f2g_conv33_wgrad_h3 --; f2g_conv33_fwd takes it over its own
+   * 9216-float matrix, see there): `w` is ONE
    * f2g_split_f16x2_seq run (nseq = 1, seq_floats = 27648) over the same matrix as for 3 -- 128 bytes per 32-float
    * row segment: 32 hi halves, then 32 lo halves -- with its one reciprocal scale at float 27648 of `w`.  The
    * patch / gradient tile is scaled inside the kernel while it is staged: one power of two per tile and launch,
@@ -790,11 +791,24 @@ int f2g_conv32_s2_wgrad_h3(const f2g_conv32_desc* d, float* gw, f2g_stream_t str
  *     |error| <= 3 * 2^-22 sum |a||w| + 2^-28 (amax_patch sum_k |w_k| + wmax sum_k |a_k|).  A patch whose maximum is
  *     zero or not finite is staged unscaled.  Apart from the colsum atomics the result is bit-reproducible. */
 int f2g_conv33_fwd(const f2g_conv32_desc* d, f2g_stream_t stream);
-/* Weight gradient of that layer (discriminators.py:171-181 backward), fp32 class (precision = 3; 4 is refused): x = the layer's
+/* Weight gradient of that layer (discriminators.py:171-181 backward), fp32 class (precision = 3; 4 is refused here and
+ * taken by f2g_conv33_wgrad_h3): x = the layer's
  * input (S, H, W, 32), y = the gradient of its pre-activation (S, H, W, 32) -- both optionally strided slices of
  * wider maps through x_line / x_seq, y_line / y_seq --, gw (32, 9 * 32) [co][tap][ci] += sum over the pixels; W <= 112.
  * The caller zero-initialises gw (blocks accumulate atomically).  w / bias / slope / mask fields unused. */
 int f2g_conv33_wgrad(const f2g_conv32_desc* d, float* gw, f2g_stream_t stream);
+/* The same weight gradient on fp16x3 products (conv33h3w.hip): precision must be 4 (F2G_EINVAL otherwise); roles,
+ * alignment, strides and size limits as f2g_conv33_wgrad (x, y and gw non-null, x and y 16-byte aligned, line and
+ * sequence strides multiples of 4 floats, Win == Wout == W <= 112, W * 32 <= line strides < 2^24, fewer than 2^30
+ * tiles; S, H or W <= 0: F2G_OK, nothing touched; a refused call launches nothing).  Tiles (R whole rows, as
+ * f2g_conv33_fwd) and walk are f2g_conv33_wgrad's: min(ntiles, 256) blocks, block b takes the tiles b, b + grid, ...
+ * Both operands are split inside the kernel under ONE MONOTONE RUNNING SCALE per operand and block: the largest
+ * magnitude met so far in the block's walk (x: every float of the rows h0 - 1 .. h0 + R of a tile's patch, halo rows
+ * included, nothing outside the map; y: the tile's R x W gradient rows; a zero or non-finite tile leaves it alone),
+ * the stored sums rescaled when it moves.  Per output: |error| <= 3 * 2^-22 sum |g||x| + 2^-28 sum_T (xrun_T
+ * sum_{px in T} |g| + grun_T sum_{px in T} |x|), xrun_T / grun_T the running maxima in force at tile T.  A separate
+ * symbol, so that f2g_conv33_wgrad keeps refusing precision 4. */
+int f2g_conv33_wgrad_h3(const f2g_conv32_desc* d, float* gw, f2g_stream_t stream);
 
 /* First layer of every MRD band stack, Conv2d(2, 32, (3, 9), stride 1, padding (1, 4))
  * (discriminators.py:171,195-203), as direct kernels (conv2ch.hip).  The input is a frequency band

@@ -12,8 +12,10 @@ fp16x3_conv32_wgrad alone differing between the legs and the other two band-conv
 the (3, 3) fifth layer instead -- every band width of the three resolutions after the three stride-2 layers, 15
 shapes: forward (S = 128), plain data gradient (S = 64), masked data gradient + column sums (S = 128) --, the
 precision-3 f2g_conv33_fwd launch (conv32x6.hip: conv33_x6_kernel) against its precision-4 launch (conv33h3.hip:
-conv33_h3_kernel), then the stage-2 step with fp16x3_conv33_fwd / fp16x3_conv33_dgrad alone differing.  OUT=path: the
-report is written there as well."""
+conv33_h3_kernel), then the stage-2 step with fp16x3_conv33_fwd / fp16x3_conv33_dgrad alone differing.  ONLY=wgrad33:
+that layer's weight gradient at the same 15 shapes (S = 128), the precision-3 f2g_conv33_wgrad launch (conv32x6.hip:
+conv33_wgrad6_kernel) against f2g_conv33_wgrad_h3 (conv33h3w.hip: conv33_wgrad3h_kernel), then the stage-2 step with
+fp16x3_conv33_wgrad alone differing.  OUT=path: the report is written there as well."""
 import os, sys, ctypes as C
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -64,12 +66,15 @@ def ab_main():
 
     WG = ONLY == "wgrad"                       # the weight-gradient tunable alone differs between the legs
     C33 = ONLY == "conv33"                     # the (3, 3) layer's two tunables alone differ between the legs
-    only = "" if C33 else ONLY
-    shapes = list(band33_shapes() if C33 else band_shapes())
+    WG33 = ONLY == "wgrad33"                   # the (3, 3) layer's weight-gradient tunable alone differs
+    only = "" if C33 or WG33 else ONLY
+    shapes = list(band33_shapes() if C33 or WG33 else band_shapes())
 
     def leg(on):
         if WG:
             ops.FP16X3_CONV32_WGRAD = on
+        elif WG33:
+            ops.FP16X3_CONV33_WGRAD = on
         elif C33:
             ops.FP16X3_CONV33_FWD = ops.FP16X3_CONV33_DGRAD = on
         else:
@@ -77,12 +82,15 @@ def ab_main():
 
     say(f"# tools/conv32_probe.py AB=1  {L.version()}  {torch.cuda.get_device_name(0)}")
     say("# p3 = f2g_conv32_desc.precision 3 (conv32x6.hip), p4 = precision 4 (conv32h3.hip; weight gradient: "
-        "conv32h3w.hip; ONLY=conv33: conv33h3.hip), the same library, F2G_GEMM=fp16x3,")
+        "conv32h3w.hip; ONLY=conv33: conv33h3.hip; ONLY=wgrad33: conv33h3w.hip), the same library, F2G_GEMM=fp16x3,")
     say("# one process, legs alternating p3 1, p4 1, p3 2, p4 2, p3 3, p4 3; us per launch (10 launches after 3)")
     for title, S, kind in (("forward", 128, "fwd"), ("plain data gradient (S = 64)", 64, "dgrad"),
                            ("masked data gradient + column sums (S = 128)", 128, "mask"),
-                           ("weight gradient (S = 128)", 128, "wgrad")):
-        if (kind == "wgrad") != WG or (only and not kind.startswith(only) and not (only == "dgrad" and kind == "mask")):
+                           ("weight gradient (S = 128)", 128, "wgrad"),
+                           ("(3, 3) weight gradient (S = 128)", 128, "wgrad33")):
+        if (kind == "wgrad33") != WG33:
+            continue
+        if not WG33 and ((kind == "wgrad") != WG or (only and not kind.startswith(only) and not (only == "dgrad" and kind == "mask"))):
             continue
         runs = {False: [], True: []}
         for rep in range(3):
@@ -90,7 +98,12 @@ def ab_main():
                 leg(on)
                 ts = []
                 for H, Win, Wout in shapes:
-                    if C33:
+                    if WG33:
+                        x = torch.randn(S * H * Win, 32, device=dev)
+                        gy = torch.randn(S * H * Win, 32, device=dev)
+                        gw = torch.zeros(32, 9 * 32, device=dev)
+                        ts.append(timeit(lambda: ops.conv33_wgrad(x, gy, S, H, Win, gw)))
+                    elif C33:
                         x = torch.randn(S * H * Win, 32, device=dev)
                         y = torch.empty(S * H * Win, 32, device=dev)
                         if kind == "fwd":
@@ -136,7 +149,7 @@ def ab_main():
         say(f"total of the {len(shapes)} launches (ms): p3 " + " ".join(f"{t:.2f}" for t in ta) + "   p4 "
             + " ".join(f"{t:.2f}" for t in tb) + f"   ranges {max(ta) - min(ta):.2f} / {max(tb) - min(tb):.2f}"
             + f"   medians {statistics.median(ta):.2f} -> {statistics.median(tb):.2f}")
-    if not ONLY or WG or C33:
+    if not ONLY or WG or C33 or WG33:
         import flow2gan_amd
         from flow2gan_amd import harness
         from flow2gan_amd.models.config import get_gan_config, get_generator_config
@@ -173,6 +186,8 @@ def ab_main():
             for on in (False, True):
                 leg(on)
                 def launches():
+                    if WG33:
+                        return 0, 0, ops.FP16X3_CONV33_WGRAD_LAUNCHES
                     if C33:
                         return ops.FP16X3_CONV33_FWD_LAUNCHES, ops.FP16X3_CONV33_DGRAD_LAUNCHES, 0
                     return ops.FP16X3_CONV32_FWD_LAUNCHES, ops.FP16X3_CONV32_DGRAD_LAUNCHES, ops.FP16X3_CONV32_WGRAD_LAUNCHES
@@ -185,6 +200,7 @@ def ab_main():
                 per[on].append((time.perf_counter() - t0) * 1e3 / nsteps)
                 counts[on] = tuple((a - b) // nsteps for a, b in zip(launches(), n0))
         what = "fp16x3_conv32_wgrad alone off against on, the other band-conv tunables as shipped" if WG \
+            else "fp16x3_conv33_wgrad alone off against on, the other band-conv tunables as shipped" if WG33 \
             else ("fp16x3_conv33_fwd / fp16x3_conv33_dgrad alone off against on, the other band-conv tunables as "
                   "shipped" if C33 else "tunables off against on")
         say(f"\n== the stage-2 step (B = {Bn}, F2G_GEMM=fp16x3), {what}: ms per step, blocks of "
