@@ -1,5 +1,5 @@
 // What more than one of the GEMM translation units needs (gemm.hip, gemm_lean.hip, gemm_wgrad.hip, gemm_x6.hip,
-// gemm_x6p.hip, gemm_f16.hip, gemm_f16p.hip, gemm_f16wt.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
+// gemm_x6p.hip, gemm_f16.hip, gemm_f16p.hip, gemm_f16p3.hip, gemm_f16wt.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
 // three-piece split, the LDS barrier, the lab switches, and the host functions that cross those files.  Everything
 // defined here has internal linkage; no GEMM file includes another.  (gemm_f16_common.h: what only fp16x3 shares.)
 #pragma once
@@ -18,14 +18,18 @@ bool f2g_leanw_fp32_takes(const f2g_gemm_desc& d, int split);
 int f2g_launch_leanw(const f2g_gemm_desc& d, int pieces, int split, hipStream_t st);
 // gemm_x6.hip: form 0 at precision 3 (checks the descriptor, picks the kernel, launches)
 int f2g_gemm_x6(const f2g_gemm_desc& d, hipStream_t st);
-// gemm_f16.hip: precision 4 -- decides which of the four fp16x3 kernels a descriptor belongs to (its own two: form 0
-// over f2g_split_f16x2 images, form 2 over f2g_split_f16x2_cols images; the two below), checks it, launches that one
+// gemm_f16.hip: precision 4 -- decides which of the five fp16x3 kernels a descriptor belongs to (its own two: form 0
+// over f2g_split_f16x2 images, form 2 over f2g_split_f16x2_cols images; the three below), checks it, launches that one
 int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st);
 // gemm_f16p.hip: precision 4, form 0 over stride-1 windows of 5 or 2 positions of a halo map (gemm_h3p_kernel).
 // f2g_h3p_ok: 1 = runs as handed over (both operands f2g_split_f16x2_seq images with their reciprocal scales), 2 = once
 // both fp32 operands are replaced by those images, 0 = not for this kernel; `taps` receives 5 or 2
 int f2g_h3p_ok(const f2g_gemm_desc& d, int* taps);
 int f2g_launch_h3p(const f2g_gemm_desc& d, int taps, hipStream_t st);
+// gemm_f16p3.hip: precision 4, form 0 over STRIDE-3 windows of 5 positions of a halo map with a multiple of 128
+// channels (gemm_h3p3_kernel: the MPD's strided forward layers).  f2g_h3p3_ok answers as f2g_h3p_ok does
+int f2g_h3p3_ok(const f2g_gemm_desc& d);
+int f2g_launch_h3p3(const f2g_gemm_desc& d, hipStream_t st);
 // gemm_f16wt.hip: precision 4, form 2 over unbounded stride-1 windows of 5 positions of a halo map (gemm_h3wt_kernel:
 // the tap-walking weight gradient).  f2g_h3wt_ok: 1 = runs as handed over (A and the whole map as
 // f2g_split_f16x2_cols images with their reciprocal scales), 2 = once both fp32 operands are replaced by those
@@ -122,6 +126,18 @@ inline bool x6_tap_ok(const f2g_gemm_desc& d, int taps) {
   if (A.P0 < 8 || HpIn < A.P0) return false;
   // staged positions of a tile: its rows, the taps' overhang, the extra positions of every sequence end inside
   return 128 + taps - 1 + (HpIn - A.P0) * (128 / A.P0 + 1) <= 160;
+}
+
+// stride-3 conv windows of 5 positions x C channels over a halo map image (gemm_h3p3_kernel, whose planes hold
+// `plane` entries: a group's 128 rows, one entry more per sequence they touch, one for the taps' overhang).
+// unit % 128 == 0: the kernel is for the MPD's 128- and 512-channel strided layers, as gemm_h3wt_kernel is for the
+// 1024-channel one, and a stride-3 descriptor with fewer channels is declined, never handed to another fp16x3 kernel
+inline bool x6_tap3_ok(const f2g_gemm_desc& d, int plane) {
+  const f2g_operand& A = d.A;
+  if (host_plain(A) || A.P1 != 1 || A.step0 != 3 || A.unit < 128 || (A.unit % 128)) return false;
+  if (A.cols != 5 * A.unit || A.seglen < A.cols || (A.seq_stride % A.unit) || (A.pad0 > 0)) return false;
+  if (A.P0 < 8 || A.L0u > A.seq_stride) return false;
+  return 130 + 126 / A.P0 <= plane;
 }
 
 // Raises the dynamic-LDS limit of the kernels KERNS to `bytes`, the first time a launcher comes by.

@@ -831,8 +831,8 @@ extern "C" int32_t f2g_gemm_colsum_part_rows(const f2g_gemm_desc* dp) {
   if (!dp || (dp->precision != 3 && dp->precision != 4) || dp->form != 0) return 0;
   f2g_gemm_desc d = *dp;
   if (d.E.colsum_part_ld <= 0) d.E.colsum_part_ld = 4;          // (alignment of the pointers is the caller's)
-  // precision 4: the tap-walking kernel alone has the wide epilogue (gemm_f16p.hip; 256-row tiles)
-  if (d.precision == 4) return f2g_h3p_ok(d, nullptr) ? 4 * ((d.A.rows + 255) / 256) : 0;
+  // precision 4: the tap-walking kernels alone have the wide epilogue (gemm_f16p.hip, gemm_f16p3.hip; 256-row tiles)
+  if (d.precision == 4) return f2g_h3p_ok(d, nullptr) || f2g_h3p3_ok(d) ? 4 * ((d.A.rows + 255) / 256) : 0;
   if (!x6_wide(d)) return 0;
   const int M = d.A.rows;
   switch (x6_choose(d).kind) {

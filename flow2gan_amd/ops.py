@@ -1021,7 +1021,7 @@ def _fp16x3_gemm(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offse
     the library about `d` as it will be launched (d.precision = 4; f2g_gemm_f16_ok decides which kernel that is).
     True: one took the launch -- d.A / d.B are its images, its counter went up.  False: the launch goes the bf16x6
     way (d.precision may be left at 4: gemm() sets it)."""
-    global FP16X3_LAUNCHES, FP16X3_WGRAD_LAUNCHES, FP16X3_TAP_LAUNCHES, FP16X3_TAPW_LAUNCHES
+    global FP16X3_LAUNCHES, FP16X3_WGRAD_LAUNCHES, FP16X3_TAP_LAUNCHES, FP16X3_TAPW_LAUNCHES, FP16X3_TAP3_LAUNCHES
     if not (GEMM_PRECISION == 3 and FP16X3) or A.split != 0 or Bm.split != 0 or out.dtype != torch.float32:
         return False
 
@@ -1066,6 +1066,18 @@ def _fp16x3_gemm(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offse
         if _ask_with_x3_out(d, out, out_offset, x3_out, prelu_out, takes):
             d.A, d.B = _f16_seq_operand(A), _f16_seq_operand(Bm)
             FP16X3_TAP_LAUNCHES += 1
+            if x3_out and d.E.x3_out:
+                out._f2g_x3 = out._f2g_x3_buf
+            return True
+        d.E.x3_out = None
+    if form == 0 and A.P1 == 1 and A.P0 > 1 and A.step0 == 3 and A.cols == 5 * A.unit and A.unit % 128 == 0 \
+            and A.rows >= FP16X3_TAP3_MIN_ROWS and not atomic and split_k <= 1 and _f16_seq_window_ok(A):
+        # fp16x3 over stride-3 windows of 5 positions of a contiguous halo map with a multiple of 128 channels (the
+        # MPD's 128 -> 512 and 512 -> 1024 forward layers): the stride-1 route's images, scales, epilogue and x3_out
+        # image on gemm_h3p3_kernel.  What the library declines goes the bf16x6 way
+        if _ask_with_x3_out(d, out, out_offset, x3_out, prelu_out, takes):
+            d.A, d.B = _f16_seq_operand(A), _f16_seq_operand(Bm)
+            FP16X3_TAP3_LAUNCHES += 1
             if x3_out and d.E.x3_out:
                 out._f2g_x3 = out._f2g_x3_buf
             return True
@@ -1498,6 +1510,14 @@ FP16X3_TAP_LAUNCHES = 0    # launches gemm_h3p_kernel took (tests and tools)
 # lower it; F2G_OPTS=fp16x3_tapw_min_rows=1 turns it on)
 FP16X3_TAPW_MIN_ROWS = opt("fp16x3_tapw_min_rows", FP16X3_TAP_OFF)
 FP16X3_TAPW_LAUNCHES = 0   # launches gemm_h3wt_kernel took (tests and tools)
+# fewest output rows at which a forward-form GEMM over STRIDE-3 windows of 5 positions of a halo map with a multiple of
+# 128 channels (the MPD's 128 -> 512 and 512 -> 1024 forward layers) goes to gemm_h3p3_kernel: the map pays
+# f2g_split_f16x2_seq per call, the weight's image is cached, exactly as for the stride-1 route above.
+# profiles/fp16x3_tap3_shapes.txt (tools/fp16x3_tap_shapes.py, legs fwd3 / fwd4) has what was measured.  The route
+# ships off whatever that file says -- turning it on is a change of its own, as for the other fp16x3 routes:
+# FP16X3_TAP_OFF = disabled (tests and the tool lower it; F2G_OPTS=fp16x3_tap3_min_rows=1 turns it on)
+FP16X3_TAP3_MIN_ROWS = opt("fp16x3_tap3_min_rows", FP16X3_TAP_OFF)
+FP16X3_TAP3_LAUNCHES = 0   # launches gemm_h3p3_kernel took (tests and tools)
 
 
 def set_gemm_precision(name: str) -> None:

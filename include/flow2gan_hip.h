@@ -88,7 +88,7 @@ typedef struct {
    *    operand B of the tap-walking weight gradient -- unbounded stride-1 windows of 5 positions over a halo map:
    *    the image of the WHOLE contiguous map as a (map rows, unit) matrix, `unit` scales);
    * 7: `base` holds the flat two-piece fp16 image written by f2g_split_f16x2_seq (precision 4, form 0, over stride-1
-   *    windows of 5 or 2 positions only): operand A = windows over a halo map, the image of the contiguous buffer
+   *    windows of 5 or 2 positions or stride-3 windows of 5 positions only): operand A = windows over a halo map, the image of the contiguous buffer
    *    the windows address -- same addressing as the fp32 buffer, element e in the 128 bytes at (e / 32) * 128 --
    *    with one run per sequence (`seq_stride` floats) and `rscale` = one reciprocal scale per SEQUENCE, rows / P0
    *    floats; operand B = the plain weight matrix with one run per row (row stride % 32 == 0), `rows` scales */
@@ -197,7 +197,8 @@ typedef struct {
    *     taps shift ROWS of the map, so one scale per column of the whole map leaves every tap's sum), both given as
    *     f2g_split_f16x2_cols images (split = 6 with rscale);
    *     form 0 over stride-1 windows of 5 or 2 positions of a halo map against a plain weight matrix, both given as
-   *     f2g_split_f16x2_seq images (split = 7 with rscale: one scale per sequence, which leaves every window's sum).
+   *     f2g_split_f16x2_seq images (split = 7 with rscale: one scale per sequence, which leaves every window's sum);
+   *     form 0 over stride-3 windows of 5 positions of a halo map with unit % 128 == 0, over the same images.
    *     A descriptor f2g_gemm_f16_ok does not answer with 1 is F2G_EINVAL, never run elsewhere. */
   int32_t precision;
   int32_t _pad3;
@@ -319,7 +320,14 @@ int f2g_split_f16x2_cols(float* dst, float* rscale, uint32_t* work, const float*
  * accumulation, no bf16 output, no split-K.  Error: 3 * 2^-22 |a| |b| per product plus at most 2^-28 amax_seq
  * sum_k |b[n,k]| per output (elements 2^-28 below their sequence's largest are subnormal in hi).  Library option
  * x6p applies (0 off, 1 chip-filling grids only, 2 any grid).  f2g_gemm_f16_ok answers 1 / 2 / 0 as for the other
- * forms; f2g_gemm_last_kernel reports "h3p<taps=5>" / "h3p<taps=2>", path 6. */
+ * forms; f2g_gemm_last_kernel reports "h3p<taps=5>" / "h3p<taps=2>", path 6.
+ * STRIDE-3 windows of 5 positions (step0 == 3, cols == 5 * unit: the MPD's strided forward layers) over the same
+ * images go to a kernel of their own with the same arithmetic, tiles, epilogue, error bound and answers.  Its
+ * conditions: unit % 128 == 0 (it is for the 128- and 512-channel layers; a stride-3 descriptor with fewer channels
+ * is F2G_EINVAL, never run on another precision-4 kernel), pad0 <= 0, P1 == 1, seq_stride % unit == 0, L0u <=
+ * seq_stride, P0 >= 8 and 130 + 126 / P0 <= 144 (the entries of one residue plane of its staging area: 128 rows,
+ * one more per sequence they touch, one for the taps' overhang -- whatever the distance between the sequences).
+ * f2g_gemm_last_kernel reports "h3p<taps=5,step=3>", path 6. */
 int f2g_split_f16x2_seq(float* dst, float* rscale, const float* src, int64_t ld, int32_t nseq, int32_t seq_floats,
                         f2g_stream_t stream);
 

@@ -19,8 +19,17 @@ with the route off, fp16x3 with the route on.
 The tool, whose purpose is to measure the route, sets the threshold itself: --min-rows, default 1 = every launch the
 library accepts goes to the new kernel.  The header of the output states the command it was made with.
 
+--tap3 measures the STRIDE-3 route instead (gemm_h3p3_kernel, ops.FP16X3_TAP3_MIN_ROWS; default output
+profiles/fp16x3_tap3_shapes.txt), the stride-1 route staying as shipped:
+  fwd3    the forward of the 128 -> 512 stride-3 layer (five taps, K = 640; bias + leaky ReLU, halo row map, the
+          result's bf16x3 image -- as _mpd_forward_one launches it)
+  fwd4    the forward of the 512 -> 1024 stride-3 layer (K = 2560; the same epilogue)
+per period at B = 64 and for periods 2 and 11 at B = 32 and 16, under the same timing conditions (fp16x3 = the map's
+f2g_split_f16x2_seq pass plus the kernel; bf16x6 = gemm_x6_kernel over a three-piece image made once outside the timed
+region), then the stage-2 step in the fp16x3 mode with that tunable alone differing, in three alternating pairs.
+
     python tools/fp16x3_tap_shapes.py [--out profiles/fp16x3_tap_shapes.txt] [--append] [--no-shapes] [--no-steps]
-                                      [--min-rows R]
+                                      [--min-rows R] [--tap3]
 """
 import argparse
 import os
@@ -95,6 +104,53 @@ def cases(ops, FD, p, dev, batch=B):
     return out
 
 
+def cases3(ops, FD, p, dev, batch=B):
+    """(name, rows, K, N, fn) of the two stride-3 forwards of period p at `batch` clips"""
+    S, hs = 2 * batch * p, heights(p)
+    g = torch.Generator().manual_seed(100 + p)
+    out = []
+    for name, l in (("fwd3", 2), ("fwd4", 3)):
+        Cin, Cout, H, Hout = FD.MPD_CH[l], FD.MPD_CH[l + 1], hs[l], hs[l + 1]
+        x = FD._halo_rows(S, H, Cin, dev, x3=True)
+        FD.unhalo(x, S, H).copy_(torch.randn(S, H, Cin, generator=g).to(dev))
+        if getattr(x, "_f2g_x3_buf", None) is not None:      # the producer's image, made once
+            x._f2g_x3 = ops.x3_flat_image(x)
+        y = FD._halo_rows(S, Hout, Cout, dev, x3=True)
+        w = torch.nn.Parameter((torch.randn(Cout, Cin, 5, 1, generator=g) * (5 * Cin) ** -0.5).to(dev))
+        b = torch.randn(Cout, generator=g).to(dev)
+        wp = ops.derived(w, "pack", FD.pack_conv_weight)
+
+        def fn(x=x, y=y, wp=wp, b=b, H=H, Hout=Hout, Cin=Cin, Cout=Cout):
+            ops.gemm(ops.win1d(x, S, H + 2 * FD.HALO, Cin, Hout, 3, 0, 5), ops.mat(wp), y, bias=b, lrelu=FD.SLOPE,
+                     rowmap=FD._halo_map(Hout, Cout), x3_out=True)
+        out.append((name, S * Hout, 5 * Cin, Cout, fn))
+    return out
+
+
+def shapes3_table(ops, dev, say):
+    from flow2gan_amd import fused_disc as FD
+    ops.set_gemm_precision("bf16x6")        # (the maps' three-piece images are reserved in this mode only)
+    say("batch period  launch     rows      K      N  bf16x6_us  spread  fp16x3_us  spread  ratio  beyond spread  "
+        "TFLOP/s(fp16x3)  kernels")
+    seen = []
+    for batch, periods in ((B, PERIODS), (32, (2, 11)), (16, (2, 11))):
+        for p in periods:
+            for name, rows, K, N, fn in cases3(ops, FD, p, dev, batch):
+                n0 = ops.FP16X3_TAP3_LAUNCHES
+                per, kern = time_blocks(ops, fn)
+                taken = ops.FP16X3_TAP3_LAUNCHES > n0
+                (a, sa), (b, sb) = med_spread(per["bf16x6"]), med_spread(per["fp16x3"])
+                verdict = "-" if not taken else ("wins" if b / a < 1.0 - max(sa, sb) else
+                                                 ("loses" if b / a > 1.0 + max(sa, sb) else "inside"))
+                say(f"{batch:5d} {p:6d}  {name:7s} {rows:7d} {K:6d} {N:6d} {a:10.1f} {sa:7.3f} {b:10.1f} {sb:7.3f} "
+                    f"{b / a:6.3f}  {verdict:13s} {2.0 * rows * K * N / b * 1e-6:12.1f}      "
+                    f"{kern['bf16x6']} | {kern['fp16x3']}" + ("" if taken else "   (not taken by the library)"))
+                seen.append(verdict)
+            torch.cuda.empty_cache()
+    say(f"# launches: {len(seen)}; fp16x3 wins by more than the spread: {seen.count('wins')}, loses by more than the "
+        f"spread: {seen.count('loses')}, inside the spread: {seen.count('inside')}, not taken: {seen.count('-')}")
+
+
 def shapes_table(ops, dev, say):
     from flow2gan_amd import fused_disc as FD
     ops.set_gemm_precision("bf16x6")        # (the maps' three-piece images are reserved in this mode only)
@@ -129,7 +185,7 @@ def shapes_table(ops, dev, say):
             "more than its spread" + ("" if lost else "; no launch the library accepts loses"))
 
 
-def steps_table(ops, dev, say, min_rows, steps=4):
+def steps_table(ops, dev, say, min_rows, steps=4, tap3=False):
     import flow2gan_amd
     from flow2gan_amd import harness
     from flow2gan_amd.models.config import get_gan_config, get_generator_config
@@ -157,10 +213,17 @@ def steps_table(ops, dev, say, min_rows, steps=4):
 
     legs = (("bf16x6", "bf16x6", ops.FP16X3_TAP_OFF), ("fp16x3 route off", "fp16x3", ops.FP16X3_TAP_OFF),
             ("fp16x3 route on", "fp16x3", min_rows))
+    if tap3:        # the fp16x3 mode as shipped, the stride-3 tunable alone differing: three alternating pairs
+        legs, counter, blocks = legs[1:], "FP16X3_TAP3_LAUNCHES", 3
+    else:
+        counter, blocks = "FP16X3_TAP_LAUNCHES", 7
 
     def enter(leg):
         ops.set_gemm_precision(leg[1])
-        ops.FP16X3_TAP_MIN_ROWS = leg[2]
+        if tap3:
+            ops.FP16X3_TAP3_MIN_ROWS = leg[2]
+        else:
+            ops.FP16X3_TAP_MIN_ROWS = leg[2]
 
     per = {leg[0]: [] for leg in legs}
     launches = {leg[0]: 0 for leg in legs}
@@ -168,23 +231,29 @@ def steps_table(ops, dev, say, min_rows, steps=4):
         enter(leg)
         stage2(), stage2()
     torch.cuda.synchronize()
-    for _ in range(7):
+    for _ in range(blocks):
         for leg in legs:
             enter(leg)
-            n0 = ops.FP16X3_TAP_LAUNCHES
+            n0 = getattr(ops, counter)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(steps):
                 stage2()
             torch.cuda.synchronize()
             per[leg[0]].append((time.perf_counter() - t0) * 1e3 / steps)
-            launches[leg[0]] = max(launches[leg[0]], (ops.FP16X3_TAP_LAUNCHES - n0) // steps)
-    say("# stage-2 step: medians of 7 alternating blocks of 4 steps per leg; spread = (max - min) / median")
-    say("stage-2 step        ms  spread  ratio to bf16x6  tap-route launches per step")
-    base = med_spread(per["bf16x6"])[0]
-    for leg in legs:
-        m, s = med_spread(per[leg[0]])
-        say(f"{leg[0]:17s} {m:7.2f} {s:7.3f} {m / base:8.3f}          {launches[leg[0]]}")
+            launches[leg[0]] = max(launches[leg[0]], (getattr(ops, counter) - n0) // steps)
+    say(f"# stage-2 step: medians of {blocks} alternating blocks of 4 steps per leg; spread = (max - min) / median")
+    if tap3:
+        say("stage-2 step        ms   min..max of the leg's blocks   stride-3 route launches per step")
+        for leg in legs:
+            say(f"{leg[0]:17s} {med_spread(per[leg[0]])[0]:7.2f}   {min(per[leg[0]]):7.2f}..{max(per[leg[0]]):7.2f}"
+                f"                  {launches[leg[0]]}")
+    else:
+        say("stage-2 step        ms  spread  ratio to bf16x6  tap-route launches per step")
+        base = med_spread(per["bf16x6"])[0]
+        for leg in legs:
+            m, s = med_spread(per[leg[0]])
+            say(f"{leg[0]:17s} {m:7.2f} {s:7.3f} {m / base:8.3f}          {launches[leg[0]]}")
     off, on = med_spread(per["fp16x3 route off"]), med_spread(per["fp16x3 route on"])
     say(f"# route on / route off (the same mode, the route alone differing): {on[0] / off[0]:.3f} "
         f"(spreads {on[1]:.3f} / {off[1]:.3f})")
@@ -192,18 +261,21 @@ def steps_table(ops, dev, say, min_rows, steps=4):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fp16x3_tap_shapes.txt"))
+    ap.add_argument("--out", default=None, help="default profiles/fp16x3_tap_shapes.txt (--tap3: fp16x3_tap3_shapes.txt)")
+    ap.add_argument("--tap3", action="store_true", help="measure the stride-3 route (legs fwd3 / fwd4) instead")
     ap.add_argument("--append", action="store_true", help="add this run's table to --out instead of replacing it")
     ap.add_argument("--no-steps", action="store_true")
     ap.add_argument("--no-shapes", action="store_true")
     ap.add_argument("--min-rows", type=int, default=1, help="ops.FP16X3_TAP_MIN_ROWS for this run (1: every launch "
                     "of the table on the new kernel)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "fp16x3_tap3_shapes.txt" if args.tap3 else "fp16x3_tap_shapes.txt")
     assert torch.cuda.is_available(), "needs an MI355X"
     from flow2gan_amd import ops
     if args.min_rows < 1 or args.min_rows >= ops.FP16X3_TAP_OFF:
         ap.error("--min-rows must enable the route: both modes would time the same bf16x6 launch otherwise")
-    was_rows = ops.FP16X3_TAP_MIN_ROWS
+    was_rows, was_rows3 = ops.FP16X3_TAP_MIN_ROWS, ops.FP16X3_TAP3_MIN_ROWS
     dev = torch.device("cuda")
     lines = []
 
@@ -213,20 +285,24 @@ def main():
 
     given = [a for i, a in enumerate(sys.argv[1:], 1) if a != "--out" and sys.argv[i - 1] != "--out"]
     say("# command (the output path aside): python tools/fp16x3_tap_shapes.py " + " ".join(given))
-    say(f"# tools/fp16x3_tap_shapes.py  {ops.L.version()}  FP16X3_TAP_MIN_ROWS={args.min_rows} "
-        f"X6_MIN_K={ops.X6_MIN_K}  {torch.cuda.get_device_name(0)}")
+    say(f"# tools/fp16x3_tap_shapes.py  {ops.L.version()}  "
+        + (f"FP16X3_TAP3_MIN_ROWS={args.min_rows} FP16X3_TAP_MIN_ROWS={was_rows} " if args.tap3 else
+           f"FP16X3_TAP_MIN_ROWS={args.min_rows} ") + f"X6_MIN_K={ops.X6_MIN_K}  {torch.cuda.get_device_name(0)}")
     say("# per-launch medians of 5 alternating blocks of 12 launches (us), the map's image pass included in the fp16x3 "
         "leg; spread = (max - min) / median of a mode's blocks; ratio = fp16x3 / bf16x6 (< 1: fp16x3 faster)")
     from test_hip_gemm_f16 import mode_name       # (the one place that names the mode in force)
     was = mode_name(ops)
     try:
-        if not args.no_shapes:
+        if not args.no_shapes and args.tap3:
+            ops.FP16X3_TAP3_MIN_ROWS = args.min_rows
+            shapes3_table(ops, dev, say)
+        elif not args.no_shapes:
             ops.FP16X3_TAP_MIN_ROWS = args.min_rows
             shapes_table(ops, dev, say)
         if not args.no_steps:
-            steps_table(ops, dev, say, args.min_rows)
+            steps_table(ops, dev, say, args.min_rows, tap3=args.tap3)
     finally:
-        ops.FP16X3_TAP_MIN_ROWS = was_rows
+        ops.FP16X3_TAP_MIN_ROWS, ops.FP16X3_TAP3_MIN_ROWS = was_rows, was_rows3
         ops.set_gemm_precision(was)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "a" if args.append else "w") as f:
