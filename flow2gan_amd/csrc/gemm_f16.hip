@@ -3,7 +3,8 @@
 // f2g_split_f16x2_cols writes the images of K-major operands (one scale per column), gemm_h3w_kernel reads those.
 // (gemm_f16p.hip: f2g_split_f16x2_seq and gemm_h3p_kernel, the same over stride-1 windows of a halo map;
 // gemm_f16p3.hip: gemm_h3p3_kernel, the same over stride-3 windows; gemm_f16wt.hip: gemm_h3wt_kernel, the weight
-// gradient of a stride-1 layer over column images.)  The five kernels share
+// gradient of a stride-1 layer over column images; gemm_f16ws.hip: gemm_h3ws_kernel, that of a stride-3 layer.)  The
+// six kernels share
 // gemm_f16_common.h, the image writers split_f16.h; h3_route_of below says which kernel a descriptor belongs to.
 #include <stddef.h>
 #include <stdint.h>
@@ -357,11 +358,12 @@ inline bool h3w_operand_ok(const f2g_operand& S) {
 }
 
 // The ONE route decision of precision 4: the kernel a descriptor belongs to -- gemm_h3_kernel, gemm_h3w_kernel,
-// gemm_h3p_kernel (gemm_f16p.hip), gemm_h3p3_kernel (gemm_f16p3.hip), gemm_h3wt_kernel (gemm_f16wt.hip) --, what f2g_gemm_f16_ok answers for it (0: not for
+// gemm_h3p_kernel (gemm_f16p.hip), gemm_h3p3_kernel (gemm_f16p3.hip), gemm_h3wt_kernel (gemm_f16wt.hip),
+// gemm_h3ws_kernel (gemm_f16ws.hip) --, what f2g_gemm_f16_ok answers for it (0: not for
 // that kernel; 1: runs as handed over, both operands the kernel's images with their reciprocal scales; 2: once both
 // fp32 operands are replaced by those images) and the taps of H3_TAP.  The shape of the operands picks the candidate,
 // the candidate's own conditions decide: a descriptor one kernel declines is never offered to another.
-enum h3_kernel { H3_NONE, H3_PLAIN, H3_WGRAD, H3_TAP, H3_TAP3, H3_TAPW };
+enum h3_kernel { H3_NONE, H3_PLAIN, H3_WGRAD, H3_TAP, H3_TAP3, H3_TAPW, H3_TAPW3 };
 struct h3_route {
   h3_kernel kernel = H3_NONE;
   int status = 0, taps = 0;
@@ -392,9 +394,10 @@ h3_route h3_route_of(const f2g_gemm_desc& d) {
   h3_kernel cand = H3_NONE;
   if (!d.A.base || !d.B.base || !d.E.C) return r;
   if (d.form == 2) {
-    // B a window operand: the tap-walking weight gradient or nothing
-    cand = d.precision == 4 && host_plain(d.A) && !host_plain(d.B) ? H3_TAPW : H3_WGRAD;
-    r.status = cand == H3_TAPW ? f2g_h3wt_ok(d) : h3w_ok(d);
+    // B a window operand: a tap-walking weight gradient (the windows' stride says which: 3 gemm_h3ws_kernel, anything
+    // else gemm_h3wt_kernel) or nothing
+    cand = d.precision == 4 && host_plain(d.A) && !host_plain(d.B) ? (d.B.step0 == 3 ? H3_TAPW3 : H3_TAPW) : H3_WGRAD;
+    r.status = cand == H3_TAPW3 ? f2g_h3ws_ok(d) : (cand == H3_TAPW ? f2g_h3wt_ok(d) : h3w_ok(d));
   } else if (d.form == 0) {
     // windows of a halo map, or f2g_split_f16x2_seq images: a tap-walking kernel (the windows' stride says which:
     // 3 gemm_h3p3_kernel, anything else gemm_h3p_kernel) or nothing
@@ -417,13 +420,16 @@ int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st) {
     f2g_set_error("f2g_gemm precision 4: form 0 over f2g_split_f16x2 images, or form 2 over f2g_split_f16x2_cols "
                   "images, of two plain matrices, or form 0 over f2g_split_f16x2_seq images of stride-1 windows of 5 or "
                   "2 positions or of stride-3 windows of 5 positions over a multiple of 128 channels, or form 2 + atomic over f2g_split_f16x2_cols images of a plain matrix and of the map "
-                  "under unbounded stride-1 windows of 5 positions (f2g_gemm_f16_ok(d) != 1 for this descriptor)");
+                  "under unbounded stride-1 windows of 5 positions, or of stride-3 windows of 5 positions that overhang a "
+                  "sequence of seq_stride / unit map rows by at most pad0 rows (f2g_gemm_f16_ok(d) != 1 for this "
+                  "descriptor)");
     return F2G_EINVAL;
   }
   switch (r.kernel) {
     case H3_TAP: return f2g_launch_h3p(d, r.taps, st);
     case H3_TAP3: return f2g_launch_h3p3(d, st);
     case H3_TAPW: return f2g_launch_h3wt(d, st);
+    case H3_TAPW3: return f2g_launch_h3ws(d, st);
     case H3_WGRAD: {
       const int M = d.A.cols, N = d.B.cols, K = d.A.rows, split = d.split_k > 1 ? d.split_k : 1;
       const int kchunk = ((K + split - 1) / split + BK - 1) / BK * BK;

@@ -1,5 +1,6 @@
 // The GEMM side of fp16x3 (split_f16.h has the image side), shared by gemm_h3_kernel and gemm_h3w_kernel
-// (gemm_f16.hip), gemm_h3p_kernel (gemm_f16p.hip) and gemm_h3wt_kernel (gemm_f16wt.hip): the fragment type, the
+// (gemm_f16.hip), gemm_h3p_kernel (gemm_f16p.hip), gemm_h3wt_kernel (gemm_f16wt.hip) and gemm_h3ws_kernel
+// (gemm_f16ws.hip): the fragment type, the
 // K-major fragment read, the three MFMAs of a product tile, zeroing and rescaling the two accumulator sets.  What a
 // kernel stages and where its fragments and scales lie stay with the kernel.  Internal linkage throughout.
 #pragma once
@@ -9,12 +10,14 @@ namespace {
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-// K-major fragment read (gemm_common.h: tr_frag, the bf16 kernels') out of planes whose rows lie PITCH bytes apart
-template <int PITCH>
+// K-major fragment read (gemm_common.h: tr_frag, the bf16 kernels') out of planes whose rows lie PITCH bytes apart;
+// the second half of the read -- four reduction rows further -- lies HALF plane rows further (4, or 4 * stride where
+// consecutive reduction rows are `stride` plane rows apart: gemm_h3ws_kernel)
+template <int PITCH, int HALF = 4>
 __device__ __forceinline__ f16x8 tr_frag_f16(const unsigned char* p) {
   typedef s16x4 __attribute__((address_space(3))) * lds_p;
   const s16x4 a = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p));
-  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p + 4 * PITCH));
+  const s16x4 b = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_p)(p + HALF * PITCH));
   const s16x8 v = __builtin_shufflevector(a, b, 0, 1, 2, 3, 4, 5, 6, 7);
   return __builtin_bit_cast(f16x8, v);
 }

@@ -1022,6 +1022,7 @@ def _fp16x3_gemm(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offse
     True: one took the launch -- d.A / d.B are its images, its counter went up.  False: the launch goes the bf16x6
     way (d.precision may be left at 4: gemm() sets it)."""
     global FP16X3_LAUNCHES, FP16X3_WGRAD_LAUNCHES, FP16X3_TAP_LAUNCHES, FP16X3_TAPW_LAUNCHES, FP16X3_TAP3_LAUNCHES
+    global FP16X3_TAPW3_LAUNCHES
     if not (GEMM_PRECISION == 3 and FP16X3) or A.split != 0 or Bm.split != 0 or out.dtype != torch.float32:
         return False
 
@@ -1052,6 +1053,16 @@ def _fp16x3_gemm(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offse
         # library declines goes the bf16x6 way
         d.A, d.B = _f16_cols_operand(A), _f16_cols_window_operand(Bm)
         FP16X3_TAPW_LAUNCHES += 1
+        return True
+    if wgrad and a_plain and Bm.P1 == 1 and Bm.P0 > 1 and Bm.step0 == 3 and Bm.unbounded \
+            and Bm.cols == 5 * Bm.unit and Bm.unit % 128 == 0 and A.rows >= FP16X3_TAPW3_MIN_ROWS \
+            and _f16_cols_window_ok(Bm) and takes():
+        # fp16x3 tap-walking weight gradient of a STRIDE-3 five-tap layer (the MPD's 128 -> 512 and 512 -> 1024
+        # layers): tap and stride only select rows of the map, so the stride-1 route's two column images serve as they
+        # are -- the gradient's, and one of the whole map -- on gemm_h3ws_kernel.  What the library declines goes the
+        # bf16x6 way
+        d.A, d.B = _f16_cols_operand(A), _f16_cols_window_operand(Bm)
+        FP16X3_TAPW3_LAUNCHES += 1
         return True
     if form == 0 and A.P1 == 1 and A.P0 > 1 and A.step0 == 1 and A.cols in (5 * A.unit, 2 * A.unit) \
             and A.rows >= FP16X3_TAP_MIN_ROWS and A.cols >= X6_MIN_K and not atomic and split_k <= 1 \
@@ -1518,6 +1529,19 @@ FP16X3_TAPW_LAUNCHES = 0   # launches gemm_h3wt_kernel took (tests and tools)
 # FP16X3_TAP_OFF = disabled (tests and the tool lower it; F2G_OPTS=fp16x3_tap3_min_rows=1 turns it on)
 FP16X3_TAP3_MIN_ROWS = opt("fp16x3_tap3_min_rows", FP16X3_TAP_OFF)
 FP16X3_TAP3_LAUNCHES = 0   # launches gemm_h3p3_kernel took (tests and tools)
+# fewest reduction rows at which the weight gradient of a STRIDE-3 five-tap layer over a halo map with a multiple of 128
+# channels (the MPD's 128 -> 512 and 512 -> 1024 layers; ops.wgrad over unbounded windows) goes to gemm_h3ws_kernel:
+# the gradient and the whole map pay f2g_split_f16x2_cols per call, exactly as for the stride-1 route above, against
+# gemm_leanw6s_kernel's in-kernel split.  Measured per launch, both image calls included, on one box
+# (tools/fp16x3_tapw_shapes.py --step3 -> profiles/fp16x3_tapw3_shapes.txt): no launch wins by more than its spread --
+# the 512 -> 1024 layer 0.91-0.93 of the bf16x6 time at B = 64 and 1.05-1.07 at B = 16, inside the spread in all ten
+# launches; the 128 -> 512 layer LOSES in all ten, 1.8-1.9 at B = 64 and 2.4-2.5 at B = 16 (the image passes of its long
+# thin map cost more than the launch they replace); the stage-2 step 147.33 -> 147.95 ms, inside the legs' ranges.
+# The route ships off whatever that file says -- turning it on is a change of its own, as for the
+# other fp16x3 routes: FP16X3_TAP_OFF = disabled (tests and the tool lower it; F2G_OPTS=fp16x3_tapw3_min_rows=1 turns
+# it on)
+FP16X3_TAPW3_MIN_ROWS = opt("fp16x3_tapw3_min_rows", FP16X3_TAP_OFF)
+FP16X3_TAPW3_LAUNCHES = 0  # launches gemm_h3ws_kernel took (tests and tools)
 
 
 def set_gemm_precision(name: str) -> None:

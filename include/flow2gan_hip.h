@@ -294,7 +294,14 @@ int f2g_gemm_f16_ok(const f2g_gemm_desc* d);
  * rows included: zero rows stay zero and do not move a column's maximum --, B.rscale its `unit` scales.  The rescale
  * (acc0 + 2^-11 acc1) * rscale_a[co] * rscale_b[ci] precedes the atomic add, so the K chunks the launcher cuts add up.
  * f2g_gemm_f16_ok answers 1 / 2 / 0 as above; every other window operand at form 2 is 0 (F2G_EINVAL from f2g_gemm).
- * f2g_gemm_last_kernel reports "h3wt<taps=5>", path 6. */
+ * f2g_gemm_last_kernel reports "h3wt<taps=5>", path 6.
+ * The STRIDE-3 form of that window operand is taken too: gw[co][t * unit + ci] += sum over (s, p) of g[s * P0 + p][co]
+ * x[s * HpIn + 3 p + t - pad0][ci] (gemm_h3ws_kernel, what gemm_leanw6s_kernel runs at precision 3: the MPD's 128 ->
+ * 512 and 512 -> 1024 layers).  The conditions above with step0 == 3, seq_stride % unit == 0 instead of == P0 * unit
+ * (a sequence has HpIn = seq_stride / unit map rows, the map (B.rows / P0) * HpIn in all) and windows that overhang a
+ * sequence by at most pad0 rows at either end: 3 * (P0 - 1) + 5 - pad0 <= HpIn + pad0.  Tap and stride only select
+ * rows, so the images, the scales and the rescale before the atomic add are the same; the launcher cuts chunks of
+ * whole sequences.  A step0 other than 1 or 3 is 0.  f2g_gemm_last_kernel reports "h3ws<taps=5,step=3>", path 6. */
 int f2g_split_f16x2_cols(float* dst, float* rscale, uint32_t* work, const float* src, int64_t ld, int32_t rows,
                          int32_t cols, f2g_stream_t stream);
 /* The image of a HALO MAP whose stride-1 conv windows are the A operand of a precision-4, form-0 GEMM, and of that

@@ -15,8 +15,17 @@ block: the route off and on (the tap route of the forward and data gradient stay
 The tool, whose purpose is to measure the route, sets the threshold itself: --min-rows, default 1 = every launch the
 library accepts goes to the new kernel.  The header of the output states the command it was made with.
 
+--step3 measures the weight gradient of the two STRIDE-3 layers instead (gemm_h3ws_kernel against gemm_leanw6s_kernel,
+ops.FP16X3_TAPW3_MIN_ROWS; default output profiles/fp16x3_tapw3_shapes.txt), the stride-1 route staying as shipped:
+  wgrad3  the 128 -> 512 layer (512 x 640 outputs; the map has heights(p)[2] rows per sequence, the gradient
+          heights(p)[3])
+  wgrad4  the 512 -> 1024 layer (1024 x 2560 outputs; heights(p)[3] -> heights(p)[4])
+per period at B = 64 and B = 16 under the same timing conditions (both image calls inside the fp16x3 leg), then the
+stage-2 step in the fp16x3 mode with that tunable alone differing, in three alternating pairs of blocks, reported as
+medians and within-leg ranges.
+
     python tools/fp16x3_tapw_shapes.py [--out profiles/fp16x3_tapw_shapes.txt] [--append] [--no-shapes] [--no-steps]
-                                       [--min-rows R]
+                                       [--min-rows R] [--step3]
 """
 import argparse
 import os
@@ -53,6 +62,49 @@ def case(ops, FD, p, dev, batch):
     return S * Hp, fn
 
 
+def case3(ops, FD, p, dev, batch, l):
+    """(reduction rows, Cin, Cout, fn) of the stride-3 layer l (2: 128 -> 512, 3: 512 -> 1024) of period p at `batch`
+    clips; the operands are allocated here, outside the timed region"""
+    S, hs = 2 * batch * p, heights(p)
+    Cin, Cout, H, Hout = FD.MPD_CH[l], FD.MPD_CH[l + 1], hs[l], hs[l + 1]
+    Hp = Hout + 2 * FD.HALO
+    g = torch.Generator().manual_seed(10 * p + l)
+    x = FD._halo_rows(S, H, Cin, dev)
+    FD.unhalo(x, S, H).copy_(torch.randn(S, H, Cin, generator=g).to(dev))
+    gy = FD._halo_rows(S, Hout, Cout, dev)
+    FD.unhalo(gy, S, Hout).copy_((torch.randn(S, Hout, Cout, generator=g) * 1e-3).to(dev))
+    gw = torch.zeros(Cout, 5 * Cin, device=dev)
+
+    def fn():
+        ops.wgrad(gy, Cout, Cout, ops.win1d(x, S, H + 2 * FD.HALO, Cin, Hp, 3, 3 * FD.HALO, 5, unbounded=True), gw)
+    return S * Hp, Cin, Cout, fn
+
+
+def shapes3_table(ops, dev, say):
+    from flow2gan_amd import fused_disc as FD
+    say("batch period  launch     rows  bf16x6_us  spread  fp16x3_us  spread  ratio  beyond spread  TFLOP/s(fp16x3)  "
+        "kernels")
+    seen = []
+    for batch in BATCHES:
+        for p in PERIODS:
+            for name, l in (("wgrad3", 2), ("wgrad4", 3)):
+                rows, Cin, Cout, fn = case3(ops, FD, p, dev, batch, l)
+                n0 = ops.FP16X3_TAPW3_LAUNCHES
+                per, kern = time_blocks(ops, fn)
+                assert ops.FP16X3_TAPW3_LAUNCHES > n0 and kern["fp16x3"].startswith("h3ws"), \
+                    f"B {batch} period {p} {name}: the fp16x3 leg never took the route"
+                (a, sa), (b, sb) = med_spread(per["bf16x6"]), med_spread(per["fp16x3"])
+                verdict = "wins" if b / a < 1.0 - max(sa, sb) else ("loses" if b / a > 1.0 + max(sa, sb) else "inside")
+                say(f"{batch:5d} {p:6d}  {name:7s} {rows:7d} {a:10.1f} {sa:7.3f} {b:10.1f} {sb:7.3f} {b / a:6.3f}  "
+                    f"{verdict:13s} {2.0 * rows * Cout * 5 * Cin / b * 1e-6:12.1f}      "
+                    f"{kern['bf16x6']} | {kern['fp16x3']}")
+                seen.append(verdict)
+                del fn
+                torch.cuda.empty_cache()
+    say(f"# launches: {len(seen)}; fp16x3 wins by more than the spread: {seen.count('wins')}, loses by more than the "
+        f"spread: {seen.count('loses')}, inside the spread: {seen.count('inside')}")
+
+
 def shapes_table(ops, dev, say):
     from flow2gan_amd import fused_disc as FD
     say("batch period     rows  bf16x6_us  spread  fp16x3_us  spread  ratio  TFLOP/s(fp16x3)  kernels")
@@ -81,7 +133,7 @@ def shapes_table(ops, dev, say):
         say("# not every accepted launch wins by more than its spread: the default stays off")
 
 
-def steps_table(ops, dev, say, min_rows, steps=4):
+def steps_table(ops, dev, say, min_rows, steps=4, step3=False):
     import flow2gan_amd
     from flow2gan_amd import harness
     from flow2gan_amd.models.config import get_gan_config, get_generator_config
@@ -109,47 +161,61 @@ def steps_table(ops, dev, say, min_rows, steps=4):
 
     legs = (("fp16x3 route off", ops.FP16X3_TAP_OFF), ("fp16x3 route on", min_rows))
     ops.set_gemm_precision("fp16x3")
+    # (--step3: the stride-3 tunable alone differing, three alternating pairs)
+    tunable, counter, blocks = ("FP16X3_TAPW3_MIN_ROWS", "FP16X3_TAPW3_LAUNCHES", 3) if step3 else \
+        ("FP16X3_TAPW_MIN_ROWS", "FP16X3_TAPW_LAUNCHES", 7)
     per = {leg[0]: [] for leg in legs}
     launches = {leg[0]: 0 for leg in legs}
     for name, rows in legs:
-        ops.FP16X3_TAPW_MIN_ROWS = rows
+        setattr(ops, tunable, rows)
         stage2(), stage2()
     torch.cuda.synchronize()
-    for _ in range(7):
+    for _ in range(blocks):
         for name, rows in legs:
-            ops.FP16X3_TAPW_MIN_ROWS = rows
-            n0 = ops.FP16X3_TAPW_LAUNCHES
+            setattr(ops, tunable, rows)
+            n0 = getattr(ops, counter)
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             for _ in range(steps):
                 stage2()
             torch.cuda.synchronize()
             per[name].append((time.perf_counter() - t0) * 1e3 / steps)
-            launches[name] = max(launches[name], (ops.FP16X3_TAPW_LAUNCHES - n0) // steps)
-    say("# stage-2 step (B = 64, fp16x3 mode): medians of 7 alternating blocks of 4 steps per leg; spread = (max - min) "
-        "/ median")
-    say("stage-2 step        ms  spread  tap-walking weight-gradient launches per step")
-    for name, _ in legs:
-        m, s = med_spread(per[name])
-        say(f"{name:17s} {m:7.2f} {s:7.3f}      {launches[name]}")
+            launches[name] = max(launches[name], (getattr(ops, counter) - n0) // steps)
+    say(f"# stage-2 step (B = 64, fp16x3 mode): medians of {blocks} alternating blocks of 4 steps per leg; spread = "
+        "(max - min) / median")
+    if step3:
+        say("stage-2 step        ms   min..max of the leg's blocks   stride-3 weight-gradient launches per step")
+        for name, _ in legs:
+            say(f"{name:17s} {med_spread(per[name])[0]:7.2f}   {min(per[name]):7.2f}..{max(per[name]):7.2f}"
+                f"                  {launches[name]}")
+    else:
+        say("stage-2 step        ms  spread  tap-walking weight-gradient launches per step")
+        for name, _ in legs:
+            m, s = med_spread(per[name])
+            say(f"{name:17s} {m:7.2f} {s:7.3f}      {launches[name]}")
     off, on = med_spread(per["fp16x3 route off"]), med_spread(per["fp16x3 route on"])
     say(f"# route on / route off: {on[0] / off[0]:.3f} (spreads {on[1]:.3f} / {off[1]:.3f})")
 
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fp16x3_tapw_shapes.txt"))
+    ap.add_argument("--out", default=None, help="default profiles/fp16x3_tapw_shapes.txt (--step3: "
+                    "fp16x3_tapw3_shapes.txt)")
+    ap.add_argument("--step3", action="store_true", help="measure the stride-3 layers' weight gradient (legs wgrad3 / "
+                    "wgrad4) instead")
     ap.add_argument("--append", action="store_true", help="add this run's table to --out instead of replacing it")
     ap.add_argument("--no-steps", action="store_true")
     ap.add_argument("--no-shapes", action="store_true")
     ap.add_argument("--min-rows", type=int, default=1, help="ops.FP16X3_TAPW_MIN_ROWS for this run (1: every launch "
                     "of the table on the new kernel)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "fp16x3_tapw3_shapes.txt" if args.step3 else "fp16x3_tapw_shapes.txt")
     assert torch.cuda.is_available(), "needs an MI355X"
     from flow2gan_amd import ops
     if args.min_rows < 1 or args.min_rows >= ops.FP16X3_TAP_OFF:
         ap.error("--min-rows must enable the route: both modes would time the same bf16x6 launch otherwise")
-    was_rows = ops.FP16X3_TAPW_MIN_ROWS
+    was_rows, was_rows3 = ops.FP16X3_TAPW_MIN_ROWS, ops.FP16X3_TAPW3_MIN_ROWS
     dev = torch.device("cuda")
     lines = []
 
@@ -159,20 +225,24 @@ def main():
 
     given = [a for i, a in enumerate(sys.argv[1:], 1) if a != "--out" and sys.argv[i - 1] != "--out"]
     say("# command (the output path aside): python tools/fp16x3_tapw_shapes.py " + " ".join(given))
-    say(f"# tools/fp16x3_tapw_shapes.py  {ops.L.version()}  FP16X3_TAPW_MIN_ROWS={args.min_rows}  "
-        f"{torch.cuda.get_device_name(0)}")
+    say(f"# tools/fp16x3_tapw_shapes.py  {ops.L.version()}  "
+        + (f"FP16X3_TAPW3_MIN_ROWS={args.min_rows} FP16X3_TAPW_MIN_ROWS={was_rows}" if args.step3 else
+           f"FP16X3_TAPW_MIN_ROWS={args.min_rows}") + f"  {torch.cuda.get_device_name(0)}")
     say("# per-launch medians of 5 alternating blocks of 12 launches (us), both column-image calls included in the "
         "fp16x3 leg; spread = (max - min) / median of a mode's blocks; ratio = fp16x3 / bf16x6 (< 1: fp16x3 faster)")
     from test_hip_gemm_f16 import mode_name       # (the one place that names the mode in force)
     was = mode_name(ops)
     try:
-        if not args.no_shapes:
+        if not args.no_shapes and args.step3:
+            ops.FP16X3_TAPW3_MIN_ROWS = args.min_rows
+            shapes3_table(ops, dev, say)
+        elif not args.no_shapes:
             ops.FP16X3_TAPW_MIN_ROWS = args.min_rows
             shapes_table(ops, dev, say)
         if not args.no_steps:
-            steps_table(ops, dev, say, args.min_rows)
+            steps_table(ops, dev, say, args.min_rows, step3=args.step3)
     finally:
-        ops.FP16X3_TAPW_MIN_ROWS = was_rows
+        ops.FP16X3_TAPW_MIN_ROWS, ops.FP16X3_TAPW3_MIN_ROWS = was_rows, was_rows3
         ops.set_gemm_precision(was)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "a" if args.append else "w") as f:
