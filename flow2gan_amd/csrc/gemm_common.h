@@ -1,5 +1,5 @@
 // What more than one of the GEMM translation units needs (gemm.hip, gemm_lean.hip, gemm_wgrad.hip, gemm_x6.hip,
-// gemm_x6p.hip, gemm_f16.hip, gemm_f16p.hip, gemm_f16p3.hip, gemm_f16wt.hip, gemm_f16ws.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
+// gemm_x6p.hip, gemm_f16.hip, gemm_f16p.hip, gemm_f16p3.hip, gemm_f16p3n.hip, gemm_f16wt.hip, gemm_f16ws.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
 // three-piece split, the LDS barrier, the lab switches, and the host functions that cross those files.  Everything
 // defined here has internal linkage; no GEMM file includes another.  (gemm_f16_common.h: what only fp16x3 shares.)
 #pragma once
@@ -30,6 +30,12 @@ int f2g_launch_h3p(const f2g_gemm_desc& d, int taps, hipStream_t st);
 // channels (gemm_h3p3_kernel: the MPD's strided forward layers).  f2g_h3p3_ok answers as f2g_h3p_ok does
 int f2g_h3p3_ok(const f2g_gemm_desc& d);
 int f2g_launch_h3p3(const f2g_gemm_desc& d, hipStream_t st);
+// gemm_f16p3n.hip: the same windows over 32 channels (K = 160, N <= 128: the MPD's 32 -> 128 forward layer), A = the
+// fp32 map itself, marked split = 8 and scaled per sequence segment inside gemm_h3p3n_kernel.  f2g_h3p3n_ok: 1 = runs
+// as handed over (B a f2g_split_f16x2_seq image with its reciprocal scales), 2 = once the fp32 B is replaced by that
+// image, 0 = not for this kernel
+int f2g_h3p3n_ok(const f2g_gemm_desc& d);
+int f2g_launch_h3p3n(const f2g_gemm_desc& d, hipStream_t st);
 // gemm_f16wt.hip: precision 4, form 2 over unbounded stride-1 windows of 5 positions of a halo map (gemm_h3wt_kernel:
 // the tap-walking weight gradient).  f2g_h3wt_ok: 1 = runs as handed over (A and the whole map as
 // f2g_split_f16x2_cols images with their reciprocal scales), 2 = once both fp32 operands are replaced by those

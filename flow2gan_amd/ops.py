@@ -1022,7 +1022,7 @@ def _fp16x3_gemm(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offse
     True: one took the launch -- d.A / d.B are its images, its counter went up.  False: the launch goes the bf16x6
     way (d.precision may be left at 4: gemm() sets it)."""
     global FP16X3_LAUNCHES, FP16X3_WGRAD_LAUNCHES, FP16X3_TAP_LAUNCHES, FP16X3_TAPW_LAUNCHES, FP16X3_TAP3_LAUNCHES
-    global FP16X3_TAPW3_LAUNCHES
+    global FP16X3_TAPW3_LAUNCHES, FP16X3_TAP3N_LAUNCHES
     if not (GEMM_PRECISION == 3 and FP16X3) or A.split != 0 or Bm.split != 0 or out.dtype != torch.float32:
         return False
 
@@ -1080,6 +1080,23 @@ def _fp16x3_gemm(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offse
             if x3_out and d.E.x3_out:
                 out._f2g_x3 = out._f2g_x3_buf
             return True
+        d.E.x3_out = None
+    if form == 0 and A.P1 == 1 and A.P0 > 1 and A.step0 == 3 and A.unit == 32 and A.cols == 160 \
+            and A.rows >= FP16X3_TAP3N_MIN_ROWS and not atomic and split_k <= 1 and _f16_seq_window_ok(A):
+        # fp16x3 over stride-3 windows of 5 positions of a contiguous 32-channel halo map (the MPD's 32 -> 128 forward
+        # layer, K = 160): NO image of the map -- d.A stays the caller's fp32 map, marked split = 8, and
+        # gemm_h3p3n_kernel scales it per sequence segment and splits it while staging; nothing is allocated per
+        # call.  The weight's f2g_split_f16x2_seq image comes from the derived-weight cache.  The output's three-piece
+        # image is written as on the other tap-walking routes (layer 128 -> 512 still reads it).  What the library
+        # declines goes the bf16x6 way
+        d.A.split = 8
+        if _ask_with_x3_out(d, out, out_offset, x3_out, prelu_out, takes):
+            d.B = _f16_seq_operand(Bm)
+            FP16X3_TAP3N_LAUNCHES += 1
+            if x3_out and d.E.x3_out:
+                out._f2g_x3 = out._f2g_x3_buf
+            return True
+        d.A.split = 0
         d.E.x3_out = None
     if form == 0 and A.P1 == 1 and A.P0 > 1 and A.step0 == 3 and A.cols == 5 * A.unit and A.unit % 128 == 0 \
             and A.rows >= FP16X3_TAP3_MIN_ROWS and not atomic and split_k <= 1 and _f16_seq_window_ok(A):
@@ -1529,6 +1546,14 @@ FP16X3_TAPW_LAUNCHES = 0   # launches gemm_h3wt_kernel took (tests and tools)
 # FP16X3_TAP_OFF = disabled (tests and the tool lower it; F2G_OPTS=fp16x3_tap3_min_rows=1 turns it on)
 FP16X3_TAP3_MIN_ROWS = opt("fp16x3_tap3_min_rows", FP16X3_TAP_OFF)
 FP16X3_TAP3_LAUNCHES = 0   # launches gemm_h3p3_kernel took (tests and tools)
+# F2G_GEMM=fp16x3: the fewest output rows at which form 0 over stride-3 windows of five positions of a contiguous
+# 32-CHANNEL halo map (the MPD's 32 -> 128 forward layer, K = 160) takes gemm_h3p3n_kernel (csrc/gemm_f16p3n.hip): the
+# fp32 map is scaled per sequence segment and split INSIDE the kernel -- no image pass, no allocation per call --, the
+# weight image stays in LDS for a block's life.  profiles/fp16x3_tap3n_shapes.txt (tools/fp16x3_tap_shapes.py --tap3n)
+# has what was measured.  The route ships off like the other tap-walking routes: FP16X3_TAP_OFF = disabled (tests and
+# the tool lower it; F2G_OPTS=fp16x3_tap3n_min_rows=1 turns it on)
+FP16X3_TAP3N_MIN_ROWS = opt("fp16x3_tap3n_min_rows", FP16X3_TAP_OFF)
+FP16X3_TAP3N_LAUNCHES = 0  # launches gemm_h3p3n_kernel took (tests and tools)
 # fewest reduction rows at which the weight gradient of a STRIDE-3 five-tap layer over a halo map with a multiple of 128
 # channels (the MPD's 128 -> 512 and 512 -> 1024 layers; ops.wgrad over unbounded windows) goes to gemm_h3ws_kernel:
 # the gradient and the whole map pay f2g_split_f16x2_cols per call, exactly as for the stride-1 route above, against

@@ -91,7 +91,11 @@ typedef struct {
    *    windows of 5 or 2 positions or stride-3 windows of 5 positions only): operand A = windows over a halo map, the image of the contiguous buffer
    *    the windows address -- same addressing as the fp32 buffer, element e in the 128 bytes at (e / 32) * 128 --
    *    with one run per sequence (`seq_stride` floats) and `rscale` = one reciprocal scale per SEQUENCE, rows / P0
-   *    floats; operand B = the plain weight matrix with one run per row (row stride % 32 == 0), `rows` scales */
+   *    floats; operand B = the plain weight matrix with one run per row (row stride % 32 == 0), `rows` scales;
+   * 8: (operand A of a precision-4, form-0 launch only) `base` is the fp32 halo map ITSELF, as for split = 0, and the
+   *    mark says: scale it per sequence segment and split it inside the precision-4 kernel (stride-3 windows of 5
+   *    positions over 32 channels, f2g_split_f16x2_seq below).  There is no image; `rscale` is ignored.  A descriptor
+   *    so marked that fails a condition of that kernel is F2G_EINVAL, never run elsewhere */
   int32_t split;
   const float* alpha;
   const float* lrelu_src;
@@ -198,7 +202,9 @@ typedef struct {
    *     f2g_split_f16x2_cols images (split = 6 with rscale);
    *     form 0 over stride-1 windows of 5 or 2 positions of a halo map against a plain weight matrix, both given as
    *     f2g_split_f16x2_seq images (split = 7 with rscale: one scale per sequence, which leaves every window's sum);
-   *     form 0 over stride-3 windows of 5 positions of a halo map with unit % 128 == 0, over the same images.
+   *     form 0 over stride-3 windows of 5 positions of a halo map with unit % 128 == 0, over the same images;
+   *     form 0 over stride-3 windows of 5 positions of an fp32 halo map with unit == 32 marked split = 8 (scaled and
+   *     split inside the kernel) against a plain weight matrix given as its f2g_split_f16x2_seq image.
    *     A descriptor f2g_gemm_f16_ok does not answer with 1 is F2G_EINVAL, never run elsewhere. */
   int32_t precision;
   int32_t _pad3;
@@ -334,7 +340,25 @@ int f2g_split_f16x2_cols(float* dst, float* rscale, uint32_t* work, const float*
  * is F2G_EINVAL, never run on another precision-4 kernel), pad0 <= 0, P1 == 1, seq_stride % unit == 0, L0u <=
  * seq_stride, P0 >= 8 and 130 + 126 / P0 <= 144 (the entries of one residue plane of its staging area: 128 rows,
  * one more per sequence they touch, one for the taps' overhang -- whatever the distance between the sequences).
- * f2g_gemm_last_kernel reports "h3p<taps=5,step=3>", path 6. */
+ * f2g_gemm_last_kernel reports "h3p<taps=5,step=3>", path 6.
+ * The 32-CHANNEL stride-3 layer (unit == 32, cols == 160: the MPD's 32 -> 128 forward layer) takes NO image of its
+ * map: A is the fp32 halo map itself, marked f2g_operand.split = 8 (rscale ignored), B the weight's image (split = 7,
+ * rscale per row) with N <= 128 rows.  gemm_h3p3n_kernel walks tiles of 128 output rows x all N columns persistently
+ * with the whole weight image resident in LDS.  While it stages the positions the rows of a tile read, it takes one
+ * scale per SEGMENT -- the staged positions of one sequence inside the tile -- by the rule above with "run" read as
+ * "segment" (exponent clamp, all-zero and non-finite cases included), and splits into LDS.  A scale never spans two
+ * sequences and a window never leaves its sequence: every output row has exactly one scale, its sum is exact, and v =
+ * (acc0 + 2^-11 acc1) * rscale_segment[row] * rscale_b[col] goes to the same wide epilogue (everything listed above,
+ * colsum_part_ld and x3_out included).  The maximum is an integer maximum of sign-less bit patterns (thread, the 8
+ * lanes of a position, one LDS word per segment): it does not depend on the order, the launch is reproducible bit for
+ * bit.  Only positions a window of a valid row reads are loaded at all.  Error: the bound above with amax_seq read as
+ * amax_segment (<= amax_seq).  Conditions: unit == 32, step0 == 3, cols == 5 * unit, P1 == 1, pad0 <= 0, seq_stride %
+ * unit == 0, L0u <= seq_stride, P0 >= 8 (at most 17 segments per tile), N % 8 == 0, N <= 128, both bases 16-byte
+ * aligned, byte extents below 0xe0000000, B's row stride % 32 == 0; no atomic accumulation, no bf16 output, no split-K;
+ * library option x6p as above (1: at least 256 row tiles).  f2g_gemm_f16_ok answers 1 for A.split == 8, B.split == 7
+ * with rscale, 2 for A.split == 8, B.split == 0 (= once B is replaced by its image), 0 otherwise; with A.split == 0
+ * every descriptor keeps the answer it had (unit == 32 at stride 3: 0).  f2g_gemm_colsum_part_rows answers for it (two
+ * partial rows per 128-row tile).  f2g_gemm_last_kernel reports "h3p3n<taps=5,step=3>", path 6. */
 int f2g_split_f16x2_seq(float* dst, float* rscale, const float* src, int64_t ld, int32_t nseq, int32_t seq_floats,
                         f2g_stream_t stream);
 

@@ -1,0 +1,386 @@
+"""fp16x3 over STRIDE-3 windows of five positions of a 32-channel halo map, scaled per sequence segment INSIDE the kernel
+(csrc/gemm_f16p3n.hip, gemm_h3p3n_kernel; f2g_operand.split = 8): against float64 over poisoned operands and guarded
+outputs with the helpers of tests/test_hip_gemm_f16_tap.py and tests/test_hip_gemm_routes.py, the descriptors it must
+decline, the ops.gemm route with its tunable and counter, the cached weight image following its weight, and one period
+of the MPD against the CPU oracle.
+
+The A operand is the fp32 map itself: no image, no rscale.  Everything no window of a valid row reads -- the positions
+behind a sequence's last window, the buffer behind the last sequence -- is NaN: one of them entering a segment's
+maximum or the LDS would show in every output of that segment.
+
+Tolerance, per element, as tests/test_hip_gemm_f16_tap.py: 1.8e-6 * (|A| |B|^T + |epilogue terms|) plus the floor term
+2^-28 amax_seq(row) sum_k |w[n,k]| carried through the epilogue like a product's scale; a segment's maximum is at most
+its sequence's, so the per-sequence floor bounds the per-segment one (tests/fp16x3_seg_emul.py has the exact bound)."""
+import ctypes as C
+import math
+import types
+
+import pytest
+import torch
+
+import fp16x3_seq3_emul as emul
+from test_hip_gemm_f16_tap import EINVAL, TOL, case, f16_ok, mode_name, seq_image
+from test_hip_gemm_routes import DEV, NAN, SENT, Out, Vec, check, expect, last_kernel, make_desc, rnd
+
+pytestmark = pytest.mark.gpu
+
+STEP, TAPS = 3, 5
+NAME = "h3p3n<taps=5,step=3>"
+SHAPES = [(3, 100, 32, 128, 2),      # 300 rows: two full 128-row tiles and a partial one; two segments per tile
+          (9, 27, 32, 96, 2),        # Hp = 85, the production period-11 geometry: a tile's rows straddle five or six
+                                     # sequences; a partial column tile
+          (40, 8, 32, 128, 0)]       # the most segments per tile the host rule admits
+
+
+@pytest.fixture(scope="module")
+def ops():
+    if not torch.cuda.is_available():
+        pytest.skip("needs an MI355X")
+    from flow2gan_amd import ops as o
+    return o
+
+
+@pytest.fixture
+def any_grid(lib_option):
+    """library option x6p = 2: the tap-walking kernels take grids that do not fill the chip"""
+    lib_option("x6p", 2)
+
+
+@pytest.fixture
+def tap3n_route(ops, any_grid):
+    """the fp16x3 mode as shipped, with FP16X3_TAP3N_MIN_ROWS = 1 and the library option x6p = 2"""
+    was, was_rows = mode_name(ops), ops.FP16X3_TAP3N_MIN_ROWS
+    ops.set_gemm_precision("fp16x3")
+    ops.FP16X3_TAP3N_MIN_ROWS = 1
+    try:
+        yield ops
+    finally:
+        ops.FP16X3_TAP3N_MIN_ROWS = was_rows
+        ops.set_gemm_precision(was)
+
+
+def seg_case(ops, S, P0, Cc, N, taps=TAPS, seed=0, step=STEP, extra=0):
+    """case() of tests/test_hip_gemm_f16_tap.py with A left the fp32 map and marked split = 8, the positions no window
+    reads poisoned, and B replaced by its f2g_split_f16x2_seq image"""
+    c = case(ops, S, P0, Cc, N, taps, seed=seed, step=step, extra=extra, images=False)
+    read = step * (P0 - 1) + taps
+    c.A.flat[:S * c.Hp * Cc].view(S, c.Hp, Cc)[:, read:] = NAN        # (the float64 products are made already)
+    c.A.o.split = 8
+    seq_image(ops, c.B, N, taps * Cc, c.B.o.seq_stride)
+    return c
+
+
+_CASES = {}
+
+
+def shared_case(ops, i):
+    """the operands, the weight image and the float64 products of SHAPES[i], made once (nothing below writes them)"""
+    if i not in _CASES:
+        S, P0, Cc, N, extra = SHAPES[i]
+        _CASES[i] = seg_case(ops, S, P0, Cc, N, seed=S + N, extra=extra)
+    return _CASES[i]
+
+
+def halo_rowmap(P0, ld):
+    return (P0, (P0 + 4) * ld, ld, 2 * ld)
+
+
+# ------------------------------------------------------------------ GEMM against float64
+def forward_check(ops, c, P0, N):
+    bias = rnd(N, seed=1) * 1e-3
+    out = Out(c.M, N, rowmap=halo_rowmap(P0, N + 8))
+    d = make_desc(ops, c.A, c.B, out, precision=4, bias=bias, lrelu=0.1)
+    assert d.A.split == 8 and not d.A.rscale
+    assert f16_ok(ops, d) == 1
+    ops.call("f2g_gemm", C.byref(d))
+    torch.cuda.synchronize()
+    assert last_kernel(ops) == NAME and ops.L.lib.f2g_gemm_last_path() == 6
+    out.guards_ok()
+    want, m, _, _ = expect(c.acc, c.mag, bias=bias, lrelu=0.1)
+    check(out.got(), want, m, TOL, "forward")
+    return d
+
+
+@pytest.mark.parametrize("i", range(len(SHAPES)))
+def test_forward_epilogue_against_float64(ops, any_grid, i):
+    """bias + leaky ReLU + halo row map (the forward's epilogue); then the same descriptor with B left fp32"""
+    S, P0, Cc, N, extra = SHAPES[i]
+    c = shared_case(ops, i)
+    d = forward_check(ops, c, P0, N)
+    d.B.base, d.B.split, d.B.rscale = c.B.flat.data_ptr() + 4 * c.B.off, 0, None
+    assert f16_ok(ops, d) == 2          # "would run once B is replaced by its image"
+    assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
+
+
+def test_distance_between_sequences_is_free(ops, any_grid):
+    """40 poisoned positions no window reads behind every sequence's last window: accepted, and the same arithmetic"""
+    S, P0, Cc, N, _ = SHAPES[0]
+    forward_check(ops, seg_case(ops, S, P0, Cc, N, seed=11, extra=40), P0, N)
+
+
+@pytest.mark.parametrize("i", range(len(SHAPES)))
+def test_column_sums_mask_and_feature_matching_against_float64(ops, any_grid, i):
+    """row map + leaky-ReLU backward mask + feature-matching term + column sums: the sums once by atomics, once as
+    partial rows"""
+    S, P0, Cc, N, extra = SHAPES[i]
+    c = shared_case(ops, i)
+    rowmap = halo_rowmap(P0, N + 8)
+    out = Out(c.M, N, rowmap=rowmap)
+    y_full, ref_full = rnd(out.flat.numel(), seed=3), rnd(out.flat.numel(), seed=4)
+    wdev = torch.tensor([0.5], device=DEV)
+    fmw = 0.3 * 1e-3
+    cs = Vec(N, 5)
+    d = make_desc(ops, c.A, c.B, out, precision=4, colsum=cs)
+    d.E.mask_src, d.E.mask_slope = y_full.data_ptr() + 4 * out.base, 0.1
+    d.E.fm_ref, d.E.fm_w, d.E.fm_wdev = ref_full.data_ptr() + 4 * out.base, fmw, wdev.data_ptr()
+    assert f16_ok(ops, d) == 1
+    ops.call("f2g_gemm", C.byref(d))
+    torch.cuda.synchronize()
+    assert last_kernel(ops) == NAME and ops.L.lib.f2g_gemm_last_path() == 6
+    out.guards_ok()
+    yy, rr = y_full[out.offs].double(), ref_full[out.offs].double()
+    v = c.acc + fmw * 0.5 * torch.sign(yy - rr)
+    m = c.mag + fmw * 0.5
+    mult = torch.where(yy > 0, torch.ones_like(yy), torch.full_like(yy, 0.1))
+    v, m = v * mult, m * mult
+    check(out.got(), v, m, TOL, "masked output")
+    check(cs.got(), cs.init.double() + v.sum(0), cs.init.double().abs() + m.sum(0), TOL, "colsum")
+    # partial rows: as many as the library says (one per 64 output rows of whole 128-row tiles), plain stores
+    nrows = ops.L.lib.f2g_gemm_colsum_part_rows(C.byref(d))
+    assert nrows == 2 * ((c.M + 127) // 128)
+    parts = torch.full((nrows + 2, N), SENT, device=DEV)
+    out2 = Out(c.M, N, rowmap=rowmap)
+    d.E.C = out2.flat.data_ptr() + 4 * out2.base
+    d.E.colsum, d.E.colsum_part_ld = parts.data_ptr() + 4 * N, N
+    assert f16_ok(ops, d) == 1
+    ops.call("f2g_gemm", C.byref(d))
+    torch.cuda.synchronize()
+    out2.guards_ok()
+    assert torch.equal(out2.got(), out.got())
+    assert bool((parts[0] == SENT).all()) and bool((parts[-1] == SENT).all())
+    check(parts[1:-1].double().sum(0), v.sum(0), m.sum(0), TOL, "partial column sums")
+
+
+def test_x3_out_of_the_row_mapped_forward(ops, any_grid):
+    """the production use of E.x3_out: a forward landing in a halo map through the row map -- the image of the whole
+    contiguous map (zero halo rows included, as x3_reserve leaves them) equals a fresh x3_flat_image of it, and the
+    halo rows stay untouched"""
+    S, P0, Cc, N, extra = SHAPES[1]
+    c = shared_case(ops, 1)
+    Hp, guard = P0 + 4, 64
+    flat = torch.full((guard + S * Hp * N + guard,), SENT, device=DEV)
+    body = flat[guard:guard + S * Hp * N].view(S, Hp, N)
+    body[:] = NAN
+    body[:, :2] = 0.0
+    body[:, Hp - 2:] = 0.0
+    img = torch.full((guard + S * Hp * N * 3 + guard,), 1.0, device=DEV, dtype=torch.bfloat16)
+    img[guard:guard + S * Hp * N * 3] = 0.0
+    bias = rnd(N, seed=2) * 1e-3
+    d = make_desc(ops, c.A, c.B, Out(c.M, N), precision=4, bias=bias, lrelu=0.1)
+    d.E.C, d.E.ldc = flat.data_ptr() + 4 * guard, N
+    d.E.P0o, d.E.seq_stride_o, d.E.row_stride_o, d.E.off_o = halo_rowmap(P0, N)
+    d.E.x3_out = img.data_ptr() + 2 * guard
+    assert f16_ok(ops, d) == 1
+    ops.call("f2g_gemm", C.byref(d))
+    torch.cuda.synchronize()
+    assert last_kernel(ops) == NAME
+    assert bool((flat[:guard] == SENT).all()) and bool((flat[guard + S * Hp * N:] == SENT).all())
+    assert bool((img[:guard] == 1.0).all()) and bool((img[guard + S * Hp * N * 3:] == 1.0).all())
+    assert bool((body[:, :2] == 0).all()) and bool((body[:, Hp - 2:] == 0).all()), "a halo row was written"
+    want, m, _, _ = expect(c.acc, c.mag, bias=bias, lrelu=0.1)
+    check(body[:, 2:2 + P0].reshape(c.M, N).double(), want, m, TOL, "row-mapped forward")
+    image = ops.x3_flat_image(body.reshape(-1).clone())
+    torch.cuda.synchronize()
+    assert torch.equal(img[guard:guard + S * Hp * N * 3].view(torch.int16), image.view(torch.int16))
+
+
+@pytest.mark.parametrize("i", [1, 2])
+def test_three_launches_give_the_same_bits(ops, any_grid, i):
+    c = shared_case(ops, i)
+    bits = []
+    for _ in range(3):
+        out = Out(c.M, c.N)
+        d = make_desc(ops, c.A, c.B, out, precision=4)
+        ops.call("f2g_gemm", C.byref(d))
+        torch.cuda.synchronize()
+        assert last_kernel(ops) == NAME
+        bits.append(out.flat.view(torch.int32).clone())
+    assert torch.equal(bits[0], bits[1]) and torch.equal(bits[0], bits[2])
+
+
+# ------------------------------------------------------------------ refusals
+@pytest.mark.parametrize("what", ["unit64", "step2", "taps2", "pad0", "P0=4", "N=136", "N=100", "misaligned", "grid",
+                                  "unmarked"])
+def test_descriptors_the_kernel_declines(ops, lib_option, what):
+    """f2g_gemm_f16_ok == 0 and F2G_EINVAL from f2g_gemm -- never another kernel; the output stays untouched"""
+    lib_option("x6p", 1 if what == "grid" else 2)      # ("grid": the default option keeps small grids off the kernel)
+    S, P0, Cc, N, extra = SHAPES[0]
+    if what == "P0=4":
+        S, P0 = 75, 4
+    Cc = 64 if what == "unit64" else Cc
+    N = 136 if what == "N=136" else (100 if what == "N=100" else N)
+    c = seg_case(ops, S, P0, Cc, N, taps=2 if what == "taps2" else TAPS, step=2 if what == "step2" else STEP,
+                 extra=extra)
+    out = Out(c.M, N)
+    d = make_desc(ops, c.A, c.B, out, precision=4)
+    if what == "pad0":
+        d.A.pad0 = 1
+    if what == "misaligned":
+        d.A.base += 4
+    if what == "unmarked":
+        # A.split == 0 with unit == 32: what the parent commit answered -- its stride-3 kernel asks for unit % 128 == 0
+        # (gemm_common.h: x6_tap3_ok) and a descriptor it declines is offered to no other kernel
+        d.A.split = 0
+    assert f16_ok(ops, d) == 0
+    assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
+    torch.cuda.synchronize()
+    assert last_kernel(ops) == ""
+    assert bool((out.flat[~torch.isnan(out.flat)] == SENT).all())
+
+
+# ------------------------------------------------------------------ ops.gemm
+def ops_case(ops, seed):
+    S, P0, Cc, N, extra = SHAPES[0]
+    Hp = STEP * (P0 - 1) + TAPS + extra
+    x = rnd(S, Hp, Cc, seed=seed) * torch.logspace(-3, 3, S, device=DEV)[:, None, None]
+    flat = torch.full((S * Hp * Cc + 256 * Cc,), NAN, device=DEV)
+    flat[:S * Hp * Cc] = x.reshape(-1)
+    a = emul.windows(x, P0, TAPS, STEP).double()
+    amax = x.double().abs().reshape(S, -1).amax(1).repeat_interleave(P0)
+    return flat, a, amax, (S, Hp, Cc, P0, N)
+
+
+def test_ops_gemm_takes_the_route_and_counts_it(tap3n_route, monkeypatch):
+    ops = tap3n_route
+    flat, a, amax, (S, Hp, Cc, P0, N) = ops_case(ops, 3)
+    w, bias = torch.nn.Parameter(rnd(N, TAPS * Cc, seed=7, scale=0.1)), rnd(N, seed=8)
+    out = torch.full((S * P0, N), NAN, device=DEV)
+    ops._f16_seq_operand(ops.mat(w))        # (the weight's cached image: built before the launches are watched)
+    seen, images = [], []
+    real_call, real_image = ops.call, ops.split_f16_seq
+
+    def watch_call(name, *args):
+        if name == "f2g_gemm":
+            d = args[0]._obj                # (C.byref's object: the descriptor as it is launched)
+            seen.append((d.A.base, d.A.split, bool(d.A.rscale), d.B.split, bool(d.B.rscale)))
+        return real_call(name, *args)
+
+    def watch_image(*args, **kw):
+        images.append(args)
+        return real_image(*args, **kw)
+
+    def go():
+        ops.gemm(ops.win1d(flat, S, Hp, Cc, P0, STEP, 0, TAPS), ops.mat(w), out, bias=bias, lrelu=0.1)
+        torch.cuda.synchronize()
+
+    n0, t0, t3 = ops.FP16X3_TAP3N_LAUNCHES, ops.FP16X3_TAP_LAUNCHES, ops.FP16X3_TAP3_LAUNCHES
+    with monkeypatch.context() as mp:
+        mp.setattr(ops, "call", watch_call)
+        mp.setattr(ops, "split_f16_seq", watch_image)
+        go()
+    assert ops.FP16X3_TAP3N_LAUNCHES == n0 + 1 and last_kernel(ops) == NAME
+    # no per-call image of A: the launch reads the caller's map itself, and nothing built an image meanwhile
+    assert seen == [(flat.data_ptr(), 8, False, 7, True)]
+    assert images == []
+    wd = w.detach().double()
+    mag = a.abs() @ wd.abs().t() + emul.FLOOR * amax[:, None] * wd.abs().sum(1)[None, :] / TOL
+    want, m, _, _ = expect(a @ wd.t(), mag, bias=bias, lrelu=0.1)
+    check(out.double(), want, m, TOL, "ops.gemm")
+    # below the threshold, with the route off, and in the plain bf16x6 mode: the bf16x6 kernels
+    for rows in (S * P0 + 1, ops.FP16X3_TAP_OFF):
+        ops.FP16X3_TAP3N_MIN_ROWS = rows
+        go()
+        assert ops.FP16X3_TAP3N_LAUNCHES == n0 + 1 and not last_kernel(ops).startswith("h3p")
+    ops.FP16X3_TAP3N_MIN_ROWS = S * P0
+    go()
+    assert ops.FP16X3_TAP3N_LAUNCHES == n0 + 2 and last_kernel(ops) == NAME
+    ops.set_gemm_precision("bf16x6")
+    go()
+    assert ops.FP16X3_TAP3N_LAUNCHES == n0 + 2 and not last_kernel(ops).startswith("h3p")
+    assert ops.FP16X3_TAP_LAUNCHES == t0 and ops.FP16X3_TAP3_LAUNCHES == t3     # (the other tap routes never saw them)
+
+
+def test_weight_images_follow_their_weights(tap3n_route):
+    """after a raw-pointer update (the optimizer's way: bump_weight_epoch + the batched rebuild_derived) and after
+    an autograd-visible in-place update, the next launch reads a rebuilt image and rebuilt scales"""
+    ops = tap3n_route
+    flat, a, amax, (S, Hp, Cc, P0, N) = ops_case(ops, 5)
+    w = torch.nn.Parameter(rnd(N, TAPS * Cc, seed=2))
+    out = torch.empty(S * P0, N, device=DEV)
+
+    def launch_and_check(what):
+        n0 = ops.FP16X3_TAP3N_LAUNCHES
+        ops.gemm(ops.win1d(flat, S, Hp, Cc, P0, STEP, 0, TAPS), ops.mat(w), out)
+        assert ops.FP16X3_TAP3N_LAUNCHES == n0 + 1 and last_kernel(ops) == NAME
+        wd = w.detach().double()
+        mag = a.abs() @ wd.abs().t() + emul.FLOOR * amax[:, None] * wd.abs().sum(1)[None, :] / TOL
+        check(out.double(), a @ wd.t(), mag, TOL, what)
+        buf = ops._f16_seq_operand(ops.mat(w))._keep[0]
+        torch.cuda.synchronize()
+        K = TAPS * Cc
+        img, rs = buf[:N * K].cpu().view(torch.int32).view(N, K), buf[N * K:N * K + N].cpu()
+        want_img, want_rs = emul.image(w.detach().cpu())
+        assert torch.equal(img, want_img) and torch.equal(rs, want_rs), f"{what}: the cached image is stale"
+        return out.clone()
+
+    first = launch_and_check("first launch")
+    factors = torch.logspace(-3, 3, N, device=DEV)
+    version = w._version
+    w.data.copy_(w.detach() * factors[:, None])
+    assert w._version == version            # (invisible to autograd: only the epoch tells the cache)
+    ops.bump_weight_epoch([w])
+    replayed = ops.rebuild_derived([w])
+    assert replayed >= 1 or not ops.EAGER_REBUILD
+    second = launch_and_check("after the raw-pointer update")
+    assert not torch.equal(first, second)
+    with torch.no_grad():
+        w.mul_(-0.37)
+    third = launch_and_check("after the in-place update")
+    assert not torch.equal(second, third)
+
+
+# ------------------------------------------------------------------ one period of the MPD against the CPU oracle
+def test_mpd_period_against_oracle(tap3n_route):
+    """the period-2 sub-discriminator at the shapes of tests/test_hip_disc_autograd.py: score, feature maps, input
+    gradient and every parameter gradient against the oracle at that file's tolerance; the route counts at least one
+    forward launch (the 32 -> 128 layer), and nothing when it is off"""
+    ops = tap3n_route
+    import test_hip_disc_autograd as T
+    do, dh = T._models("mpd")
+    sub_o, sub_h = do.discriminators[0], dh.discriminators[0]
+    _, y_hat = T._inputs()
+
+    def loss_of(score, fmap):
+        gen = torch.Generator().manual_seed(77)
+        loss = torch.relu(1 + score).mean()
+        for m in fmap:
+            loss = loss + (m * torch.randn(m.shape, generator=gen).to(m.device)).sum() / math.sqrt(m.numel())
+        return loss
+
+    def hip_run():
+        for p in sub_h.parameters():
+            p.grad = None
+        yh = y_hat.to(DEV).requires_grad_(True)
+        n0 = ops.FP16X3_TAP3N_LAUNCHES
+        score, fmap = sub_h(yh)
+        n1 = ops.FP16X3_TAP3N_LAUNCHES
+        loss_of(score, fmap).backward()
+        torch.cuda.synchronize()
+        return score, fmap, yh.grad, n1 - n0
+
+    score, fmap, gx, fwd = hip_run()
+    print(f"[h3p3n] period {sub_h.period}: {fwd} forward launches on the route")
+    assert fwd >= 1, "the 32 -> 128 layer's forward never reached the kernel"
+    sides = T._hip_sides(types.SimpleNamespace(discriminators=[sub_h]), "mpd", y_hat.to(DEV))[0]
+    yo = y_hat.clone().requires_grad_(True)
+    do.zero_grad(set_to_none=True)
+    so, fo = T._with_sides(sides, lambda: sub_o(yo))
+    loss_of(so, fo).backward()
+    pairs = [("score", score, so.detach())] + [(f"fmap.{i}", m, fo[i].detach()) for i, m in enumerate(fmap)]
+    pairs += [("y_hat", gx, yo.grad)]
+    pairs += [(k, p.grad, dict(sub_o.named_parameters())[k].grad) for k, p in sub_h.named_parameters()]
+    do.zero_grad(set_to_none=True)
+    T._compare(pairs, "mpd period 2, fp16x3 in-kernel-scaled tap route")
+    ops.FP16X3_TAP3N_MIN_ROWS = ops.FP16X3_TAP_OFF
+    _, _, _, fwd = hip_run()
+    assert fwd == 0

@@ -28,8 +28,18 @@ per period at B = 64 and for periods 2 and 11 at B = 32 and 16, under the same t
 f2g_split_f16x2_seq pass plus the kernel; bf16x6 = gemm_x6_kernel over a three-piece image made once outside the timed
 region), then the stage-2 step in the fp16x3 mode with that tunable alone differing, in three alternating pairs.
 
+--tap3n measures the route of the 32-CHANNEL stride-3 layer (gemm_h3p3n_kernel, ops.FP16X3_TAP3N_MIN_ROWS; default
+output profiles/fp16x3_tap3n_shapes.txt), every other route staying as shipped:
+  fwd2    the forward of the 32 -> 128 stride-3 layer (five taps, K = 160; bias + leaky ReLU, halo row map, the
+          result's bf16x3 image -- as _mpd_forward_one launches it)
+  fwd2-   the same launch without the result's image (E.x3_out unset)
+per period at B = 64 and B = 16.  fp16x3 = the kernel alone: it reads the fp32 map and scales it per sequence segment
+itself, there is no image pass to include; bf16x6 = the launch as that mode routes it (gemm_x6g_kernel, which splits
+the fp32 map inside the kernel: K = 160 < x6_min_k, no image pass either).  Then the stage-2 step in the fp16x3 mode with that
+tunable alone differing, in three alternating pairs.
+
     python tools/fp16x3_tap_shapes.py [--out profiles/fp16x3_tap_shapes.txt] [--append] [--no-shapes] [--no-steps]
-                                      [--min-rows R] [--tap3]
+                                      [--min-rows R] [--tap3 | --tap3n]
 """
 import argparse
 import os
@@ -127,18 +137,40 @@ def cases3(ops, FD, p, dev, batch=B):
     return out
 
 
-def shapes3_table(ops, dev, say):
+def cases3n(ops, FD, p, dev, batch=B):
+    """(name, rows, K, N, fn) of the 32 -> 128 stride-3 forward of period p at `batch` clips, with and without the
+    result's three-piece image"""
+    S, hs = 2 * batch * p, heights(p)
+    g = torch.Generator().manual_seed(200 + p)
+    Cin, Cout, H, Hout = FD.MPD_CH[1], FD.MPD_CH[2], hs[1], hs[2]
+    x = FD._halo_rows(S, H, Cin, dev, x3=True)
+    FD.unhalo(x, S, H).copy_(torch.randn(S, H, Cin, generator=g).to(dev))
+    if getattr(x, "_f2g_x3_buf", None) is not None:      # the producer's image, made once
+        x._f2g_x3 = ops.x3_flat_image(x)
+    y = FD._halo_rows(S, Hout, Cout, dev, x3=True)
+    w = torch.nn.Parameter((torch.randn(Cout, Cin, 5, 1, generator=g) * (5 * Cin) ** -0.5).to(dev))
+    b = torch.randn(Cout, generator=g).to(dev)
+    wp = ops.derived(w, "pack", FD.pack_conv_weight)
+
+    def fn(x3):
+        ops.gemm(ops.win1d(x, S, H + 2 * FD.HALO, Cin, Hout, 3, 0, 5), ops.mat(wp), y, bias=b, lrelu=FD.SLOPE,
+                 rowmap=FD._halo_map(Hout, Cout), x3_out=x3)
+    return [("fwd2", S * Hout, 5 * Cin, Cout, lambda: fn(True)), ("fwd2-", S * Hout, 5 * Cin, Cout, lambda: fn(False))]
+
+
+def shapes3_table(ops, dev, say, counter="FP16X3_TAP3_LAUNCHES", cases_of=cases3,
+                  batches=((B, PERIODS), (32, (2, 11)), (16, (2, 11)))):
     from flow2gan_amd import fused_disc as FD
     ops.set_gemm_precision("bf16x6")        # (the maps' three-piece images are reserved in this mode only)
     say("batch period  launch     rows      K      N  bf16x6_us  spread  fp16x3_us  spread  ratio  beyond spread  "
         "TFLOP/s(fp16x3)  kernels")
     seen = []
-    for batch, periods in ((B, PERIODS), (32, (2, 11)), (16, (2, 11))):
+    for batch, periods in batches:
         for p in periods:
-            for name, rows, K, N, fn in cases3(ops, FD, p, dev, batch):
-                n0 = ops.FP16X3_TAP3_LAUNCHES
+            for name, rows, K, N, fn in cases_of(ops, FD, p, dev, batch):
+                n0 = getattr(ops, counter)
                 per, kern = time_blocks(ops, fn)
-                taken = ops.FP16X3_TAP3_LAUNCHES > n0
+                taken = getattr(ops, counter) > n0
                 (a, sa), (b, sb) = med_spread(per["bf16x6"]), med_spread(per["fp16x3"])
                 verdict = "-" if not taken else ("wins" if b / a < 1.0 - max(sa, sb) else
                                                  ("loses" if b / a > 1.0 + max(sa, sb) else "inside"))
@@ -185,7 +217,7 @@ def shapes_table(ops, dev, say):
             "more than its spread" + ("" if lost else "; no launch the library accepts loses"))
 
 
-def steps_table(ops, dev, say, min_rows, steps=4, tap3=False):
+def steps_table(ops, dev, say, min_rows, steps=4, tap3=False, route="TAP3"):
     import flow2gan_amd
     from flow2gan_amd import harness
     from flow2gan_amd.models.config import get_gan_config, get_generator_config
@@ -214,14 +246,14 @@ def steps_table(ops, dev, say, min_rows, steps=4, tap3=False):
     legs = (("bf16x6", "bf16x6", ops.FP16X3_TAP_OFF), ("fp16x3 route off", "fp16x3", ops.FP16X3_TAP_OFF),
             ("fp16x3 route on", "fp16x3", min_rows))
     if tap3:        # the fp16x3 mode as shipped, the stride-3 tunable alone differing: three alternating pairs
-        legs, counter, blocks = legs[1:], "FP16X3_TAP3_LAUNCHES", 3
+        legs, counter, blocks = legs[1:], f"FP16X3_{route}_LAUNCHES", 3
     else:
         counter, blocks = "FP16X3_TAP_LAUNCHES", 7
 
     def enter(leg):
         ops.set_gemm_precision(leg[1])
         if tap3:
-            ops.FP16X3_TAP3_MIN_ROWS = leg[2]
+            setattr(ops, f"FP16X3_{route}_MIN_ROWS", leg[2])
         else:
             ops.FP16X3_TAP_MIN_ROWS = leg[2]
 
@@ -263,19 +295,23 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None, help="default profiles/fp16x3_tap_shapes.txt (--tap3: fp16x3_tap3_shapes.txt)")
     ap.add_argument("--tap3", action="store_true", help="measure the stride-3 route (legs fwd3 / fwd4) instead")
+    ap.add_argument("--tap3n", action="store_true", help="measure the 32-channel stride-3 route (legs fwd2 / fwd2-) instead")
     ap.add_argument("--append", action="store_true", help="add this run's table to --out instead of replacing it")
     ap.add_argument("--no-steps", action="store_true")
     ap.add_argument("--no-shapes", action="store_true")
     ap.add_argument("--min-rows", type=int, default=1, help="ops.FP16X3_TAP_MIN_ROWS for this run (1: every launch "
                     "of the table on the new kernel)")
     args = ap.parse_args()
+    if args.tap3 and args.tap3n:
+        ap.error("--tap3 and --tap3n are two runs")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "fp16x3_tap3_shapes.txt" if args.tap3 else "fp16x3_tap_shapes.txt")
+        args.out = os.path.join(ROOT, "profiles", "fp16x3_tap3n_shapes.txt" if args.tap3n else (
+            "fp16x3_tap3_shapes.txt" if args.tap3 else "fp16x3_tap_shapes.txt"))
     assert torch.cuda.is_available(), "needs an MI355X"
     from flow2gan_amd import ops
     if args.min_rows < 1 or args.min_rows >= ops.FP16X3_TAP_OFF:
         ap.error("--min-rows must enable the route: both modes would time the same bf16x6 launch otherwise")
-    was_rows, was_rows3 = ops.FP16X3_TAP_MIN_ROWS, ops.FP16X3_TAP3_MIN_ROWS
+    was_rows, was_rows3, was_rows3n = ops.FP16X3_TAP_MIN_ROWS, ops.FP16X3_TAP3_MIN_ROWS, ops.FP16X3_TAP3N_MIN_ROWS
     dev = torch.device("cuda")
     lines = []
 
@@ -286,23 +322,29 @@ def main():
     given = [a for i, a in enumerate(sys.argv[1:], 1) if a != "--out" and sys.argv[i - 1] != "--out"]
     say("# command (the output path aside): python tools/fp16x3_tap_shapes.py " + " ".join(given))
     say(f"# tools/fp16x3_tap_shapes.py  {ops.L.version()}  "
-        + (f"FP16X3_TAP3_MIN_ROWS={args.min_rows} FP16X3_TAP_MIN_ROWS={was_rows} " if args.tap3 else
+        + (f"FP16X3_TAP3N_MIN_ROWS={args.min_rows} FP16X3_TAP3_MIN_ROWS={was_rows3} FP16X3_TAP_MIN_ROWS={was_rows} "
+           if args.tap3n else
+           f"FP16X3_TAP3_MIN_ROWS={args.min_rows} FP16X3_TAP_MIN_ROWS={was_rows} " if args.tap3 else
            f"FP16X3_TAP_MIN_ROWS={args.min_rows} ") + f"X6_MIN_K={ops.X6_MIN_K}  {torch.cuda.get_device_name(0)}")
-    say("# per-launch medians of 5 alternating blocks of 12 launches (us), the map's image pass included in the fp16x3 "
-        "leg; spread = (max - min) / median of a mode's blocks; ratio = fp16x3 / bf16x6 (< 1: fp16x3 faster)")
+    say("# per-launch medians of 5 alternating blocks of 12 launches (us), "
+        + ("the fp16x3 leg has no image pass (the kernel scales the fp32 map itself)" if args.tap3n else
+           "the map's image pass included in the fp16x3 leg") + "; spread = (max - min) / median of a mode's blocks; ratio = fp16x3 / bf16x6 (< 1: fp16x3 faster)")
     from test_hip_gemm_f16 import mode_name       # (the one place that names the mode in force)
     was = mode_name(ops)
     try:
-        if not args.no_shapes and args.tap3:
+        if not args.no_shapes and args.tap3n:
+            ops.FP16X3_TAP3N_MIN_ROWS = args.min_rows
+            shapes3_table(ops, dev, say, "FP16X3_TAP3N_LAUNCHES", cases3n, ((B, PERIODS), (16, PERIODS)))
+        elif not args.no_shapes and args.tap3:
             ops.FP16X3_TAP3_MIN_ROWS = args.min_rows
             shapes3_table(ops, dev, say)
         elif not args.no_shapes:
             ops.FP16X3_TAP_MIN_ROWS = args.min_rows
             shapes_table(ops, dev, say)
         if not args.no_steps:
-            steps_table(ops, dev, say, args.min_rows, tap3=args.tap3)
+            steps_table(ops, dev, say, args.min_rows, tap3=args.tap3 or args.tap3n, route="TAP3N" if args.tap3n else "TAP3")
     finally:
-        ops.FP16X3_TAP_MIN_ROWS, ops.FP16X3_TAP3_MIN_ROWS = was_rows, was_rows3
+        ops.FP16X3_TAP_MIN_ROWS, ops.FP16X3_TAP3_MIN_ROWS, ops.FP16X3_TAP3N_MIN_ROWS = was_rows, was_rows3, was_rows3n
         ops.set_gemm_precision(was)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "a" if args.append else "w") as f:
