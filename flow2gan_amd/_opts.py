@@ -24,7 +24,10 @@ default), fp16x3_tapw3_min_rows (the fewest reduction rows at which the weight g
 over a halo map with a multiple of 128 channels -- the MPD's strided layers -- takes the fp16x3 stride-3 tap-walking
 weight-gradient kernel; off by default), fp16x3_tap3n_min_rows (the fewest output rows at which the GEMM over stride-3
 windows of five positions of a 32-channel halo map -- the MPD's 32 -> 128 forward layer -- takes the fp16x3 kernel that
-scales the fp32 map per sequence segment inside the kernel, without an image pass; off by default), fp16x3_conv32_fwd, fp16x3_conv32_dgrad (F2G_GEMM=fp16x3: the MRD (3, 9) band layers' forward / data gradient on the
+scales the fp32 map per sequence segment inside the kernel, without an image pass; off by default),
+fp16x3_tapn_min_rows (the fewest output rows at which a GEMM over stride-1 windows of two or one positions of a
+128-channel halo map onto at most 32 columns -- the stride-residue data gradients of that layer -- takes the fp16x3
+kernel that scales the fp32 map per sequence segment inside the kernel; off by default), fp16x3_conv32_fwd, fp16x3_conv32_dgrad (F2G_GEMM=fp16x3: the MRD (3, 9) band layers' forward / data gradient on the
 fp16x3 kernels that scale each tile's patch inside the kernel; both off by default), fp16x3_conv32_wgrad (the same
 layers' weight gradient on the fp16x3 kernel that keeps one running scale per operand and block; off by default),
 fp16x3_conv33_fwd, fp16x3_conv33_dgrad (F2G_GEMM=fp16x3: the MRD (3, 3) fifth layer's forward / data gradient on the

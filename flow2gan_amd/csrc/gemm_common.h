@@ -1,5 +1,5 @@
 // What more than one of the GEMM translation units needs (gemm.hip, gemm_lean.hip, gemm_wgrad.hip, gemm_x6.hip,
-// gemm_x6p.hip, gemm_f16.hip, gemm_f16p.hip, gemm_f16p3.hip, gemm_f16p3n.hip, gemm_f16wt.hip, gemm_f16ws.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
+// gemm_x6p.hip, gemm_f16.hip, gemm_f16p.hip, gemm_f16p3.hip, gemm_f16p3n.hip, gemm_f16pn.hip, gemm_f16wt.hip, gemm_f16ws.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
 // three-piece split, the LDS barrier, the lab switches, and the host functions that cross those files.  Everything
 // defined here has internal linkage; no GEMM file includes another.  (gemm_f16_common.h: what only fp16x3 shares.)
 #pragma once
@@ -18,8 +18,8 @@ bool f2g_leanw_fp32_takes(const f2g_gemm_desc& d, int split);
 int f2g_launch_leanw(const f2g_gemm_desc& d, int pieces, int split, hipStream_t st);
 // gemm_x6.hip: form 0 at precision 3 (checks the descriptor, picks the kernel, launches)
 int f2g_gemm_x6(const f2g_gemm_desc& d, hipStream_t st);
-// gemm_f16.hip: precision 4 -- decides which of the six fp16x3 kernels a descriptor belongs to (its own two: form 0
-// over f2g_split_f16x2 images, form 2 over f2g_split_f16x2_cols images; the four below), checks it, launches that one
+// gemm_f16.hip: precision 4 -- decides which of the fp16x3 kernels a descriptor belongs to (its own two: form 0
+// over f2g_split_f16x2 images, form 2 over f2g_split_f16x2_cols images; the ones below), checks it, launches that one
 int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st);
 // gemm_f16p.hip: precision 4, form 0 over stride-1 windows of 5 or 2 positions of a halo map (gemm_h3p_kernel).
 // f2g_h3p_ok: 1 = runs as handed over (both operands f2g_split_f16x2_seq images with their reciprocal scales), 2 = once
@@ -36,6 +36,11 @@ int f2g_launch_h3p3(const f2g_gemm_desc& d, hipStream_t st);
 // image, 0 = not for this kernel
 int f2g_h3p3n_ok(const f2g_gemm_desc& d);
 int f2g_launch_h3p3n(const f2g_gemm_desc& d, hipStream_t st);
+// gemm_f16pn.hip: the other user of split = 8 -- STRIDE-1 windows of 2 or 1 positions over 128 channels onto N <= 32
+// columns (K = 256 / 128: the stride-residue data gradients of that layer), A = the fp32 map itself, scaled per
+// sequence segment inside gemm_h3pn_kernel.  f2g_h3pn_ok answers as f2g_h3p3n_ok does; `taps` receives 2 or 1
+int f2g_h3pn_ok(const f2g_gemm_desc& d, int* taps);
+int f2g_launch_h3pn(const f2g_gemm_desc& d, int taps, hipStream_t st);
 // gemm_f16wt.hip: precision 4, form 2 over unbounded stride-1 windows of 5 positions of a halo map (gemm_h3wt_kernel:
 // the tap-walking weight gradient).  f2g_h3wt_ok: 1 = runs as handed over (A and the whole map as
 // f2g_split_f16x2_cols images with their reciprocal scales), 2 = once both fp32 operands are replaced by those

@@ -358,13 +358,13 @@ inline bool h3w_operand_ok(const f2g_operand& S) {
 }
 
 // The ONE route decision of precision 4: the kernel a descriptor belongs to -- gemm_h3_kernel, gemm_h3w_kernel,
-// gemm_h3p_kernel (gemm_f16p.hip), gemm_h3p3_kernel (gemm_f16p3.hip), gemm_h3p3n_kernel (gemm_f16p3n.hip),
+// gemm_h3p_kernel (gemm_f16p.hip), gemm_h3p3_kernel (gemm_f16p3.hip), gemm_h3p3n_kernel (gemm_f16p3n.hip), gemm_h3pn_kernel (gemm_f16pn.hip),
 // gemm_h3wt_kernel (gemm_f16wt.hip),
 // gemm_h3ws_kernel (gemm_f16ws.hip) --, what f2g_gemm_f16_ok answers for it (0: not for
 // that kernel; 1: runs as handed over, both operands the kernel's images with their reciprocal scales; 2: once both
 // fp32 operands are replaced by those images) and the taps of H3_TAP.  The shape of the operands picks the candidate,
 // the candidate's own conditions decide: a descriptor one kernel declines is never offered to another.
-enum h3_kernel { H3_NONE, H3_PLAIN, H3_WGRAD, H3_TAP, H3_TAP3, H3_TAP3N, H3_TAPW, H3_TAPW3 };
+enum h3_kernel { H3_NONE, H3_PLAIN, H3_WGRAD, H3_TAP, H3_TAP3, H3_TAP3N, H3_TAPN, H3_TAPW, H3_TAPW3 };
 struct h3_route {
   h3_kernel kernel = H3_NONE;
   int status = 0, taps = 0;
@@ -402,11 +402,13 @@ h3_route h3_route_of(const f2g_gemm_desc& d) {
   } else if (d.form == 0) {
     // windows of a halo map, or f2g_split_f16x2_seq images: a tap-walking kernel (the windows' stride says which:
     // 3 gemm_h3p3_kernel, anything else gemm_h3p_kernel) or nothing
-    // A marked split = 8 (the fp32 map, scaled inside the kernel): gemm_h3p3n_kernel (gemm_f16p3n.hip) or nothing
+    // A marked split = 8 (the fp32 map, scaled inside the kernel): the windows' stride says which -- 3
+    // gemm_h3p3n_kernel (gemm_f16p3n.hip), anything else gemm_h3pn_kernel (gemm_f16pn.hip) -- or nothing
     const bool win = !host_plain(d.A);
-    cand = d.A.split == 8 ? H3_TAP3N
+    cand = d.A.split == 8 ? (d.A.step0 == 3 ? H3_TAP3N : H3_TAPN)
                           : (win && d.A.step0 == 3 ? H3_TAP3 : (win || d.A.split == 7 || d.B.split == 7 ? H3_TAP : H3_PLAIN));
     if (cand == H3_TAP3N) r.status = f2g_h3p3n_ok(d), r.taps = 5;
+    else if (cand == H3_TAPN) r.status = f2g_h3pn_ok(d, &r.taps);
     else if (cand == H3_TAP3) r.status = f2g_h3p3_ok(d), r.taps = 5;
     else r.status = cand == H3_TAP ? f2g_h3p_ok(d, &r.taps) : h3_plain_ok(d);
   }
@@ -423,7 +425,7 @@ int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st) {
   if (r.status != 1) {
     f2g_set_error("f2g_gemm precision 4: form 0 over f2g_split_f16x2 images, or form 2 over f2g_split_f16x2_cols "
                   "images, of two plain matrices, or form 0 over f2g_split_f16x2_seq images of stride-1 windows of 5 or "
-                  "2 positions or of stride-3 windows of 5 positions over a multiple of 128 channels, or form 0 over the fp32 map (A.split = 8) under stride-3 windows of 5 positions over 32 channels against a f2g_split_f16x2_seq image, or form 2 + atomic over f2g_split_f16x2_cols images of a plain matrix and of the map "
+                  "2 positions or of stride-3 windows of 5 positions over a multiple of 128 channels, or form 0 over the fp32 map (A.split = 8) under stride-3 windows of 5 positions over 32 channels or stride-1 windows of 2 or 1 positions over 128 channels onto at most 32 columns against a f2g_split_f16x2_seq image, or form 2 + atomic over f2g_split_f16x2_cols images of a plain matrix and of the map "
                   "under unbounded stride-1 windows of 5 positions, or of stride-3 windows of 5 positions that overhang a "
                   "sequence of seq_stride / unit map rows by at most pad0 rows (f2g_gemm_f16_ok(d) != 1 for this "
                   "descriptor)");
@@ -433,6 +435,7 @@ int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st) {
     case H3_TAP: return f2g_launch_h3p(d, r.taps, st);
     case H3_TAP3: return f2g_launch_h3p3(d, st);
     case H3_TAP3N: return f2g_launch_h3p3n(d, st);
+    case H3_TAPN: return f2g_launch_h3pn(d, r.taps, st);
     case H3_TAPW: return f2g_launch_h3wt(d, st);
     case H3_TAPW3: return f2g_launch_h3ws(d, st);
     case H3_WGRAD: {

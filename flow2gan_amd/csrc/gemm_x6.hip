@@ -649,6 +649,8 @@ __global__ __launch_bounds__(256, 2) void gemm_x6n_kernel(const f2g_gemm_desc d,
   // Epilogue.  The row map of a stride residue costs the generic epilogue one 64-bit division per ELEMENT (16 per
   // lane and tile, ~35 VALU instructions each beside 96 MFMAs); here the 128 output-row offsets of the tile are
   // computed once, one division per ROW, into the (now free) operand buffer, and the elements look them up.
+  // (thin_epilogue.h has the same steps as functions, for gemm_h3pn_kernel; calling them here moved this kernel from
+  // 102 to 104 registers, so it keeps its own copy -- a change to one belongs in the other)
   const f2g_epilogue& E = d.E;
   if (E.aux || E.res || E.prelu_slope || E.atomic || E.accumulate || E.scale != 0.f) {
     gemm_epilogue<1, 1>(E, acc, M, N, m0, n0, wave, 0, li, h, true);
@@ -832,7 +834,8 @@ extern "C" int32_t f2g_gemm_colsum_part_rows(const f2g_gemm_desc* dp) {
   f2g_gemm_desc d = *dp;
   if (d.E.colsum_part_ld <= 0) d.E.colsum_part_ld = 4;          // (alignment of the pointers is the caller's)
   // precision 4: the tap-walking kernels alone have the wide epilogue (gemm_f16p.hip, gemm_f16p3.hip; 256-row tiles)
-  // (gemm_f16p3n.hip: 128-row tiles)
+  // (gemm_f16p3n.hip: 128-row tiles; gemm_f16pn.hip, the other user of split = 8, has the thin epilogue: no partial
+  // rows -- f2g_h3p3n_ok declines its stride-1 windows)
   if (d.precision == 4 && d.A.split == 8) return f2g_h3p3n_ok(d) ? 2 * ((d.A.rows + 127) / 128) : 0;
   if (d.precision == 4) return f2g_h3p_ok(d, nullptr) || f2g_h3p3_ok(d) ? 4 * ((d.A.rows + 255) / 256) : 0;
   if (!x6_wide(d)) return 0;

@@ -1022,7 +1022,7 @@ def _fp16x3_gemm(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offse
     True: one took the launch -- d.A / d.B are its images, its counter went up.  False: the launch goes the bf16x6
     way (d.precision may be left at 4: gemm() sets it)."""
     global FP16X3_LAUNCHES, FP16X3_WGRAD_LAUNCHES, FP16X3_TAP_LAUNCHES, FP16X3_TAPW_LAUNCHES, FP16X3_TAP3_LAUNCHES
-    global FP16X3_TAPW3_LAUNCHES, FP16X3_TAP3N_LAUNCHES
+    global FP16X3_TAPW3_LAUNCHES, FP16X3_TAP3N_LAUNCHES, FP16X3_TAPN_LAUNCHES
     if not (GEMM_PRECISION == 3 and FP16X3) or A.split != 0 or Bm.split != 0 or out.dtype != torch.float32:
         return False
 
@@ -1064,6 +1064,20 @@ def _fp16x3_gemm(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offse
         d.A, d.B = _f16_cols_operand(A), _f16_cols_window_operand(Bm)
         FP16X3_TAPW3_LAUNCHES += 1
         return True
+    if form == 0 and A.P1 == 1 and A.P0 > 1 and A.step0 == 1 and A.unit == 128 and A.cols in (128, 256) \
+            and Bm.rows <= 32 and A.rows >= FP16X3_TAPN_MIN_ROWS and not atomic and split_k <= 1 and not x3_out \
+            and _f16_seq_window_ok(A):
+        # fp16x3 over stride-1 windows of 2 or 1 positions of a contiguous 128-channel halo map onto at most 32 columns
+        # (the stride-residue data gradients of the MPD's 32 -> 128 layer): NO image of the map -- d.A stays the
+        # caller's fp32 map, marked split = 8, and gemm_h3pn_kernel scales it per sequence segment and splits it while
+        # staging; nothing is allocated per call.  The weight's f2g_split_f16x2_seq image comes from the
+        # derived-weight cache.  What the library declines goes the bf16x6 way
+        d.A.split = 8
+        if takes():
+            d.B = _f16_seq_operand(Bm)
+            FP16X3_TAPN_LAUNCHES += 1
+            return True
+        d.A.split = 0
     if form == 0 and A.P1 == 1 and A.P0 > 1 and A.step0 == 1 and A.cols in (5 * A.unit, 2 * A.unit) \
             and A.rows >= FP16X3_TAP_MIN_ROWS and A.cols >= X6_MIN_K and not atomic and split_k <= 1 \
             and _f16_seq_window_ok(A):
@@ -1554,6 +1568,15 @@ FP16X3_TAP3_LAUNCHES = 0   # launches gemm_h3p3_kernel took (tests and tools)
 # the tool lower it; F2G_OPTS=fp16x3_tap3n_min_rows=1 turns it on)
 FP16X3_TAP3N_MIN_ROWS = opt("fp16x3_tap3n_min_rows", FP16X3_TAP_OFF)
 FP16X3_TAP3N_LAUNCHES = 0  # launches gemm_h3p3n_kernel took (tests and tools)
+# F2G_GEMM=fp16x3: the fewest output rows at which form 0 over STRIDE-1 windows of two or one positions of a contiguous
+# 128-channel halo map onto at most 32 columns (the three stride-residue data gradients of the MPD's 32 -> 128 layer,
+# K = 256 / 256 / 128) takes gemm_h3pn_kernel (csrc/gemm_f16pn.hip): the fp32 gradient map is scaled per sequence
+# segment and split INSIDE the kernel, every position staged once whatever the taps -- no image pass, no allocation per
+# call --, the weight fragments stay in registers for a block's life.  profiles/fp16x3_tapn_shapes.txt
+# (tools/fp16x3_tap_shapes.py --tapn) has what was measured.  The route ships off like the other tap-walking routes:
+# FP16X3_TAP_OFF = disabled (tests and the tool lower it; F2G_OPTS=fp16x3_tapn_min_rows=1 turns it on)
+FP16X3_TAPN_MIN_ROWS = opt("fp16x3_tapn_min_rows", FP16X3_TAP_OFF)
+FP16X3_TAPN_LAUNCHES = 0   # launches gemm_h3pn_kernel took (tests and tools)
 # fewest reduction rows at which the weight gradient of a STRIDE-3 five-tap layer over a halo map with a multiple of 128
 # channels (the MPD's 128 -> 512 and 512 -> 1024 layers; ops.wgrad over unbounded windows) goes to gemm_h3ws_kernel:
 # the gradient and the whole map pay f2g_split_f16x2_cols per call, exactly as for the stride-1 route above, against

@@ -93,9 +93,11 @@ typedef struct {
    *    with one run per sequence (`seq_stride` floats) and `rscale` = one reciprocal scale per SEQUENCE, rows / P0
    *    floats; operand B = the plain weight matrix with one run per row (row stride % 32 == 0), `rows` scales;
    * 8: (operand A of a precision-4, form-0 launch only) `base` is the fp32 halo map ITSELF, as for split = 0, and the
-   *    mark says: scale it per sequence segment and split it inside the precision-4 kernel (stride-3 windows of 5
-   *    positions over 32 channels, f2g_split_f16x2_seq below).  There is no image; `rscale` is ignored.  A descriptor
-   *    so marked that fails a condition of that kernel is F2G_EINVAL, never run elsewhere */
+   *    mark says: scale it per sequence segment and split it inside the precision-4 kernel.  Two kernels read it
+   *    (f2g_split_f16x2_seq below has both): stride-3 windows of 5 positions over 32 channels (gemm_h3p3n_kernel), and
+   *    stride-1 windows of 2 or 1 positions over 128 channels onto at most 32 columns (gemm_h3pn_kernel); the
+   *    windows' stride says which.  There is no image; `rscale` is ignored.  A descriptor so marked that fails a
+   *    condition of its kernel is F2G_EINVAL, never run elsewhere */
   int32_t split;
   const float* alpha;
   const float* lrelu_src;
@@ -204,7 +206,9 @@ typedef struct {
    *     f2g_split_f16x2_seq images (split = 7 with rscale: one scale per sequence, which leaves every window's sum);
    *     form 0 over stride-3 windows of 5 positions of a halo map with unit % 128 == 0, over the same images;
    *     form 0 over stride-3 windows of 5 positions of an fp32 halo map with unit == 32 marked split = 8 (scaled and
-   *     split inside the kernel) against a plain weight matrix given as its f2g_split_f16x2_seq image.
+   *     split inside the kernel) against a plain weight matrix given as its f2g_split_f16x2_seq image;
+   *     form 0 over stride-1 windows of 2 or 1 positions of an fp32 halo map with unit == 128 marked split = 8 against
+   *     a plain weight matrix of at most 32 rows given as its f2g_split_f16x2_seq image.
    *     A descriptor f2g_gemm_f16_ok does not answer with 1 is F2G_EINVAL, never run elsewhere. */
   int32_t precision;
   int32_t _pad3;
@@ -358,7 +362,19 @@ int f2g_split_f16x2_cols(float* dst, float* rscale, uint32_t* work, const float*
  * library option x6p as above (1: at least 256 row tiles).  f2g_gemm_f16_ok answers 1 for A.split == 8, B.split == 7
  * with rscale, 2 for A.split == 8, B.split == 0 (= once B is replaced by its image), 0 otherwise; with A.split == 0
  * every descriptor keeps the answer it had (unit == 32 at stride 3: 0).  f2g_gemm_colsum_part_rows answers for it (two
- * partial rows per 128-row tile).  f2g_gemm_last_kernel reports "h3p3n<taps=5,step=3>", path 6. */
+ * partial rows per 128-row tile).  f2g_gemm_last_kernel reports "h3p3n<taps=5,step=3>", path 6.
+ * The layer's three stride-residue DATA GRADIENTS (stride-1 windows of 2 or 1 positions over its 128-channel gradient
+ * map, K = 256 / 128, N <= 32 columns through a row map) take the same mark and the same segment scale on
+ * gemm_h3pn_kernel: a segment is the n + taps - 1 positions the n rows of one sequence inside a 128-row tile read,
+ * every position is loaded, split and staged once whatever the taps, the maximum goes thread -> the 32 lanes of a
+ * 512-byte position -> one LDS word per segment, and the weight fragments stay in registers while a block walks its
+ * tiles.  Its epilogue is the thin one of gemm_x6n_kernel: bias, leaky ReLU, mask_src with the feature-matching term,
+ * colsum by atomics (the one part of the launch that is not bit-reproducible), the row map -- aux, res, colsum_alpha,
+ * prelu_*, scale, atomic, accumulate, c_bf16, x3_out, colsum_part_ld > 0 and split_k > 1 are F2G_EINVAL.  Conditions:
+ * unit == 128, step0 == 1, cols == 128 or 256, P1 == 1, pad0 <= 0, seq_stride % unit == 0, L0u <= seq_stride, P0 >= 8
+ * (at most 17 segments and 145 staged positions per tile), 1 <= N <= 32, alignment, extents, B's row stride and the
+ * x6p option as above.  f2g_gemm_f16_ok answers 1 / 2 / 0 as above; f2g_gemm_colsum_part_rows answers 0 (no partial
+ * rows).  f2g_gemm_last_kernel reports "h3pn<taps=2>" or "h3pn<taps=1>", path 6. */
 int f2g_split_f16x2_seq(float* dst, float* rscale, const float* src, int64_t ld, int32_t nseq, int32_t seq_floats,
                         f2g_stream_t stream);
 

@@ -38,8 +38,18 @@ itself, there is no image pass to include; bf16x6 = the launch as that mode rout
 the fp32 map inside the kernel: K = 160 < x6_min_k, no image pass either).  Then the stage-2 step in the fp16x3 mode with that
 tunable alone differing, in three alternating pairs.
 
+--tapn measures the route of that layer's DATA GRADIENT (gemm_h3pn_kernel, ops.FP16X3_TAPN_MIN_ROWS; default output
+profiles/fp16x3_tapn_shapes.txt), every other route staying as shipped:
+  dgrad2  the three stride-residue data gradients of the 32 -> 128 layer (two, two and one taps over the 128-channel
+          gradient map, K = 256 / 256 / 128, N = 32; stride-3 row map into the 32-channel halo map, no mask -- as
+          fused_disc._conv1d_dgrad launches them), timed together
+per period at B = 64 and B = 16.  fp16x3 = the kernel alone (no image pass); bf16x6 = the launches as that mode routes
+them (gemm_x6n_kernel, which splits the fp32 map inside the kernel and pays no image pass either; its device code is
+the parent commit's).  Then the stage-2 step in the fp16x3 mode with that tunable alone differing, in three alternating
+pairs.
+
     python tools/fp16x3_tap_shapes.py [--out profiles/fp16x3_tap_shapes.txt] [--append] [--no-shapes] [--no-steps]
-                                      [--min-rows R] [--tap3 | --tap3n]
+                                      [--min-rows R] [--tap3 | --tap3n | --tapn]
 """
 import argparse
 import os
@@ -158,6 +168,29 @@ def cases3n(ops, FD, p, dev, batch=B):
     return [("fwd2", S * Hout, 5 * Cin, Cout, lambda: fn(True)), ("fwd2-", S * Hout, 5 * Cin, Cout, lambda: fn(False))]
 
 
+def casesn(ops, FD, p, dev, batch=B):
+    """(name, rows, K, N, fn) of the three residue data gradients of the 32 -> 128 stride-3 layer of period p at
+    `batch` clips, launched one after the other as fused_disc._conv1d_dgrad does"""
+    S, hs = 2 * batch * p, heights(p)
+    g = torch.Generator().manual_seed(300 + p)
+    Cin, Cout, Hin, Hout = FD.MPD_CH[1], FD.MPD_CH[2], hs[1], hs[2]
+    gpre = FD._halo_rows(S, Hout, Cout, dev)
+    FD.unhalo(gpre, S, Hout).copy_((torch.randn(S, Hout, Cout, generator=g) * 1e-3).to(dev))
+    gx = FD._halo_rows(S, Hin, Cin, dev)
+    w = torch.nn.Parameter((torch.randn(Cout, Cin, 5, 1, generator=g) * (5 * Cin) ** -0.5).to(dev))
+    launches = []
+    for rho, j0, nt, e0, Lq in FD._residues(5, 3, 2, Hin):
+        if Lq:
+            launches.append((FD._dgrad_weight(w, 3, j0, nt), (nt - 1) - e0 - FD.HALO, nt, Lq,
+                             (Lq, (Hin + 2 * FD.HALO) * Cin, 3 * Cin, (FD.HALO + rho) * Cin)))
+
+    def fn():
+        for wq, pad, nt, Lq, rm in launches:
+            ops.gemm(ops.win1d(gpre, S, Hout + 2 * FD.HALO, Cout, Lq, 1, pad, nt), ops.mat(wq), gx, rowmap=rm)
+    # (FLOPs of the table: rows x the longest reduction, as for dgrad4; the one-tap residue has half of it)
+    return [("dgrad2", sum(S * l[3] for l in launches), 2 * Cout, Cin, fn)]
+
+
 def shapes3_table(ops, dev, say, counter="FP16X3_TAP3_LAUNCHES", cases_of=cases3,
                   batches=((B, PERIODS), (32, (2, 11)), (16, (2, 11)))):
     from flow2gan_amd import fused_disc as FD
@@ -171,6 +204,8 @@ def shapes3_table(ops, dev, say, counter="FP16X3_TAP3_LAUNCHES", cases_of=cases3
                 n0 = getattr(ops, counter)
                 per, kern = time_blocks(ops, fn)
                 taken = getattr(ops, counter) > n0
+                if name == "dgrad2":      # (FLOPs: the residues have 2, 2 and 1 taps -- 5 / 6 of rows x 256)
+                    K = K * 5 // 6
                 (a, sa), (b, sb) = med_spread(per["bf16x6"]), med_spread(per["fp16x3"])
                 verdict = "-" if not taken else ("wins" if b / a < 1.0 - max(sa, sb) else
                                                  ("loses" if b / a > 1.0 + max(sa, sb) else "inside"))
@@ -296,22 +331,24 @@ def main():
     ap.add_argument("--out", default=None, help="default profiles/fp16x3_tap_shapes.txt (--tap3: fp16x3_tap3_shapes.txt)")
     ap.add_argument("--tap3", action="store_true", help="measure the stride-3 route (legs fwd3 / fwd4) instead")
     ap.add_argument("--tap3n", action="store_true", help="measure the 32-channel stride-3 route (legs fwd2 / fwd2-) instead")
+    ap.add_argument("--tapn", action="store_true", help="measure the route of the 32 -> 128 layer's residue data gradients (leg dgrad2) instead")
     ap.add_argument("--append", action="store_true", help="add this run's table to --out instead of replacing it")
     ap.add_argument("--no-steps", action="store_true")
     ap.add_argument("--no-shapes", action="store_true")
     ap.add_argument("--min-rows", type=int, default=1, help="ops.FP16X3_TAP_MIN_ROWS for this run (1: every launch "
                     "of the table on the new kernel)")
     args = ap.parse_args()
-    if args.tap3 and args.tap3n:
-        ap.error("--tap3 and --tap3n are two runs")
+    if args.tap3 + args.tap3n + args.tapn > 1:
+        ap.error("--tap3, --tap3n and --tapn are separate runs")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "fp16x3_tap3n_shapes.txt" if args.tap3n else (
+        args.out = os.path.join(ROOT, "profiles", "fp16x3_tapn_shapes.txt" if args.tapn else "fp16x3_tap3n_shapes.txt" if args.tap3n else (
             "fp16x3_tap3_shapes.txt" if args.tap3 else "fp16x3_tap_shapes.txt"))
     assert torch.cuda.is_available(), "needs an MI355X"
     from flow2gan_amd import ops
     if args.min_rows < 1 or args.min_rows >= ops.FP16X3_TAP_OFF:
         ap.error("--min-rows must enable the route: both modes would time the same bf16x6 launch otherwise")
     was_rows, was_rows3, was_rows3n = ops.FP16X3_TAP_MIN_ROWS, ops.FP16X3_TAP3_MIN_ROWS, ops.FP16X3_TAP3N_MIN_ROWS
+    was_rowsn = ops.FP16X3_TAPN_MIN_ROWS
     dev = torch.device("cuda")
     lines = []
 
@@ -322,17 +359,22 @@ def main():
     given = [a for i, a in enumerate(sys.argv[1:], 1) if a != "--out" and sys.argv[i - 1] != "--out"]
     say("# command (the output path aside): python tools/fp16x3_tap_shapes.py " + " ".join(given))
     say(f"# tools/fp16x3_tap_shapes.py  {ops.L.version()}  "
-        + (f"FP16X3_TAP3N_MIN_ROWS={args.min_rows} FP16X3_TAP3_MIN_ROWS={was_rows3} FP16X3_TAP_MIN_ROWS={was_rows} "
+        + (f"FP16X3_TAPN_MIN_ROWS={args.min_rows} FP16X3_TAP3N_MIN_ROWS={was_rows3n} FP16X3_TAP3_MIN_ROWS={was_rows3} "
+           f"FP16X3_TAP_MIN_ROWS={was_rows} " if args.tapn else
+           f"FP16X3_TAP3N_MIN_ROWS={args.min_rows} FP16X3_TAP3_MIN_ROWS={was_rows3} FP16X3_TAP_MIN_ROWS={was_rows} "
            if args.tap3n else
            f"FP16X3_TAP3_MIN_ROWS={args.min_rows} FP16X3_TAP_MIN_ROWS={was_rows} " if args.tap3 else
            f"FP16X3_TAP_MIN_ROWS={args.min_rows} ") + f"X6_MIN_K={ops.X6_MIN_K}  {torch.cuda.get_device_name(0)}")
     say("# per-launch medians of 5 alternating blocks of 12 launches (us), "
-        + ("the fp16x3 leg has no image pass (the kernel scales the fp32 map itself)" if args.tap3n else
+        + ("the fp16x3 leg has no image pass (the kernel scales the fp32 map itself)" if args.tap3n or args.tapn else
            "the map's image pass included in the fp16x3 leg") + "; spread = (max - min) / median of a mode's blocks; ratio = fp16x3 / bf16x6 (< 1: fp16x3 faster)")
     from test_hip_gemm_f16 import mode_name       # (the one place that names the mode in force)
     was = mode_name(ops)
     try:
-        if not args.no_shapes and args.tap3n:
+        if not args.no_shapes and args.tapn:
+            ops.FP16X3_TAPN_MIN_ROWS = args.min_rows
+            shapes3_table(ops, dev, say, "FP16X3_TAPN_LAUNCHES", casesn, ((B, PERIODS), (16, PERIODS)))
+        elif not args.no_shapes and args.tap3n:
             ops.FP16X3_TAP3N_MIN_ROWS = args.min_rows
             shapes3_table(ops, dev, say, "FP16X3_TAP3N_LAUNCHES", cases3n, ((B, PERIODS), (16, PERIODS)))
         elif not args.no_shapes and args.tap3:
@@ -342,9 +384,11 @@ def main():
             ops.FP16X3_TAP_MIN_ROWS = args.min_rows
             shapes_table(ops, dev, say)
         if not args.no_steps:
-            steps_table(ops, dev, say, args.min_rows, tap3=args.tap3 or args.tap3n, route="TAP3N" if args.tap3n else "TAP3")
+            steps_table(ops, dev, say, args.min_rows, tap3=args.tap3 or args.tap3n or args.tapn,
+                        route="TAPN" if args.tapn else ("TAP3N" if args.tap3n else "TAP3"))
     finally:
         ops.FP16X3_TAP_MIN_ROWS, ops.FP16X3_TAP3_MIN_ROWS, ops.FP16X3_TAP3N_MIN_ROWS = was_rows, was_rows3, was_rows3n
+        ops.FP16X3_TAPN_MIN_ROWS = was_rowsn
         ops.set_gemm_precision(was)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "a" if args.append else "w") as f:
