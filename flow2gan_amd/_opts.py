@@ -22,7 +22,10 @@ fp16x3_tap3_min_rows (the fewest output rows at which a GEMM over stride-3 windo
 a multiple of 128 channels -- the MPD's strided forward layers -- takes the fp16x3 stride-3 tap-walking kernel; off by
 default), fp16x3_tapw3_min_rows (the fewest reduction rows at which the weight gradient of a stride-3 five-tap layer
 over a halo map with a multiple of 128 channels -- the MPD's strided layers -- takes the fp16x3 stride-3 tap-walking
-weight-gradient kernel; off by default), fp16x3_tap3n_min_rows (the fewest output rows at which the GEMM over stride-3
+weight-gradient kernel; off by default), fp16x3_tapw3n_min_rows (the fewest reduction rows at which the weight gradient
+of the stride-3 five-tap layer over a 32-channel halo map onto 128 channels -- the MPD's 32 -> 128 layer -- takes the
+fp16x3 kernel that reads both fp32 operands once and scales them under one running scale per operand and block inside
+the kernel, without an image pass; off by default), fp16x3_tap3n_min_rows (the fewest output rows at which the GEMM over stride-3
 windows of five positions of a 32-channel halo map -- the MPD's 32 -> 128 forward layer -- takes the fp16x3 kernel that
 scales the fp32 map per sequence segment inside the kernel, without an image pass; off by default),
 fp16x3_tapn_min_rows (the fewest output rows at which a GEMM over stride-1 windows of two or one positions of a

@@ -3,8 +3,9 @@
 // f2g_split_f16x2_cols writes the images of K-major operands (one scale per column), gemm_h3w_kernel reads those.
 // (gemm_f16p.hip: f2g_split_f16x2_seq and gemm_h3p_kernel, the same over stride-1 windows of a halo map;
 // gemm_f16p3.hip: gemm_h3p3_kernel, the same over stride-3 windows; gemm_f16wt.hip: gemm_h3wt_kernel, the weight
-// gradient of a stride-1 layer over column images; gemm_f16ws.hip: gemm_h3ws_kernel, that of a stride-3 layer.)  The
-// six kernels share
+// gradient of a stride-1 layer over column images; gemm_f16ws.hip: gemm_h3ws_kernel, that of a stride-3 layer;
+// gemm_f16wsn.hip: gemm_h3wsn_kernel, that of the 32-channel stride-3 layer over the fp32 operands themselves.)  The
+// kernels share
 // gemm_f16_common.h, the image writers split_f16.h; h3_route_of below says which kernel a descriptor belongs to.
 #include <stddef.h>
 #include <stdint.h>
@@ -360,11 +361,11 @@ inline bool h3w_operand_ok(const f2g_operand& S) {
 // The ONE route decision of precision 4: the kernel a descriptor belongs to -- gemm_h3_kernel, gemm_h3w_kernel,
 // gemm_h3p_kernel (gemm_f16p.hip), gemm_h3p3_kernel (gemm_f16p3.hip), gemm_h3p3n_kernel (gemm_f16p3n.hip), gemm_h3pn_kernel (gemm_f16pn.hip),
 // gemm_h3wt_kernel (gemm_f16wt.hip),
-// gemm_h3ws_kernel (gemm_f16ws.hip) --, what f2g_gemm_f16_ok answers for it (0: not for
+// gemm_h3ws_kernel (gemm_f16ws.hip), gemm_h3wsn_kernel (gemm_f16wsn.hip) --, what f2g_gemm_f16_ok answers for it (0: not for
 // that kernel; 1: runs as handed over, both operands the kernel's images with their reciprocal scales; 2: once both
 // fp32 operands are replaced by those images) and the taps of H3_TAP.  The shape of the operands picks the candidate,
 // the candidate's own conditions decide: a descriptor one kernel declines is never offered to another.
-enum h3_kernel { H3_NONE, H3_PLAIN, H3_WGRAD, H3_TAP, H3_TAP3, H3_TAP3N, H3_TAPN, H3_TAPW, H3_TAPW3 };
+enum h3_kernel { H3_NONE, H3_PLAIN, H3_WGRAD, H3_TAP, H3_TAP3, H3_TAP3N, H3_TAPN, H3_TAPW, H3_TAPW3, H3_TAPW3N };
 struct h3_route {
   h3_kernel kernel = H3_NONE;
   int status = 0, taps = 0;
@@ -397,8 +398,12 @@ h3_route h3_route_of(const f2g_gemm_desc& d) {
   if (d.form == 2) {
     // B a window operand: a tap-walking weight gradient (the windows' stride says which: 3 gemm_h3ws_kernel, anything
     // else gemm_h3wt_kernel) or nothing
-    cand = d.precision == 4 && host_plain(d.A) && !host_plain(d.B) ? (d.B.step0 == 3 ? H3_TAPW3 : H3_TAPW) : H3_WGRAD;
-    r.status = cand == H3_TAPW3 ? f2g_h3ws_ok(d) : (cand == H3_TAPW ? f2g_h3wt_ok(d) : h3w_ok(d));
+    // an operand marked split = 8 (the fp32 operands themselves, scaled inside the kernel): gemm_h3wsn_kernel
+    // (gemm_f16wsn.hip) or nothing
+    if (d.precision == 4 && (d.A.split == 8 || d.B.split == 8)) cand = H3_TAPW3N;
+    else cand = d.precision == 4 && host_plain(d.A) && !host_plain(d.B) ? (d.B.step0 == 3 ? H3_TAPW3 : H3_TAPW) : H3_WGRAD;
+    if (cand == H3_TAPW3N) r.status = f2g_h3wsn_ok(d);
+    else r.status = cand == H3_TAPW3 ? f2g_h3ws_ok(d) : (cand == H3_TAPW ? f2g_h3wt_ok(d) : h3w_ok(d));
   } else if (d.form == 0) {
     // windows of a halo map, or f2g_split_f16x2_seq images: a tap-walking kernel (the windows' stride says which:
     // 3 gemm_h3p3_kernel, anything else gemm_h3p_kernel) or nothing
@@ -427,8 +432,9 @@ int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st) {
                   "images, of two plain matrices, or form 0 over f2g_split_f16x2_seq images of stride-1 windows of 5 or "
                   "2 positions or of stride-3 windows of 5 positions over a multiple of 128 channels, or form 0 over the fp32 map (A.split = 8) under stride-3 windows of 5 positions over 32 channels or stride-1 windows of 2 or 1 positions over 128 channels onto at most 32 columns against a f2g_split_f16x2_seq image, or form 2 + atomic over f2g_split_f16x2_cols images of a plain matrix and of the map "
                   "under unbounded stride-1 windows of 5 positions, or of stride-3 windows of 5 positions that overhang a "
-                  "sequence of seq_stride / unit map rows by at most pad0 rows (f2g_gemm_f16_ok(d) != 1 for this "
-                  "descriptor)");
+                  "sequence of seq_stride / unit map rows by at most pad0 rows, or form 2 + atomic over a plain fp32 matrix "
+                  "of 128 columns and the fp32 map under such stride-3 windows over 32 channels, both marked split = 8 "
+                  "without rscale (f2g_gemm_f16_ok(d) != 1 for this descriptor)");
     return F2G_EINVAL;
   }
   switch (r.kernel) {
@@ -438,6 +444,7 @@ int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st) {
     case H3_TAPN: return f2g_launch_h3pn(d, r.taps, st);
     case H3_TAPW: return f2g_launch_h3wt(d, st);
     case H3_TAPW3: return f2g_launch_h3ws(d, st);
+    case H3_TAPW3N: return f2g_launch_h3wsn(d, st);
     case H3_WGRAD: {
       const int M = d.A.cols, N = d.B.cols, K = d.A.rows, split = d.split_k > 1 ? d.split_k : 1;
       const int kchunk = ((K + split - 1) / split + BK - 1) / BK * BK;

@@ -1022,7 +1022,7 @@ def _fp16x3_gemm(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offse
     True: one took the launch -- d.A / d.B are its images, its counter went up.  False: the launch goes the bf16x6
     way (d.precision may be left at 4: gemm() sets it)."""
     global FP16X3_LAUNCHES, FP16X3_WGRAD_LAUNCHES, FP16X3_TAP_LAUNCHES, FP16X3_TAPW_LAUNCHES, FP16X3_TAP3_LAUNCHES
-    global FP16X3_TAPW3_LAUNCHES, FP16X3_TAP3N_LAUNCHES, FP16X3_TAPN_LAUNCHES
+    global FP16X3_TAPW3_LAUNCHES, FP16X3_TAP3N_LAUNCHES, FP16X3_TAPN_LAUNCHES, FP16X3_TAPW3N_LAUNCHES
     if not (GEMM_PRECISION == 3 and FP16X3) or A.split != 0 or Bm.split != 0 or out.dtype != torch.float32:
         return False
 
@@ -1044,6 +1044,19 @@ def _fp16x3_gemm(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offse
         d.A, d.B = _f16_cols_operand(A), _f16_cols_operand(Bm)
         FP16X3_WGRAD_LAUNCHES += 1
         return True
+    if wgrad and a_plain and A.cols == 128 and Bm.P1 == 1 and Bm.P0 > 1 and Bm.step0 == 3 and Bm.unbounded \
+            and Bm.unit == 32 and Bm.cols == 5 * Bm.unit and A.rows >= FP16X3_TAPW3N_MIN_ROWS:
+        # fp16x3 weight gradient of the STRIDE-3 five-tap layer over 32 channels onto 128 (the MPD's 32 -> 128 layer): NO
+        # images -- d.A and d.B stay the caller's fp32 gradient matrix and map, both marked split = 8, and
+        # gemm_h3wsn_kernel scales each under one running scale per block and splits it while staging; nothing is
+        # allocated per call.  The library answers 1 or 0 (there is nothing to make first); what it declines goes the
+        # bf16x6 way
+        d.A.split = d.B.split = 8
+        d.precision = 4
+        if L.lib.f2g_gemm_f16_ok(C.byref(d)) == 1:
+            FP16X3_TAPW3N_LAUNCHES += 1
+            return True
+        d.A.split = d.B.split = 0
     if wgrad and a_plain and Bm.P1 == 1 and Bm.P0 > 1 and Bm.step0 == 1 and Bm.unbounded \
             and Bm.cols == 5 * Bm.unit and A.rows >= FP16X3_TAPW_MIN_ROWS and _f16_cols_window_ok(Bm) and takes():
         # fp16x3 tap-walking weight gradient (the MPD's stride-1 1024-channel layer): the gradient as a plain K-major
@@ -1590,6 +1603,15 @@ FP16X3_TAPN_LAUNCHES = 0   # launches gemm_h3pn_kernel took (tests and tools)
 # it on)
 FP16X3_TAPW3_MIN_ROWS = opt("fp16x3_tapw3_min_rows", FP16X3_TAP_OFF)
 FP16X3_TAPW3_LAUNCHES = 0  # launches gemm_h3ws_kernel took (tests and tools)
+# F2G_GEMM=fp16x3: the fewest reduction rows at which the weight gradient of the STRIDE-3 five-tap layer over a
+# 32-CHANNEL halo map onto 128 channels (the MPD's 32 -> 128 layer; ops.wgrad over unbounded windows) takes
+# gemm_h3wsn_kernel (csrc/gemm_f16wsn.hip): both fp32 operands are read once, scaled under one running scale per operand
+# and block and split INSIDE the kernel -- no image pass, no allocation per call --, against the generic exact-fp32
+# kernel with a K split (gemm_leanw6s_kernel declines 32 channels).  profiles/fp16x3_tapw3n_shapes.txt (tools/fp16x3_tapw_shapes.py --step3n) has what was
+# measured.  The route ships off like the other tap-walking routes: FP16X3_TAP_OFF = disabled (tests and the tool
+# lower it; F2G_OPTS=fp16x3_tapw3n_min_rows=1 turns it on)
+FP16X3_TAPW3N_MIN_ROWS = opt("fp16x3_tapw3n_min_rows", FP16X3_TAP_OFF)
+FP16X3_TAPW3N_LAUNCHES = 0  # launches gemm_h3wsn_kernel took (tests and tools)
 
 
 def set_gemm_precision(name: str) -> None:

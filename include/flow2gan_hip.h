@@ -96,8 +96,12 @@ typedef struct {
    *    mark says: scale it per sequence segment and split it inside the precision-4 kernel.  Two kernels read it
    *    (f2g_split_f16x2_seq below has both): stride-3 windows of 5 positions over 32 channels (gemm_h3p3n_kernel), and
    *    stride-1 windows of 2 or 1 positions over 128 channels onto at most 32 columns (gemm_h3pn_kernel); the
-   *    windows' stride says which.  There is no image; `rscale` is ignored.  A descriptor so marked that fails a
-   *    condition of its kernel is F2G_EINVAL, never run elsewhere */
+   *    windows' stride says which.  There is no image; `rscale` is ignored.
+   *    (BOTH operands of a precision-4, FORM-2 launch) the same mark on the fp32 gradient matrix A and on the fp32
+   *    halo map B under unbounded windows: the weight gradient of a stride-3 five-tap layer over 32 channels onto 128
+   *    (gemm_h3wsn_kernel; f2g_split_f16x2_cols below has it), each operand scaled under one running scale per block
+   *    and split inside the kernel.  There are no images; `rscale` must be NULL on both.
+   *    A descriptor so marked that fails a condition of its kernel is F2G_EINVAL, never run elsewhere */
   int32_t split;
   const float* alpha;
   const float* lrelu_src;
@@ -208,7 +212,9 @@ typedef struct {
    *     form 0 over stride-3 windows of 5 positions of an fp32 halo map with unit == 32 marked split = 8 (scaled and
    *     split inside the kernel) against a plain weight matrix given as its f2g_split_f16x2_seq image;
    *     form 0 over stride-1 windows of 2 or 1 positions of an fp32 halo map with unit == 128 marked split = 8 against
-   *     a plain weight matrix of at most 32 rows given as its f2g_split_f16x2_seq image.
+   *     a plain weight matrix of at most 32 rows given as its f2g_split_f16x2_seq image;
+   *     form 2 with E.atomic over a plain fp32 matrix A of 128 columns and unbounded stride-3 windows B of 5 positions
+   *     of an fp32 halo map with unit == 32, both marked split = 8 without rscale (scaled and split inside the kernel).
    *     A descriptor f2g_gemm_f16_ok does not answer with 1 is F2G_EINVAL, never run elsewhere. */
   int32_t precision;
   int32_t _pad3;
@@ -311,7 +317,19 @@ int f2g_gemm_f16_ok(const f2g_gemm_desc* d);
  * (a sequence has HpIn = seq_stride / unit map rows, the map (B.rows / P0) * HpIn in all) and windows that overhang a
  * sequence by at most pad0 rows at either end: 3 * (P0 - 1) + 5 - pad0 <= HpIn + pad0.  Tap and stride only select
  * rows, so the images, the scales and the rescale before the atomic add are the same; the launcher cuts chunks of
- * whole sequences.  A step0 other than 1 or 3 is 0.  f2g_gemm_last_kernel reports "h3ws<taps=5,step=3>", path 6. */
+ * whole sequences.  A step0 other than 1 or 3 is 0.  f2g_gemm_last_kernel reports "h3ws<taps=5,step=3>", path 6.
+ * WITHOUT IMAGES (gemm_h3wsn_kernel: the MPD's 32 -> 128 layer, whose long thin maps the two image passes would cost
+ * more than the launch): the same stride-3 sum with A.cols == 128, B.unit == 32, B.cols == 160, E.ldc >= 160 and both
+ * operands the fp32 buffers themselves, marked split = 8 with rscale == NULL; the other conditions as above.  A block
+ * owns the whole 128 x 160 output and walks a contiguous range of slabs (16 gradient rows of one sequence and the 50
+ * map rows they touch; at most 512 blocks, at least 16 slabs each unless the grid is one block) under ONE MONOTONE
+ * RUNNING SCALE per operand: m_run = 0 (scale 1) at the block's first slab, m_run = max(m_run, m_T) over every staged
+ * float before slab T is split -- a slab whose maximum is zero or not finite leaves it alone --, s = 2^(14 -
+ * floor(log2 m_run)) as for a row of f2g_split_f16x2, the stored sums following every change of scale by exact powers
+ * of two.  Error per output: 3 * 2^-22 sum |g||x| + 2^-28 sum_T (xrun_T sum_{rows in T} |g| + grun_T sum_{rows in T}
+ * |x|) with the running maxima in force at slab T.  Each block's sum is reproducible; the atomic adds between blocks
+ * reorder.  f2g_gemm_f16_ok answers 1 or 0 (there is nothing to make first); a descriptor with only one operand
+ * marked, or marked at any other shape, is 0.  f2g_gemm_last_kernel reports "h3wsn<taps=5,step=3>", path 6. */
 int f2g_split_f16x2_cols(float* dst, float* rscale, uint32_t* work, const float* src, int64_t ld, int32_t rows,
                          int32_t cols, f2g_stream_t stream);
 /* The image of a HALO MAP whose stride-1 conv windows are the A operand of a precision-4, form-0 GEMM, and of that

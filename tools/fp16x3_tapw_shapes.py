@@ -24,8 +24,16 @@ per period at B = 64 and B = 16 under the same timing conditions (both image cal
 stage-2 step in the fp16x3 mode with that tunable alone differing, in three alternating pairs of blocks, reported as
 medians and within-leg ranges.
 
+--step3n measures the weight gradient of the 32 -> 128 STRIDE-3 layer on the kernel that scales both fp32 operands
+inside itself (gemm_h3wsn_kernel, ops.FP16X3_TAPW3N_MIN_ROWS; default output profiles/fp16x3_tapw3n_shapes.txt): leg
+wgrad2 (128 x 160 outputs; the map has heights(p)[1] rows per sequence, the gradient heights(p)[2]) per period at B = 64
+and B = 16.  Both legs run in the fp16x3 mode with that tunable alone differing -- off, the library launches what it
+launched before the kernel existed, and the table names it --, in three alternating blocks of 12 launches per leg,
+reported as medians and within-leg ranges, with the bytes per second of reading both operands once.  Then the stage-2
+step as for --step3.
+
     python tools/fp16x3_tapw_shapes.py [--out profiles/fp16x3_tapw_shapes.txt] [--append] [--no-shapes] [--no-steps]
-                                       [--min-rows R] [--step3]
+                                       [--min-rows R] [--step3 | --step3n]
 """
 import argparse
 import os
@@ -105,6 +113,53 @@ def shapes3_table(ops, dev, say):
         f"spread: {seen.count('loses')}, inside the spread: {seen.count('inside')}")
 
 
+def shapes3n_table(ops, dev, say, min_rows, blocks=3, reps=12):
+    """the 32 -> 128 layer: the route off and on in the fp16x3 mode, the legs alternating block by block"""
+    import statistics
+    from flow2gan_amd import fused_disc as FD
+    ops.set_gemm_precision("fp16x3")
+    legs = (("off", ops.FP16X3_TAP_OFF), ("on", min_rows))
+    say("batch period  launch     rows     MB   off_us   min..max     on_us   min..max  ratio  beyond ranges  "
+        "GB/s(on)  kernels off | on")
+    seen = []
+    for batch in BATCHES:
+        for p in PERIODS:
+            rows, Cin, Cout, fn = case3(ops, FD, p, dev, batch, 1)
+            S, H = 2 * batch * p, heights(p)[1]
+            mb = (rows * Cout + S * (H + 2 * FD.HALO) * Cin) * 4e-6
+            per, kern = {k: [] for k, _ in legs}, {}
+            for k, r in legs:               # warm-up: code objects
+                ops.FP16X3_TAPW3N_MIN_ROWS = r
+                n0 = ops.FP16X3_TAPW3N_LAUNCHES
+                for _ in range(3):
+                    fn()
+                kern[k] = ops.L.lib.f2g_gemm_last_kernel().decode()
+                assert (ops.FP16X3_TAPW3N_LAUNCHES > n0) == (k == "on"), f"B {batch} period {p}: leg {k}"
+            assert kern["on"].startswith("h3wsn") and not kern["off"].startswith("h3")
+            torch.cuda.synchronize()
+            for _ in range(blocks):
+                for k, r in legs:
+                    ops.FP16X3_TAPW3N_MIN_ROWS = r
+                    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    s.record()
+                    for _ in range(reps):
+                        fn()
+                    e.record()
+                    torch.cuda.synchronize()
+                    per[k].append(s.elapsed_time(e) * 1e3 / reps)
+            a, b = statistics.median(per["off"]), statistics.median(per["on"])
+            verdict = "wins" if max(per["on"]) < min(per["off"]) else \
+                ("loses" if min(per["on"]) > max(per["off"]) else "inside")
+            say(f"{batch:5d} {p:6d}  wgrad2  {rows:7d} {mb:6.1f} {a:8.1f} {min(per['off']):6.1f}..{max(per['off']):<6.1f}"
+                f" {b:8.1f} {min(per['on']):6.1f}..{max(per['on']):<6.1f} {b / a:6.3f}  {verdict:13s} {mb / b * 1e3:8.0f}  "
+                f"{kern['off']} | {kern['on']}")
+            seen.append(verdict)
+            del fn
+            torch.cuda.empty_cache()
+    say(f"# launches: {len(seen)}; the route wins beyond the legs' ranges: {seen.count('wins')}, loses beyond them: "
+        f"{seen.count('loses')}, ranges overlap: {seen.count('inside')}")
+
+
 def shapes_table(ops, dev, say):
     from flow2gan_amd import fused_disc as FD
     say("batch period     rows  bf16x6_us  spread  fp16x3_us  spread  ratio  TFLOP/s(fp16x3)  kernels")
@@ -133,7 +188,7 @@ def shapes_table(ops, dev, say):
         say("# not every accepted launch wins by more than its spread: the default stays off")
 
 
-def steps_table(ops, dev, say, min_rows, steps=4, step3=False):
+def steps_table(ops, dev, say, min_rows, steps=4, step3=False, step3n=False):
     import flow2gan_amd
     from flow2gan_amd import harness
     from flow2gan_amd.models.config import get_gan_config, get_generator_config
@@ -164,6 +219,8 @@ def steps_table(ops, dev, say, min_rows, steps=4, step3=False):
     # (--step3: the stride-3 tunable alone differing, three alternating pairs)
     tunable, counter, blocks = ("FP16X3_TAPW3_MIN_ROWS", "FP16X3_TAPW3_LAUNCHES", 3) if step3 else \
         ("FP16X3_TAPW_MIN_ROWS", "FP16X3_TAPW_LAUNCHES", 7)
+    if step3n:
+        tunable, counter, blocks, step3 = "FP16X3_TAPW3N_MIN_ROWS", "FP16X3_TAPW3N_LAUNCHES", 3, True
     per = {leg[0]: [] for leg in legs}
     launches = {leg[0]: 0 for leg in legs}
     for name, rows in legs:
@@ -203,6 +260,8 @@ def main():
                     "fp16x3_tapw3_shapes.txt)")
     ap.add_argument("--step3", action="store_true", help="measure the stride-3 layers' weight gradient (legs wgrad3 / "
                     "wgrad4) instead")
+    ap.add_argument("--step3n", action="store_true", help="measure the 32 -> 128 stride-3 layer's weight gradient on "
+                    "the kernel that scales the fp32 operands itself (leg wgrad2) instead")
     ap.add_argument("--append", action="store_true", help="add this run's table to --out instead of replacing it")
     ap.add_argument("--no-steps", action="store_true")
     ap.add_argument("--no-shapes", action="store_true")
@@ -210,12 +269,13 @@ def main():
                     "of the table on the new kernel)")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "fp16x3_tapw3_shapes.txt" if args.step3 else "fp16x3_tapw_shapes.txt")
+        args.out = os.path.join(ROOT, "profiles", "fp16x3_tapw3n_shapes.txt" if args.step3n else
+                                "fp16x3_tapw3_shapes.txt" if args.step3 else "fp16x3_tapw_shapes.txt")
     assert torch.cuda.is_available(), "needs an MI355X"
     from flow2gan_amd import ops
     if args.min_rows < 1 or args.min_rows >= ops.FP16X3_TAP_OFF:
         ap.error("--min-rows must enable the route: both modes would time the same bf16x6 launch otherwise")
-    was_rows, was_rows3 = ops.FP16X3_TAPW_MIN_ROWS, ops.FP16X3_TAPW3_MIN_ROWS
+    was_rows, was_rows3, was_rows3n = ops.FP16X3_TAPW_MIN_ROWS, ops.FP16X3_TAPW3_MIN_ROWS, ops.FP16X3_TAPW3N_MIN_ROWS
     dev = torch.device("cuda")
     lines = []
 
@@ -226,23 +286,32 @@ def main():
     given = [a for i, a in enumerate(sys.argv[1:], 1) if a != "--out" and sys.argv[i - 1] != "--out"]
     say("# command (the output path aside): python tools/fp16x3_tapw_shapes.py " + " ".join(given))
     say(f"# tools/fp16x3_tapw_shapes.py  {ops.L.version()}  "
-        + (f"FP16X3_TAPW3_MIN_ROWS={args.min_rows} FP16X3_TAPW_MIN_ROWS={was_rows}" if args.step3 else
+        + (f"FP16X3_TAPW3N_MIN_ROWS={args.min_rows} FP16X3_TAPW3_MIN_ROWS={was_rows3} FP16X3_TAPW_MIN_ROWS={was_rows}"
+           if args.step3n else
+           f"FP16X3_TAPW3_MIN_ROWS={args.min_rows} FP16X3_TAPW_MIN_ROWS={was_rows}" if args.step3 else
            f"FP16X3_TAPW_MIN_ROWS={args.min_rows}") + f"  {torch.cuda.get_device_name(0)}")
-    say("# per-launch medians of 5 alternating blocks of 12 launches (us), both column-image calls included in the "
-        "fp16x3 leg; spread = (max - min) / median of a mode's blocks; ratio = fp16x3 / bf16x6 (< 1: fp16x3 faster)")
+    if args.step3n:
+        say("# per-launch medians and ranges of 3 alternating blocks of 12 launches (us) per leg, both legs in the fp16x3 "
+            "mode: off = the tunable at its default, on = at --min-rows; ratio = on / off (< 1: the route faster); MB = "
+            "both fp32 operands read once")
+    else:
+        say("# per-launch medians of 5 alternating blocks of 12 launches (us), both column-image calls included in the "
+            "fp16x3 leg; spread = (max - min) / median of a mode's blocks; ratio = fp16x3 / bf16x6 (< 1: fp16x3 faster)")
     from test_hip_gemm_f16 import mode_name       # (the one place that names the mode in force)
     was = mode_name(ops)
     try:
-        if not args.no_shapes and args.step3:
+        if not args.no_shapes and args.step3n:
+            shapes3n_table(ops, dev, say, args.min_rows)
+        elif not args.no_shapes and args.step3:
             ops.FP16X3_TAPW3_MIN_ROWS = args.min_rows
             shapes3_table(ops, dev, say)
         elif not args.no_shapes:
             ops.FP16X3_TAPW_MIN_ROWS = args.min_rows
             shapes_table(ops, dev, say)
         if not args.no_steps:
-            steps_table(ops, dev, say, args.min_rows, step3=args.step3)
+            steps_table(ops, dev, say, args.min_rows, step3=args.step3, step3n=args.step3n)
     finally:
-        ops.FP16X3_TAPW_MIN_ROWS, ops.FP16X3_TAPW3_MIN_ROWS = was_rows, was_rows3
+        ops.FP16X3_TAPW_MIN_ROWS, ops.FP16X3_TAPW3_MIN_ROWS, ops.FP16X3_TAPW3N_MIN_ROWS = was_rows, was_rows3, was_rows3n
         ops.set_gemm_precision(was)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "a" if args.append else "w") as f:
