@@ -13,6 +13,8 @@ The names (each declared in flow2gan_amd/ops.py unless noted): conv32_x6, fft, f
 eager_rebuild, time_ahead (models/generator.py), colsum_parts, x6f, x6g, x3_check, multi_cap, lane_cap_<pool>,
 x6_min_k, x6_min_rows, x6_nopass_k, x6f_min_k, x6f_min_n, x6f_min_tiles, x6f_tall_rows, fp16x3_min_k, fp16x3_min_n
 (F2G_GEMM=fp16x3: the shortest reduction and the fewest output columns the fp16x3 GEMM kernel takes),
+fp16x3_plainn_min_n (the fewest output columns at which such a GEMM takes the fp16x3 kernel that reads the fp32
+activation matrix itself and scales it per 128-row tile inside the kernel, without an image pass; off by default),
 fp16x3_wgrad_min_rows (the fewest reduction rows at which a weight gradient takes the fp16x3 weight-gradient kernel),
 fp16x3_tap_min_rows (the fewest output rows at which a GEMM over stride-1 windows of a halo map takes the fp16x3
 tap-walking kernel; the route also asks for a reduction of at least x6_min_k, i.e. the launches the bf16x6 mode gives

@@ -1,5 +1,5 @@
 // What more than one of the GEMM translation units needs (gemm.hip, gemm_lean.hip, gemm_wgrad.hip, gemm_x6.hip,
-// gemm_x6p.hip, gemm_f16.hip, gemm_f16p.hip, gemm_f16p3.hip, gemm_f16p3n.hip, gemm_f16pn.hip, gemm_f16wt.hip, gemm_f16ws.hip, gemm_f16wsn.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
+// gemm_x6p.hip, gemm_f16.hip, gemm_f16p.hip, gemm_f16p3.hip, gemm_f16p3n.hip, gemm_f16pn.hip, gemm_f16wt.hip, gemm_f16ws.hip, gemm_f16wsn.hip, gemm_f16n.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
 // three-piece split, the LDS barrier, the lab switches, and the host functions that cross those files.  Everything
 // defined here has internal linkage; no GEMM file includes another.  (gemm_f16_common.h: what only fp16x3 shares.)
 #pragma once
@@ -58,6 +58,10 @@ int f2g_launch_h3ws(const f2g_gemm_desc& d, hipStream_t st);
 // f2g_h3wsn_ok: 1 = runs as handed over, 0 = not for this kernel (there is nothing to make first: no 2)
 int f2g_h3wsn_ok(const f2g_gemm_desc& d);
 int f2g_launch_h3wsn(const f2g_gemm_desc& d, hipStream_t st);
+// gemm_f16n.hip: precision 4, form 0 over a plain fp32 matrix A marked split = 9 (no image, no rscale) against B's
+// f2g_split_f16x2 image: gemm_h3_kernel with A scaled under one running scale per 128-row tile and split inside
+// gemm_h3n_kernel.  gemm_f16.hip's h3_plain_ok decides (1 with B's image, 2 with B fp32, 0 otherwise)
+int f2g_launch_h3n(const f2g_gemm_desc& d, hipStream_t st);
 
 // ---- lab switches (product builds: both 0) ---------------------------------------------------------------------
 // F2G_LABVAR (tools/micro/build_variants.sh; timing only): ablations of the bf16 lean K loop (gemm_lean.hip) --

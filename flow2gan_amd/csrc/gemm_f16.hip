@@ -4,8 +4,9 @@
 // (gemm_f16p.hip: f2g_split_f16x2_seq and gemm_h3p_kernel, the same over stride-1 windows of a halo map;
 // gemm_f16p3.hip: gemm_h3p3_kernel, the same over stride-3 windows; gemm_f16wt.hip: gemm_h3wt_kernel, the weight
 // gradient of a stride-1 layer over column images; gemm_f16ws.hip: gemm_h3ws_kernel, that of a stride-3 layer;
-// gemm_f16wsn.hip: gemm_h3wsn_kernel, that of the 32-channel stride-3 layer over the fp32 operands themselves.)  The
-// kernels share
+// gemm_f16wsn.hip: gemm_h3wsn_kernel, that of the 32-channel stride-3 layer over the fp32 operands themselves;
+// gemm_f16n.hip: gemm_h3n_kernel, gemm_h3_kernel over the fp32 activation matrix itself, scaled per row tile inside
+// the kernel.)  The kernels share
 // gemm_f16_common.h, the image writers split_f16.h; h3_route_of below says which kernel a descriptor belongs to.
 #include <stddef.h>
 #include <stdint.h>
@@ -365,20 +366,24 @@ inline bool h3w_operand_ok(const f2g_operand& S) {
 // that kernel; 1: runs as handed over, both operands the kernel's images with their reciprocal scales; 2: once both
 // fp32 operands are replaced by those images) and the taps of H3_TAP.  The shape of the operands picks the candidate,
 // the candidate's own conditions decide: a descriptor one kernel declines is never offered to another.
-enum h3_kernel { H3_NONE, H3_PLAIN, H3_WGRAD, H3_TAP, H3_TAP3, H3_TAP3N, H3_TAPN, H3_TAPW, H3_TAPW3, H3_TAPW3N };
+enum h3_kernel { H3_NONE, H3_PLAIN, H3_PLAINN, H3_WGRAD, H3_TAP, H3_TAP3, H3_TAP3N, H3_TAPN, H3_TAPW, H3_TAPW3, H3_TAPW3N };
 struct h3_route {
   h3_kernel kernel = H3_NONE;
   int status = 0, taps = 0;
 };
 
+// A marked split = 9 (gemm_h3n_kernel, gemm_f16n.hip: the fp32 matrix itself, scaled per row tile inside the kernel):
+// the same conditions, A without rscale, and the answer follows B alone -- 1 with its image and rscale, 2 while fp32
 int h3_plain_ok(const f2g_gemm_desc& d) {
   if (d.A.cols != d.B.cols || !h3_operand_ok(d.A) || !h3_operand_ok(d.B)) return 0;
+  if (d.A.split == 9 && d.A.rscale) return 0;
   const f2g_epilogue& E = d.E;
   if (d.split_k > 1 || E.x3_out || E.colsum_part_ld > 0 || E.c_bf16) return 0;
   // (the combinations f2g_gemm refuses for every kernel)
   if (E.prelu_slope && (E.atomic || E.accumulate || E.P0o > 0)) return 0;
   if (E.mask_src && (E.atomic || E.accumulate)) return 0;
   if (E.aux && !E.alpha_n) return 0;
+  if (d.A.split == 9) return d.B.split == 5 ? (d.B.rscale ? 1 : 0) : (d.B.split == 0 ? 2 : 0);
   return f16_images_status(d.A, d.B, 5);
 }
 
@@ -409,13 +414,15 @@ h3_route h3_route_of(const f2g_gemm_desc& d) {
     // 3 gemm_h3p3_kernel, anything else gemm_h3p_kernel) or nothing
     // A marked split = 8 (the fp32 map, scaled inside the kernel): the windows' stride says which -- 3
     // gemm_h3p3n_kernel (gemm_f16p3n.hip), anything else gemm_h3pn_kernel (gemm_f16pn.hip) -- or nothing
+    // A marked split = 9 (the fp32 matrix, scaled per row tile inside the kernel): gemm_h3n_kernel (gemm_f16n.hip) or
+    // nothing -- h3_plain_ok declines a window operand so marked
     const bool win = !host_plain(d.A);
-    cand = d.A.split == 8 ? (d.A.step0 == 3 ? H3_TAP3N : H3_TAPN)
+    cand = d.A.split == 9 ? H3_PLAINN : d.A.split == 8 ? (d.A.step0 == 3 ? H3_TAP3N : H3_TAPN)
                           : (win && d.A.step0 == 3 ? H3_TAP3 : (win || d.A.split == 7 || d.B.split == 7 ? H3_TAP : H3_PLAIN));
     if (cand == H3_TAP3N) r.status = f2g_h3p3n_ok(d), r.taps = 5;
     else if (cand == H3_TAPN) r.status = f2g_h3pn_ok(d, &r.taps);
     else if (cand == H3_TAP3) r.status = f2g_h3p3_ok(d), r.taps = 5;
-    else r.status = cand == H3_TAP ? f2g_h3p_ok(d, &r.taps) : h3_plain_ok(d);
+    else r.status = cand == H3_TAP ? f2g_h3p_ok(d, &r.taps) : h3_plain_ok(d);      // (H3_PLAIN, H3_PLAINN)
   }
   if (r.status) r.kernel = cand;
   return r;
@@ -428,7 +435,8 @@ extern "C" int f2g_gemm_f16_ok(const f2g_gemm_desc* dp) { return dp ? h3_route_o
 int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st) {
   const h3_route r = h3_route_of(d);
   if (r.status != 1) {
-    f2g_set_error("f2g_gemm precision 4: form 0 over f2g_split_f16x2 images, or form 2 over f2g_split_f16x2_cols "
+    f2g_set_error("f2g_gemm precision 4: form 0 over f2g_split_f16x2 images, or form 0 over the plain fp32 matrix A "
+                  "itself (A.split = 9 without rscale) against B's f2g_split_f16x2 image, or form 2 over f2g_split_f16x2_cols "
                   "images, of two plain matrices, or form 0 over f2g_split_f16x2_seq images of stride-1 windows of 5 or "
                   "2 positions or of stride-3 windows of 5 positions over a multiple of 128 channels, or form 0 over the fp32 map (A.split = 8) under stride-3 windows of 5 positions over 32 channels or stride-1 windows of 2 or 1 positions over 128 channels onto at most 32 columns against a f2g_split_f16x2_seq image, or form 2 + atomic over f2g_split_f16x2_cols images of a plain matrix and of the map "
                   "under unbounded stride-1 windows of 5 positions, or of stride-3 windows of 5 positions that overhang a "
@@ -445,6 +453,7 @@ int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st) {
     case H3_TAPW: return f2g_launch_h3wt(d, st);
     case H3_TAPW3: return f2g_launch_h3ws(d, st);
     case H3_TAPW3N: return f2g_launch_h3wsn(d, st);
+    case H3_PLAINN: return f2g_launch_h3n(d, st);
     case H3_WGRAD: {
       const int M = d.A.cols, N = d.B.cols, K = d.A.rows, split = d.split_k > 1 ? d.split_k : 1;
       const int kchunk = ((K + split - 1) / split + BK - 1) / BK * BK;

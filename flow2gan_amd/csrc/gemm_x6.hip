@@ -836,6 +836,8 @@ extern "C" int32_t f2g_gemm_colsum_part_rows(const f2g_gemm_desc* dp) {
   // precision 4: the tap-walking kernels alone have the wide epilogue (gemm_f16p.hip, gemm_f16p3.hip; 256-row tiles)
   // (gemm_f16p3n.hip: 128-row tiles; gemm_f16pn.hip, the other user of split = 8, has the thin epilogue: no partial
   // rows -- f2g_h3p3n_ok declines its stride-1 windows)
+  // (gemm_f16n.hip: A marked split = 9, gemm_h3_kernel's generic epilogue -- no partial rows)
+  if (d.precision == 4 && d.A.split == 9) return 0;
   if (d.precision == 4 && d.A.split == 8) return f2g_h3p3n_ok(d) ? 2 * ((d.A.rows + 127) / 128) : 0;
   if (d.precision == 4) return f2g_h3p_ok(d, nullptr) || f2g_h3p3_ok(d) ? 4 * ((d.A.rows + 255) / 256) : 0;
   if (!x6_wide(d)) return 0;

@@ -1023,6 +1023,7 @@ def _fp16x3_gemm(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offse
     way (d.precision may be left at 4: gemm() sets it)."""
     global FP16X3_LAUNCHES, FP16X3_WGRAD_LAUNCHES, FP16X3_TAP_LAUNCHES, FP16X3_TAPW_LAUNCHES, FP16X3_TAP3_LAUNCHES
     global FP16X3_TAPW3_LAUNCHES, FP16X3_TAP3N_LAUNCHES, FP16X3_TAPN_LAUNCHES, FP16X3_TAPW3N_LAUNCHES
+    global FP16X3_PLAINN_LAUNCHES
     if not (GEMM_PRECISION == 3 and FP16X3) or A.split != 0 or Bm.split != 0 or out.dtype != torch.float32:
         return False
 
@@ -1031,6 +1032,17 @@ def _fp16x3_gemm(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offse
         return L.lib.f2g_gemm_f16_ok(C.byref(d)) == 2
     a_plain, b_plain = A.P0 == 1 and A.P1 == 1, Bm.P0 == 1 and Bm.P1 == 1
     wgrad = form == 2 and atomic and A.lrelu_src is None
+    if form == 0 and a_plain and A.cols >= FP16X3_MIN_K and Bm.rows >= FP16X3_PLAINN_MIN_N and split_k <= 1:
+        # fp16x3 over the fp32 activation matrix ITSELF: NO image of A -- d.A stays the caller's operand, marked
+        # split = 9, and gemm_h3n_kernel scales it under one running scale per 128-row tile and splits it while
+        # staging; nothing is allocated per call.  The weight's f2g_split_f16x2 image comes from the derived-weight
+        # cache.  What the library declines falls through with the mark cleared (the image route below, then bf16x6)
+        d.A.split = 9
+        if takes():
+            d.B = _f16_operand(Bm)
+            FP16X3_PLAINN_LAUNCHES += 1
+            return True
+        d.A.split = 0
     if form == 0 and a_plain and A.cols >= FP16X3_MIN_K and Bm.rows >= FP16X3_MIN_N and split_k <= 1 and takes():
         # fp16x3: two plain matrices (a data gradient arrives here as form 0 over the cached transpose) as
         # f2g_split_f16x2 images -- the weight's from the derived-weight cache, the activation's made here.  The
@@ -1553,6 +1565,20 @@ FP16X3_WGRAD_LAUNCHES = 0  # launches gemm_h3w_kernel took (tests and tools)
 FP16X3_TAP_OFF = 1 << 30
 FP16X3_TAP_MIN_ROWS = opt("fp16x3_tap_min_rows", 9504)
 FP16X3_TAP_LAUNCHES = 0    # launches gemm_h3p_kernel took (tests and tools)
+# F2G_GEMM=fp16x3: the fewest output columns at which a forward-form GEMM over two plain matrices with a reduction of at
+# least FP16X3_MIN_K takes gemm_h3n_kernel (csrc/gemm_f16n.hip) -- gemm_h3_kernel reading the fp32 activation matrix as
+# it is (4 bytes per element, as gemm_x6g_kernel), scaled under one running scale per 128-row tile and split INSIDE the
+# kernel: no image pass, no allocation per call; the weight's image stays the cached one.  The route is tried before the
+# image route (FP16X3_MIN_N above).  Measured on one box, three legs alternating over the 36 launches of
+# profiles/fp16x3_gemm_shapes.txt (tools/fp16x3_shapes.py --noimage -> profiles/fp16x3_gemm_noimage_shapes.txt): against
+# bf16x6 no launch wins beyond the spread and 21 lose (768 -> 2304 at 0.916-1.116 of the bf16x6 time, the other shapes
+# 0.984-1.553); against the image route 9 win and 8 lose; stage 1 31.67 -> 35.33 ms and stage 2 145.38 -> 149.04 ms with
+# the tunable alone differing (153 / 234 launches per step).  Every one of the N / 128 column tiles splits its A tile
+# again beside its MFMAs.  The route ships off whatever that file says -- turning it on, or changing
+# FP16X3_MIN_N, is a change of its own: FP16X3_TAP_OFF = disabled (tests and the tool lower it;
+# F2G_OPTS=fp16x3_plainn_min_n=1 turns it on for every pointwise shape)
+FP16X3_PLAINN_MIN_N = opt("fp16x3_plainn_min_n", FP16X3_TAP_OFF)
+FP16X3_PLAINN_LAUNCHES = 0  # launches gemm_h3n_kernel took (tests and tools)
 # fewest reduction rows at which the weight gradient of a stride-1 five-tap layer over a halo map (the MPD's
 # 1024-channel layer; ops.wgrad over unbounded windows) goes to gemm_h3wt_kernel: the gradient and the whole map pay
 # f2g_split_f16x2_cols per call (two reads and one write each: 12 bytes per element), against gemm_leanw6t_kernel's

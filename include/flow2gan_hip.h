@@ -101,7 +101,11 @@ typedef struct {
    *    halo map B under unbounded windows: the weight gradient of a stride-3 five-tap layer over 32 channels onto 128
    *    (gemm_h3wsn_kernel; f2g_split_f16x2_cols below has it), each operand scaled under one running scale per block
    *    and split inside the kernel.  There are no images; `rscale` must be NULL on both.
-   *    A descriptor so marked that fails a condition of its kernel is F2G_EINVAL, never run elsewhere */
+   *    A descriptor so marked that fails a condition of its kernel is F2G_EINVAL, never run elsewhere;
+   * 9: (operand A of a precision-4, form-0 launch over a PLAIN matrix only) `base` is the fp32 matrix ITSELF, as for
+   *    split = 0, `rscale` must be NULL, and the mark says: scale it per 128-row tile and split it inside the kernel
+   *    (gemm_h3n_kernel; f2g_split_f16x2 below has it).  Operand B is the weight's f2g_split_f16x2 image (split = 5
+   *    with rscale).  A descriptor so marked that fails a condition of the kernel is F2G_EINVAL, never run elsewhere */
   int32_t split;
   const float* alpha;
   const float* lrelu_src;
@@ -201,7 +205,9 @@ typedef struct {
    *     for form 2, with E.atomic when split_k > 1 -- split into pieces inside the kernel;
    * 4 = fp16x3: fp32-class products from TWO fp16 pieces per operand, three MFMAs per product (per-product error
    *     <= 3 * 2^-22): form 0 over two plain matrices, both given as f2g_split_f16x2 images (f2g_operand.split = 5
-   *     with rscale); form 2 (weight gradient) over two plain matrices, both given as f2g_split_f16x2_cols images
+   *     with rscale); form 0 over the plain fp32 matrix A itself marked split = 9 without rscale (scaled per 128-row
+   *     tile and split inside the kernel) against B's f2g_split_f16x2 image;
+   *     form 2 (weight gradient) over two plain matrices, both given as f2g_split_f16x2_cols images
    *     (split = 6 with rscale: one scale per column, which leaves the sum over rows), E.atomic when split_k > 1;
    *     form 2 with E.atomic over a plain matrix A and unbounded stride-1 windows B of 5 positions of a halo map (the
    *     taps shift ROWS of the map, so one scale per column of the whole map leaves every tap's sum), both given as
@@ -279,7 +285,21 @@ int32_t f2g_gemm_colsum_part_rows(const f2g_gemm_desc* d);
  * epilogue (bias, residual, leaky ReLU, PReLU with both outputs, PReLU backward with column sums, accumulate /
  * atomic, row map, mask).  No x3_out, no colsum_part_ld, no bf16 output, no split-K.
  * f2g_gemm_f16_ok(d) applies the tests of that dispatch without launching: 1 = f2g_gemm runs d as handed over,
- * 2 = it would once both fp32 operands (split = 0) are replaced by their images, 0 = not at precision 4. */
+ * 2 = it would once both fp32 operands (split = 0) are replaced by their images, 0 = not at precision 4.
+ * WITHOUT AN IMAGE OF A (gemm_h3n_kernel, csrc/gemm_f16n.hip): operand A the plain fp32 matrix itself, marked
+ * split = 9 with rscale == NULL, operand B the image above with its rscale; the other conditions and every epilogue as
+ * above (K % 32 == 0, 32 <= K <= 4096, 16-byte aligned rows, rows * row stride * 4 < 0x7ff00000; no x3_out, no
+ * colsum_part_ld, no bf16 output, no split-K, no `alpha`).  The kernel is the one above with the split moved to where
+ * a staged chunk goes to LDS: every 128-row tile of A keeps ONE MONOTONE RUNNING SCALE -- m_run = 0 (scale 1) at the
+ * first slab of 32 reduction columns; before slab T is split m_run = max(m_run, m_T) over the slab's floats of the
+ * tile's rows inside the matrix, a slab whose maximum is zero or not finite leaving it alone; s = 2^(14 -
+ * floor(log2 m_run)) as for a row above; the stored sums follow every change of scale by an exact power of two --, and
+ * v = (acc0 + 2^-11 acc1) / s_run * rscale_b[col].  Error per output: 3 * 2^-22 sum_k |a||b| + 2^-28 sum_T arun_T
+ * sum_{k in T} |b_k| with arun_T the running maximum in force at slab T: rows share their tile's scale, so a row quiet
+ * against its tile sees the second term, which the per-row scale of the image spares it.  An inf or NaN stays in its
+ * row.  Reproducible (integer maxima, no atomics).  f2g_gemm_f16_ok answers 1 with B's image and rscale, 2 with B
+ * fp32 (= once B is replaced by its image), 0 for anything the kernel declines and for an A with rscale set;
+ * f2g_gemm_colsum_part_rows answers 0.  f2g_gemm_last_kernel reports "h3n<ep=all>", path 6. */
 int f2g_split_f16x2(float* dst, float* rscale, const float* src, int64_t ld, int32_t rows, int32_t K,
                     f2g_stream_t stream);
 int f2g_gemm_f16_ok(const f2g_gemm_desc* d);
@@ -403,7 +423,7 @@ int f2g_split_f16x2_seq(float* dst, float* rscale, const float* src, int64_t ld,
 int f2g_gemm_last_path(void);
 /* Kernel instance the last f2g_gemm call launched (tests and diagnostics, not thread safe; "" when it
  * launched nothing), e.g. "lean<sk=1,ep=3,pm=0>" (lean kernel: stream-K, epilogue instance, operand mode),
- * "lean_tall<ep=2,pm=1>", "lean_tap<ep=3>", "narrow_wgrad4<4>", "x6f<wimg=1>", "h3<ep=all>", "h3w", "h3p<taps=5>" or "generic<F1,GF,PF> split=3"
+ * "lean_tall<ep=2,pm=1>", "lean_tap<ep=3>", "narrow_wgrad4<4>", "x6f<wimg=1>", "h3<ep=all>", "h3n<ep=all>", "h3w", "h3p<taps=5>" or "generic<F1,GF,PF> split=3"
  * (generic MFMA tiles: form, loader modes of A and B, and the K split when > 1). */
 const char* f2g_gemm_last_kernel(void);
 
