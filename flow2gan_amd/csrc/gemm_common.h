@@ -1,7 +1,8 @@
 // What more than one of the GEMM translation units needs (gemm.hip, gemm_lean.hip, gemm_wgrad.hip, gemm_x6.hip,
-// gemm_x6p.hip, gemm_f16.hip, gemm_f16p.hip, gemm_f16p3.hip, gemm_f16p3n.hip, gemm_f16pn.hip, gemm_f16wt.hip, gemm_f16ws.hip, gemm_f16wsn.hip, gemm_f16n.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major fragment read, the
-// three-piece split, the LDS barrier, the lab switches, and the host functions that cross those files.  Everything
-// defined here has internal linkage; no GEMM file includes another.  (gemm_f16_common.h: what only fp16x3 shares.)
+// gemm_x6p.hip, gemm_f16*.hip): vector types, tile constants, the tile order, the generic epilogue, the K-major
+// fragment read, the three-piece split, the LDS barrier, the lab switches, and the host functions that cross those
+// files.  Everything defined here has internal linkage; no GEMM file includes another.  (gemm_f16_common.h: what only
+// fp16x3 shares; gemm_f16_checks.h: its host-side checks.)
 #pragma once
 #include "common.h"
 
@@ -18,50 +19,30 @@ bool f2g_leanw_fp32_takes(const f2g_gemm_desc& d, int split);
 int f2g_launch_leanw(const f2g_gemm_desc& d, int pieces, int split, hipStream_t st);
 // gemm_x6.hip: form 0 at precision 3 (checks the descriptor, picks the kernel, launches)
 int f2g_gemm_x6(const f2g_gemm_desc& d, hipStream_t st);
-// gemm_f16.hip: precision 4 -- decides which of the fp16x3 kernels a descriptor belongs to (its own two: form 0
-// over f2g_split_f16x2 images, form 2 over f2g_split_f16x2_cols images; the ones below), checks it, launches that one
+// gemm_f16.hip: precision 4 -- decides which of the fp16x3 kernels a descriptor belongs to (h3_table there lists them:
+// one entry per kernel, with what it takes), checks it, launches that one
 int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st);
-// gemm_f16p.hip: precision 4, form 0 over stride-1 windows of 5 or 2 positions of a halo map (gemm_h3p_kernel).
-// f2g_h3p_ok: 1 = runs as handed over (both operands f2g_split_f16x2_seq images with their reciprocal scales), 2 = once
-// both fp32 operands are replaced by those images, 0 = not for this kernel; `taps` receives 5 or 2
-int f2g_h3p_ok(const f2g_gemm_desc& d, int* taps);
-int f2g_launch_h3p(const f2g_gemm_desc& d, int taps, hipStream_t st);
-// gemm_f16p3.hip: precision 4, form 0 over STRIDE-3 windows of 5 positions of a halo map with a multiple of 128
-// channels (gemm_h3p3_kernel: the MPD's strided forward layers).  f2g_h3p3_ok answers as f2g_h3p_ok does
-int f2g_h3p3_ok(const f2g_gemm_desc& d);
+// ... and the tile height that kernel counts partial column sums in (one row per 64 output rows of whole tiles), 0
+// where it has no wide epilogue or declines the descriptor (f2g_gemm_colsum_part_rows)
+int f2g_gemm_h3_part_tile(const f2g_gemm_desc& d);
+// gemm_f16<x>.hip, one fp16x3 kernel each: f2g_h3<x>_ok answers f2g_gemm_f16_ok for the kernel's candidates -- 1 = runs
+// as handed over (the operands the kernel's images with their reciprocal scales, or fp32 under its mark), 2 = once the
+// fp32 operands are replaced by those images, 0 = not for this kernel -- and f2g_launch_h3<x> launches what it accepted
+int f2g_h3p_ok(const f2g_gemm_desc& d);        // form 0, stride-1 windows of 5 or 2 positions over seq images
+int f2g_launch_h3p(const f2g_gemm_desc& d, hipStream_t st);
+int f2g_h3p3_ok(const f2g_gemm_desc& d);       // ... stride-3 windows of 5 positions over a multiple of 128 channels
 int f2g_launch_h3p3(const f2g_gemm_desc& d, hipStream_t st);
-// gemm_f16p3n.hip: the same windows over 32 channels (K = 160, N <= 128: the MPD's 32 -> 128 forward layer), A = the
-// fp32 map itself, marked split = 8 and scaled per sequence segment inside gemm_h3p3n_kernel.  f2g_h3p3n_ok: 1 = runs
-// as handed over (B a f2g_split_f16x2_seq image with its reciprocal scales), 2 = once the fp32 B is replaced by that
-// image, 0 = not for this kernel
-int f2g_h3p3n_ok(const f2g_gemm_desc& d);
+int f2g_h3p3n_ok(const f2g_gemm_desc& d);      // ... over 32 channels of the fp32 map itself (A.split = 8), N <= 128
 int f2g_launch_h3p3n(const f2g_gemm_desc& d, hipStream_t st);
-// gemm_f16pn.hip: the other user of split = 8 -- STRIDE-1 windows of 2 or 1 positions over 128 channels onto N <= 32
-// columns (K = 256 / 128: the stride-residue data gradients of that layer), A = the fp32 map itself, scaled per
-// sequence segment inside gemm_h3pn_kernel.  f2g_h3pn_ok answers as f2g_h3p3n_ok does; `taps` receives 2 or 1
-int f2g_h3pn_ok(const f2g_gemm_desc& d, int* taps);
-int f2g_launch_h3pn(const f2g_gemm_desc& d, int taps, hipStream_t st);
-// gemm_f16wt.hip: precision 4, form 2 over unbounded stride-1 windows of 5 positions of a halo map (gemm_h3wt_kernel:
-// the tap-walking weight gradient).  f2g_h3wt_ok: 1 = runs as handed over (A and the whole map as
-// f2g_split_f16x2_cols images with their reciprocal scales), 2 = once both fp32 operands are replaced by those
-// images, 0 = not for this kernel
-int f2g_h3wt_ok(const f2g_gemm_desc& d);
+int f2g_h3pn_ok(const f2g_gemm_desc& d);       // ... stride-1 windows of 2 or 1 positions of the fp32 map, N <= 32
+int f2g_launch_h3pn(const f2g_gemm_desc& d, hipStream_t st);
+int f2g_h3wt_ok(const f2g_gemm_desc& d);       // form 2, unbounded stride-1 windows of 5 positions over column images
 int f2g_launch_h3wt(const f2g_gemm_desc& d, hipStream_t st);
-// gemm_f16ws.hip: the same over unbounded STRIDE-3 windows of 5 positions (gemm_h3ws_kernel: the weight gradient of
-// the MPD's strided layers; a sequence has seq_stride / unit map rows, its windows overhang it by at most pad0 rows).
-// f2g_h3ws_ok answers as f2g_h3wt_ok does
-int f2g_h3ws_ok(const f2g_gemm_desc& d);
+int f2g_h3ws_ok(const f2g_gemm_desc& d);       // ... stride-3 windows over a multiple of 128 channels
 int f2g_launch_h3ws(const f2g_gemm_desc& d, hipStream_t st);
-// gemm_f16wsn.hip: the user of split = 8 at form 2 -- the weight gradient of the 32-channel stride-3 layer (A plain
-// with 128 columns, B unbounded stride-3 windows of 5 positions over unit == 32), BOTH fp32 operands marked split = 8
-// and scaled by one running scale per operand and block inside gemm_h3wsn_kernel: no images, no rscale.
-// f2g_h3wsn_ok: 1 = runs as handed over, 0 = not for this kernel (there is nothing to make first: no 2)
-int f2g_h3wsn_ok(const f2g_gemm_desc& d);
+int f2g_h3wsn_ok(const f2g_gemm_desc& d);      // ... over 32 channels, both fp32 operands marked split = 8 (1 or 0)
 int f2g_launch_h3wsn(const f2g_gemm_desc& d, hipStream_t st);
-// gemm_f16n.hip: precision 4, form 0 over a plain fp32 matrix A marked split = 9 (no image, no rscale) against B's
-// f2g_split_f16x2 image: gemm_h3_kernel with A scaled under one running scale per 128-row tile and split inside
-// gemm_h3n_kernel.  gemm_f16.hip's h3_plain_ok decides (1 with B's image, 2 with B fp32, 0 otherwise)
-int f2g_launch_h3n(const f2g_gemm_desc& d, hipStream_t st);
+int f2g_launch_h3n(const f2g_gemm_desc& d, hipStream_t st);      // form 0, plain fp32 A marked split = 9 (h3_plain_ok)
 
 // ---- lab switches (product builds: both 0) ---------------------------------------------------------------------
 // F2G_LABVAR (tools/micro/build_variants.sh; timing only): ablations of the bf16 lean K loop (gemm_lean.hip) --

@@ -1,16 +1,15 @@
 // fp16x3: fp32-class products from TWO scaled fp16 pieces per operand, three MFMAs per product (gemm.hip has the
 // family, gemm_common.h what the GEMM files share).  f2g_split_f16x2 writes the operand images, gemm_h3_kernel reads them;
 // f2g_split_f16x2_cols writes the images of K-major operands (one scale per column), gemm_h3w_kernel reads those.
-// (gemm_f16p.hip: f2g_split_f16x2_seq and gemm_h3p_kernel, the same over stride-1 windows of a halo map;
-// gemm_f16p3.hip: gemm_h3p3_kernel, the same over stride-3 windows; gemm_f16wt.hip: gemm_h3wt_kernel, the weight
-// gradient of a stride-1 layer over column images; gemm_f16ws.hip: gemm_h3ws_kernel, that of a stride-3 layer;
-// gemm_f16wsn.hip: gemm_h3wsn_kernel, that of the 32-channel stride-3 layer over the fp32 operands themselves;
-// gemm_f16n.hip: gemm_h3n_kernel, gemm_h3_kernel over the fp32 activation matrix itself, scaled per row tile inside
-// the kernel.)  The kernels share
-// gemm_f16_common.h, the image writers split_f16.h; h3_route_of below says which kernel a descriptor belongs to.
+// The other fp16x3 kernels have a file each (gemm_f16*.hip); all share gemm_f16_common.h, the image writers
+// split_f16.h, the ok functions gemm_f16_checks.h.  h3_table below lists every kernel of the family and says which one
+// a descriptor belongs to.
 #include <stddef.h>
 #include <stdint.h>
 
+#include <string>
+
+#include "gemm_f16_checks.h"
 #include "gemm_f16_common.h"
 #include "split_f16.h"
 
@@ -347,7 +346,7 @@ __global__ __launch_bounds__(256, 2) void gemm_h3w_kernel(const f2g_gemm_desc d,
 inline bool h3_operand_ok(const f2g_operand& S) {
   return host_plain(S) && !S.alpha && S.rows > 0 && S.cols >= BK && S.cols % BK == 0 && S.cols <= F2G_F16_MAX_K &&
          al16(S.base) && (S.seq_stride & 3) == 0 && S.seq_stride >= S.cols &&
-         (long long)S.rows * S.seq_stride * 4 < 0x7ff00000ll;
+         h3_fits31((long long)S.rows * S.seq_stride);
 }
 
 // form 2 (weight gradient): what gemm_leanw6_kernel<false> takes for two plain operands, with partial tiles (any
@@ -356,24 +355,11 @@ inline bool h3w_operand_ok(const f2g_operand& S) {
   return host_plain(S) && !S.alpha && S.rows > 0 && S.cols >= 4 && S.cols % 4 == 0 && al16(S.base) &&
          (S.seq_stride & 3) == 0 && S.seq_stride >= S.cols &&
          // (the kernel's 32-bit byte offsets reach one slab of 32 rows past the last row: they must not wrap)
-         ((long long)S.rows + 32) * S.seq_stride * 4 < 0x7ff00000ll;
+         h3_fits31(((long long)S.rows + 32) * S.seq_stride);
 }
 
-// The ONE route decision of precision 4: the kernel a descriptor belongs to -- gemm_h3_kernel, gemm_h3w_kernel,
-// gemm_h3p_kernel (gemm_f16p.hip), gemm_h3p3_kernel (gemm_f16p3.hip), gemm_h3p3n_kernel (gemm_f16p3n.hip), gemm_h3pn_kernel (gemm_f16pn.hip),
-// gemm_h3wt_kernel (gemm_f16wt.hip),
-// gemm_h3ws_kernel (gemm_f16ws.hip), gemm_h3wsn_kernel (gemm_f16wsn.hip) --, what f2g_gemm_f16_ok answers for it (0: not for
-// that kernel; 1: runs as handed over, both operands the kernel's images with their reciprocal scales; 2: once both
-// fp32 operands are replaced by those images) and the taps of H3_TAP.  The shape of the operands picks the candidate,
-// the candidate's own conditions decide: a descriptor one kernel declines is never offered to another.
-enum h3_kernel { H3_NONE, H3_PLAIN, H3_PLAINN, H3_WGRAD, H3_TAP, H3_TAP3, H3_TAP3N, H3_TAPN, H3_TAPW, H3_TAPW3, H3_TAPW3N };
-struct h3_route {
-  h3_kernel kernel = H3_NONE;
-  int status = 0, taps = 0;
-};
-
-// A marked split = 9 (gemm_h3n_kernel, gemm_f16n.hip: the fp32 matrix itself, scaled per row tile inside the kernel):
-// the same conditions, A without rscale, and the answer follows B alone -- 1 with its image and rscale, 2 while fp32
+// gemm_h3_kernel, and gemm_h3n_kernel (gemm_f16n.hip) where A is marked split = 9 -- the fp32 matrix itself, scaled
+// per row tile inside the kernel: the same conditions, A without rscale, and the answer follows B alone
 int h3_plain_ok(const f2g_gemm_desc& d) {
   if (d.A.cols != d.B.cols || !h3_operand_ok(d.A) || !h3_operand_ok(d.B)) return 0;
   if (d.A.split == 9 && d.A.rscale) return 0;
@@ -383,8 +369,7 @@ int h3_plain_ok(const f2g_gemm_desc& d) {
   if (E.prelu_slope && (E.atomic || E.accumulate || E.P0o > 0)) return 0;
   if (E.mask_src && (E.atomic || E.accumulate)) return 0;
   if (E.aux && !E.alpha_n) return 0;
-  if (d.A.split == 9) return d.B.split == 5 ? (d.B.rscale ? 1 : 0) : (d.B.split == 0 ? 2 : 0);
-  return f16_images_status(d.A, d.B, 5);
+  return d.A.split == 9 ? f16_b_image_status(d.B, 5) : f16_images_status(d.A, d.B, 5);
 }
 
 int h3w_ok(const f2g_gemm_desc& d) {
@@ -396,35 +381,102 @@ int h3w_ok(const f2g_gemm_desc& d) {
   return f16_images_status(d.A, d.B, 6);
 }
 
+int f2g_launch_h3(const f2g_gemm_desc& d, hipStream_t st) {
+  const int M = d.A.rows, N = d.B.rows, K = d.A.cols;
+  constexpr int smem = 4 * 128 * LDR * 4;
+  dyn_lds_once<gemm_h3_kernel>(smem);
+  f2g_note_kernel("h3<ep=all>", 1, 6);
+  hipLaunchKernelGGL(gemm_h3_kernel, dim3((M + 127) / 128, (N + 127) / 128), dim3(256), smem, st, d, M, N, K);
+  return f2g_check_launch();
+}
+
+int f2g_launch_h3w(const f2g_gemm_desc& d, hipStream_t st) {
+  const int M = d.A.cols, N = d.B.cols, K = d.A.rows, split = d.split_k > 1 ? d.split_k : 1;
+  const int kchunk = ((K + split - 1) / split + BK - 1) / BK * BK;
+  constexpr int smem = 2 * 4 * 32 * 256;      // [buf][A hi | A lo | B hi | B lo] planes of 32 rows x 128 halves
+  dyn_lds_once<gemm_h3w_kernel>(smem);
+  f2g_note_kernel("h3w", split, 6);
+  hipLaunchKernelGGL(gemm_h3w_kernel, dim3((M + 127) / 128, (N + 127) / 128, (K + kchunk - 1) / kchunk),
+                     dim3(256), smem, st, d, M, N, K, kchunk);
+  return f2g_check_launch();
+}
+
+// ---- the ONE route decision of precision 4 -------------------------------------------------------------------------
+// The fp16x3 kernels, one entry each.  h3_route_of walks the table in order: the FIRST entry whose `claims` holds -- a
+// test of the descriptor's form, marks and operand shapes alone -- is the descriptor's candidate, and that kernel's own
+// conditions (`ok`) decide.  Nothing else is asked: a descriptor one kernel declines is never offered to another.  So
+// the order is part of the rule -- the marked operands (split = 8 / 9: fp32, scaled inside the kernel) in front of the
+// shapes, a windows' stride 3 in front of "any stride", the plain kernels of each form last.
+// `ok` answers f2g_gemm_f16_ok: 0 = not for this kernel, 1 = runs as handed over (the operands the kernel's images
+// with their reciprocal scales, or marked fp32), 2 = once the fp32 operands are replaced by those images.
+// `part_tile`: the tile height the kernel's wide epilogue counts partial column sums in, one row per 64 output rows of
+// whole tiles (f2g_gemm_colsum_part_rows); 0 = no wide epilogue.  `what`: the descriptors it takes, for F2G_EINVAL.
+struct h3_entry {
+  bool (*claims)(const f2g_gemm_desc& d);
+  int (*ok)(const f2g_gemm_desc& d);
+  int (*launch)(const f2g_gemm_desc& d, hipStream_t st);
+  int part_tile;
+  const char* what;
+};
+
+inline bool h3_form2_p4(const f2g_gemm_desc& d) { return d.form == 2 && d.precision == 4; }
+inline bool h3_tapw_shape(const f2g_gemm_desc& d) { return h3_form2_p4(d) && host_plain(d.A) && !host_plain(d.B); }
+
+const h3_entry h3_table[] = {
+    // H3_TAPW3N, gemm_h3wsn_kernel (gemm_f16wsn.hip)
+    {[](const f2g_gemm_desc& d) { return h3_form2_p4(d) && (d.A.split == 8 || d.B.split == 8); }, f2g_h3wsn_ok,
+     f2g_launch_h3wsn, 0,
+     "form 2 + atomic over a plain fp32 matrix of 128 columns and the fp32 map under unbounded stride-3 windows of 5 "
+     "positions over 32 channels, both marked split = 8 without rscale"},
+    // H3_TAPW3, gemm_h3ws_kernel (gemm_f16ws.hip)
+    {[](const f2g_gemm_desc& d) { return h3_tapw_shape(d) && d.B.step0 == 3; }, f2g_h3ws_ok, f2g_launch_h3ws, 0,
+     "form 2 + atomic over f2g_split_f16x2_cols images of a plain matrix and of the map under unbounded stride-3 "
+     "windows of 5 positions that overhang a sequence of seq_stride / unit map rows by at most pad0 rows"},
+    // H3_TAPW, gemm_h3wt_kernel (gemm_f16wt.hip)
+    {h3_tapw_shape, f2g_h3wt_ok, f2g_launch_h3wt, 0,
+     "form 2 + atomic over such images under unbounded stride-1 windows of 5 positions"},
+    // H3_WGRAD, gemm_h3w_kernel
+    {[](const f2g_gemm_desc& d) { return d.form == 2; }, h3w_ok, f2g_launch_h3w, 0,
+     "form 2 over f2g_split_f16x2_cols images of two plain matrices"},
+    // H3_PLAINN, gemm_h3n_kernel (gemm_f16n.hip); h3_plain_ok declines a window operand so marked
+    {[](const f2g_gemm_desc& d) { return d.form == 0 && d.A.split == 9; }, h3_plain_ok, f2g_launch_h3n, 0,
+     "form 0 over the plain fp32 matrix A itself (A.split = 9 without rscale) against B's f2g_split_f16x2 image"},
+    // H3_TAP3N, gemm_h3p3n_kernel (gemm_f16p3n.hip)
+    {[](const f2g_gemm_desc& d) { return d.form == 0 && d.A.split == 8 && d.A.step0 == 3; }, f2g_h3p3n_ok,
+     f2g_launch_h3p3n, 128,
+     "form 0 over the fp32 map (A.split = 8) under stride-3 windows of 5 positions over 32 channels against a "
+     "f2g_split_f16x2_seq image"},
+    // H3_TAPN, gemm_h3pn_kernel (gemm_f16pn.hip): the thin epilogue
+    {[](const f2g_gemm_desc& d) { return d.form == 0 && d.A.split == 8; }, f2g_h3pn_ok, f2g_launch_h3pn, 0,
+     "form 0 over the fp32 map (A.split = 8) under stride-1 windows of 2 or 1 positions over 128 channels onto at "
+     "most 32 columns against a f2g_split_f16x2_seq image"},
+    // H3_TAP3, gemm_h3p3_kernel (gemm_f16p3.hip)
+    {[](const f2g_gemm_desc& d) { return d.form == 0 && !host_plain(d.A) && d.A.step0 == 3; }, f2g_h3p3_ok,
+     f2g_launch_h3p3, 256,
+     "form 0 over f2g_split_f16x2_seq images of stride-3 windows of 5 positions over a multiple of 128 channels"},
+    // H3_TAP, gemm_h3p_kernel (gemm_f16p.hip): windows of a halo map, or f2g_split_f16x2_seq images
+    {[](const f2g_gemm_desc& d) { return d.form == 0 && (!host_plain(d.A) || d.A.split == 7 || d.B.split == 7); },
+     f2g_h3p_ok, f2g_launch_h3p, 256,
+     "form 0 over f2g_split_f16x2_seq images of stride-1 windows of 5 or 2 positions"},
+    // H3_PLAIN, gemm_h3_kernel
+    {[](const f2g_gemm_desc& d) { return d.form == 0; }, h3_plain_ok, f2g_launch_h3, 0,
+     "form 0 over f2g_split_f16x2 images of two plain matrices"},
+};
+
+struct h3_route {
+  const h3_entry* entry = nullptr;      // set where status != 0
+  int status = 0;
+};
+
 h3_route h3_route_of(const f2g_gemm_desc& d) {
   h3_route r;
-  h3_kernel cand = H3_NONE;
   if (!d.A.base || !d.B.base || !d.E.C) return r;
-  if (d.form == 2) {
-    // B a window operand: a tap-walking weight gradient (the windows' stride says which: 3 gemm_h3ws_kernel, anything
-    // else gemm_h3wt_kernel) or nothing
-    // an operand marked split = 8 (the fp32 operands themselves, scaled inside the kernel): gemm_h3wsn_kernel
-    // (gemm_f16wsn.hip) or nothing
-    if (d.precision == 4 && (d.A.split == 8 || d.B.split == 8)) cand = H3_TAPW3N;
-    else cand = d.precision == 4 && host_plain(d.A) && !host_plain(d.B) ? (d.B.step0 == 3 ? H3_TAPW3 : H3_TAPW) : H3_WGRAD;
-    if (cand == H3_TAPW3N) r.status = f2g_h3wsn_ok(d);
-    else r.status = cand == H3_TAPW3 ? f2g_h3ws_ok(d) : (cand == H3_TAPW ? f2g_h3wt_ok(d) : h3w_ok(d));
-  } else if (d.form == 0) {
-    // windows of a halo map, or f2g_split_f16x2_seq images: a tap-walking kernel (the windows' stride says which:
-    // 3 gemm_h3p3_kernel, anything else gemm_h3p_kernel) or nothing
-    // A marked split = 8 (the fp32 map, scaled inside the kernel): the windows' stride says which -- 3
-    // gemm_h3p3n_kernel (gemm_f16p3n.hip), anything else gemm_h3pn_kernel (gemm_f16pn.hip) -- or nothing
-    // A marked split = 9 (the fp32 matrix, scaled per row tile inside the kernel): gemm_h3n_kernel (gemm_f16n.hip) or
-    // nothing -- h3_plain_ok declines a window operand so marked
-    const bool win = !host_plain(d.A);
-    cand = d.A.split == 9 ? H3_PLAINN : d.A.split == 8 ? (d.A.step0 == 3 ? H3_TAP3N : H3_TAPN)
-                          : (win && d.A.step0 == 3 ? H3_TAP3 : (win || d.A.split == 7 || d.B.split == 7 ? H3_TAP : H3_PLAIN));
-    if (cand == H3_TAP3N) r.status = f2g_h3p3n_ok(d), r.taps = 5;
-    else if (cand == H3_TAPN) r.status = f2g_h3pn_ok(d, &r.taps);
-    else if (cand == H3_TAP3) r.status = f2g_h3p3_ok(d), r.taps = 5;
-    else r.status = cand == H3_TAP ? f2g_h3p_ok(d, &r.taps) : h3_plain_ok(d);      // (H3_PLAIN, H3_PLAINN)
-  }
-  if (r.status) r.kernel = cand;
+  for (const h3_entry& e : h3_table)
+    if (e.claims(d)) {
+      r.status = e.ok(d);
+      if (r.status) r.entry = &e;
+      break;
+    }
   return r;
 }
 
@@ -432,46 +484,18 @@ h3_route h3_route_of(const f2g_gemm_desc& d) {
 
 extern "C" int f2g_gemm_f16_ok(const f2g_gemm_desc* dp) { return dp ? h3_route_of(*dp).status : 0; }
 
+int f2g_gemm_h3_part_tile(const f2g_gemm_desc& d) {
+  const h3_route r = h3_route_of(d);
+  return r.entry ? r.entry->part_tile : 0;
+}
+
 int f2g_gemm_h3(const f2g_gemm_desc& d, hipStream_t st) {
   const h3_route r = h3_route_of(d);
-  if (r.status != 1) {
-    f2g_set_error("f2g_gemm precision 4: form 0 over f2g_split_f16x2 images, or form 0 over the plain fp32 matrix A "
-                  "itself (A.split = 9 without rscale) against B's f2g_split_f16x2 image, or form 2 over f2g_split_f16x2_cols "
-                  "images, of two plain matrices, or form 0 over f2g_split_f16x2_seq images of stride-1 windows of 5 or "
-                  "2 positions or of stride-3 windows of 5 positions over a multiple of 128 channels, or form 0 over the fp32 map (A.split = 8) under stride-3 windows of 5 positions over 32 channels or stride-1 windows of 2 or 1 positions over 128 channels onto at most 32 columns against a f2g_split_f16x2_seq image, or form 2 + atomic over f2g_split_f16x2_cols images of a plain matrix and of the map "
-                  "under unbounded stride-1 windows of 5 positions, or of stride-3 windows of 5 positions that overhang a "
-                  "sequence of seq_stride / unit map rows by at most pad0 rows, or form 2 + atomic over a plain fp32 matrix "
-                  "of 128 columns and the fp32 map under such stride-3 windows over 32 channels, both marked split = 8 "
-                  "without rscale (f2g_gemm_f16_ok(d) != 1 for this descriptor)");
-    return F2G_EINVAL;
-  }
-  switch (r.kernel) {
-    case H3_TAP: return f2g_launch_h3p(d, r.taps, st);
-    case H3_TAP3: return f2g_launch_h3p3(d, st);
-    case H3_TAP3N: return f2g_launch_h3p3n(d, st);
-    case H3_TAPN: return f2g_launch_h3pn(d, r.taps, st);
-    case H3_TAPW: return f2g_launch_h3wt(d, st);
-    case H3_TAPW3: return f2g_launch_h3ws(d, st);
-    case H3_TAPW3N: return f2g_launch_h3wsn(d, st);
-    case H3_PLAINN: return f2g_launch_h3n(d, st);
-    case H3_WGRAD: {
-      const int M = d.A.cols, N = d.B.cols, K = d.A.rows, split = d.split_k > 1 ? d.split_k : 1;
-      const int kchunk = ((K + split - 1) / split + BK - 1) / BK * BK;
-      constexpr int smem = 2 * 4 * 32 * 256;      // [buf][A hi | A lo | B hi | B lo] planes of 32 rows x 128 halves
-      dyn_lds_once<gemm_h3w_kernel>(smem);
-      f2g_note_kernel("h3w", split, 6);
-      hipLaunchKernelGGL(gemm_h3w_kernel, dim3((M + 127) / 128, (N + 127) / 128, (K + kchunk - 1) / kchunk),
-                         dim3(256), smem, st, d, M, N, K, kchunk);
-      return f2g_check_launch();
-    }
-    default: break;      // H3_PLAIN (H3_NONE has status 0)
-  }
-  const int M = d.A.rows, N = d.B.rows, K = d.A.cols;
-  constexpr int smem = 4 * 128 * LDR * 4;
-  dyn_lds_once<gemm_h3_kernel>(smem);
-  f2g_note_kernel("h3<ep=all>", 1, 6);
-  hipLaunchKernelGGL(gemm_h3_kernel, dim3((M + 127) / 128, (N + 127) / 128), dim3(256), smem, st, d, M, N, K);
-  return f2g_check_launch();
+  if (r.status == 1) return r.entry->launch(d, st);
+  std::string msg = "f2g_gemm precision 4: f2g_gemm_f16_ok(d) != 1 for this descriptor.  The kernels take";
+  for (const h3_entry& e : h3_table) msg += std::string(&e == h3_table ? " " : "; or ") + e.what;
+  f2g_set_error(msg.c_str());
+  return F2G_EINVAL;
 }
 
 extern "C" int f2g_split_f16x2_cols(float* dst, float* rscale, uint32_t* work, const float* src, int64_t ld,

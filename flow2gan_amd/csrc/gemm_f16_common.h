@@ -1,7 +1,6 @@
-// The GEMM side of fp16x3 (split_f16.h has the image side), shared by gemm_h3_kernel and gemm_h3w_kernel
-// (gemm_f16.hip), gemm_h3p_kernel (gemm_f16p.hip), gemm_h3wt_kernel (gemm_f16wt.hip) and gemm_h3ws_kernel
-// (gemm_f16ws.hip), gemm_h3wsn_kernel (gemm_f16wsn.hip), gemm_h3n_kernel (gemm_f16n.hip): the fragment type, the
-// K-major fragment read, the three MFMAs of a product tile, zeroing and rescaling the two accumulator sets.  What a
+// The GEMM side of fp16x3 (split_f16.h has the image side), shared by the kernels of gemm_f16*.hip (gemm_f16.hip:
+// h3_table lists them): the fragment type, the K-major fragment read, the three MFMAs of a product tile, zeroing and
+// rescaling the two accumulator sets.  What a
 // kernel stages and where its fragments and scales lie stay with the kernel.  Internal linkage throughout.
 #pragma once
 #include "gemm_common.h"

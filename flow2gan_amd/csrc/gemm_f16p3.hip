@@ -26,6 +26,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gemm_f16_checks.h"
 #include "gemm_f16_common.h"
 #include "x6_epilogue.h"
 
@@ -211,25 +212,10 @@ __global__ __launch_bounds__(512, 1) void gemm_h3p3_kernel(const f2g_gemm_desc d
 
 }  // namespace
 
+// stride-3 windows of 5 positions over a multiple of 128 channels (x6_tap3_ok), on 256 x 128 tiles
 int f2g_h3p3_ok(const f2g_gemm_desc& d) {
-  const f2g_operand& A = d.A;
-  const f2g_operand& B = d.B;
-  const f2g_epilogue& E = d.E;
-  if (d.precision != 4 || d.form != 0 || !A.base || !B.base || !E.C || !host_plain(B) || A.cols != B.cols) return 0;
-  if (!x6_tap3_ok(d, LP)) return 0;
-  const int mode = f2g_opt(F2G_OPT_X6P);    // (gemm_x6p_kernel's switch: 0 off, 1 chip-filling grids, 2 whatever the grid)
-  const long long M = A.rows, N = B.rows, ext = x6_a_extent(A);
-  if (mode == 0 || M < 1 || N < 1 || ext <= 0 || A.L0u > A.seq_stride) return 0;     // (a window stays in its run)
-  if (mode < 2 && ((M + 255) / 256) * ((N + 127) / 128) < 256) return 0;
-  // the images have the fp32 buffers' own addressing: 32-bit byte offsets, whole slabs, 16-byte loads
-  if (ext * 4 >= 0xe0000000ll || N * B.seq_stride * 4 >= 0xe0000000ll) return 0;
-  if (!al16(A.base) || !al16(B.base) || (B.seq_stride % 32) || B.seq_stride < B.cols) return 0;
-  if (A.alpha || A.lrelu_src || B.alpha || B.lrelu_src) return 0;                     // (no on-load transforms)
-  if (d.split_k > 1 || !x6e::wide_ok(E, B.rows) || (E.x3_out && E.prelu_out)) return 0;
-  // (the combinations f2g_gemm refuses for every kernel)
-  if (E.prelu_slope && (E.accumulate || E.P0o > 0)) return 0;
-  if (E.mask_src && E.accumulate) return 0;
-  return f16_images_status(A, B, 7);
+  if (!h3_tap_fwd_ok(d, 256, 128, true) || !x6_tap3_ok(d, LP)) return 0;
+  return f16_images_status(d.A, d.B, 7);
 }
 
 int f2g_launch_h3p3(const f2g_gemm_desc& d, hipStream_t st) {

@@ -38,6 +38,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gemm_f16_checks.h"
 #include "gemm_f16_common.h"
 #include "split_f16.h"
 #include "x6_epilogue.h"
@@ -223,28 +224,14 @@ __global__ __launch_bounds__(NTHR, 1) void gemm_h3p3n_kernel(const f2g_gemm_desc
 
 }  // namespace
 
+// A the fp32 map marked split = 8 under stride-3 windows of 5 positions over 32 channels, at most 128 columns, row
+// tiles of 128
 int f2g_h3p3n_ok(const f2g_gemm_desc& d) {
   const f2g_operand& A = d.A;
-  const f2g_operand& B = d.B;
-  const f2g_epilogue& E = d.E;
-  if (d.precision != 4 || d.form != 0 || A.split != 8 || !A.base || !B.base || !E.C) return 0;
-  if (!host_plain(B) || A.cols != B.cols) return 0;
+  if (A.split != 8 || d.B.rows > 128 || !h3_tap_fwd_ok(d, 128, 0, true)) return 0;
   if (host_plain(A) || A.P1 != 1 || A.step0 != 3 || A.unit != 32 || A.cols != 5 * A.unit || A.seglen < A.cols) return 0;
-  if ((A.seq_stride % A.unit) || A.pad0 > 0 || A.P0 < 8 || A.L0u > A.seq_stride) return 0;   // (P0: NSEG segments)
-  const int mode = f2g_opt(F2G_OPT_X6P);    // (gemm_x6p_kernel's switch: 0 off, 1 chip-filling grids, 2 whatever the grid)
-  const long long M = A.rows, N = B.rows, ext = x6_a_extent(A);
-  if (mode == 0 || M < 1 || N < 1 || N > 128 || ext <= 0) return 0;
-  if (mode < 2 && (M + 127) / 128 < 256) return 0;
-  // the map and the weight image are read through buffer resources: 32-bit byte offsets, 16-byte loads
-  if (ext * 4 >= 0xe0000000ll || N * B.seq_stride * 4 >= 0xe0000000ll) return 0;
-  if (!al16(A.base) || !al16(B.base) || (B.seq_stride % 32) || B.seq_stride < B.cols) return 0;
-  if (A.alpha || A.lrelu_src || B.alpha || B.lrelu_src) return 0;                     // (no on-load transforms)
-  if (d.split_k > 1 || !x6e::wide_ok(E, B.rows) || (E.x3_out && E.prelu_out)) return 0;
-  // (the combinations f2g_gemm refuses for every kernel)
-  if (E.prelu_slope && (E.accumulate || E.P0o > 0)) return 0;
-  if (E.mask_src && E.accumulate) return 0;
-  if (B.split == 7) return B.rscale ? 1 : 0;
-  return B.split == 0 ? 2 : 0;
+  if ((A.seq_stride % A.unit) || A.pad0 > 0 || A.P0 < 8) return 0;      // (P0: NSEG segments)
+  return f16_b_image_status(d.B, 7);
 }
 
 int f2g_launch_h3p3n(const f2g_gemm_desc& d, hipStream_t st) {

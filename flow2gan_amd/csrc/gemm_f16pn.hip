@@ -49,6 +49,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gemm_f16_checks.h"
 #include "gemm_f16_common.h"
 #include "split_f16.h"
 #include "thin_epilogue.h"
@@ -232,31 +233,17 @@ __global__ __launch_bounds__(NTHR, 2) void gemm_h3pn_kernel(const f2g_gemm_desc 
 
 }  // namespace
 
-int f2g_h3pn_ok(const f2g_gemm_desc& d, int* taps) {
+// A the fp32 map marked split = 8 under stride-1 windows of 2 or 1 positions over 128 channels, at most 32 columns,
+// row tiles of 128, the thin epilogue
+int f2g_h3pn_ok(const f2g_gemm_desc& d) {
   const f2g_operand& A = d.A;
-  const f2g_operand& B = d.B;
-  const f2g_epilogue& E = d.E;
-  if (d.precision != 4 || d.form != 0 || A.split != 8 || !A.base || !B.base || !E.C) return 0;
-  if (!host_plain(B) || A.cols != B.cols) return 0;
+  if (A.split != 8 || d.B.rows > 32 || !h3_tap_fwd_ok(d, 128, 0, false)) return 0;
   if (host_plain(A) || A.P1 != 1 || A.step0 != 1 || A.unit != 128 || A.seglen < A.cols) return 0;
   if (A.cols != A.unit && A.cols != 2 * A.unit) return 0;
-  if ((A.seq_stride % A.unit) || A.pad0 > 0 || A.P0 < 8 || A.L0u > A.seq_stride) return 0;   // (P0: NSEG segments)
-  const int mode = f2g_opt(F2G_OPT_X6P);    // (gemm_x6p_kernel's switch: 0 off, 1 chip-filling grids, 2 whatever the grid)
-  const long long M = A.rows, N = B.rows, ext = x6_a_extent(A);
-  if (mode == 0 || M < 1 || N < 1 || N > 32 || ext <= 0) return 0;
-  if (mode < 2 && (M + 127) / 128 < 256) return 0;
-  // the map and the weight image are read through buffer resources: 32-bit byte offsets, 16-byte loads
-  if (ext * 4 >= 0xe0000000ll || N * B.seq_stride * 4 >= 0xe0000000ll) return 0;
-  if (!al16(A.base) || !al16(B.base) || (B.seq_stride % 32) || B.seq_stride < B.cols) return 0;
-  if (A.alpha || A.lrelu_src || B.alpha || B.lrelu_src) return 0;                     // (no on-load transforms)
-  // the thin epilogue: bias, leaky ReLU, mask + feature-matching term, column sums by atomics, the row map --
-  // everything else is refused here, not run on a slower path
-  if (d.split_k > 1 || E.aux || E.res || E.colsum_alpha || E.prelu_slope || E.prelu_out || E.scale != 0.f) return 0;
-  if (E.atomic || E.accumulate || E.c_bf16 || E.x3_out || E.colsum_part_ld > 0) return 0;
-  if (taps) *taps = A.cols / A.unit;
-  if (B.split == 7) return B.rscale ? 1 : 0;
-  return B.split == 0 ? 2 : 0;
+  if ((A.seq_stride % A.unit) || A.pad0 > 0 || A.P0 < 8) return 0;      // (P0: NSEG segments)
+  return f16_b_image_status(d.B, 7);
 }
+
 
 template <int TAPS>
 static void h3pn_launch(const f2g_gemm_desc& d, hipStream_t st) {
@@ -271,8 +258,8 @@ static void h3pn_launch(const f2g_gemm_desc& d, hipStream_t st) {
   hipLaunchKernelGGL((gemm_h3pn_kernel<TAPS>), dim3(grid), dim3(NTHR), lds::SMEM, st, d, M, N, R);
 }
 
-int f2g_launch_h3pn(const f2g_gemm_desc& d, int taps, hipStream_t st) {
-  if (taps == 2) {
+int f2g_launch_h3pn(const f2g_gemm_desc& d, hipStream_t st) {
+  if (d.A.cols == 2 * d.A.unit) {
     f2g_note_kernel("h3pn<taps=2>", 1, 6);
     h3pn_launch<2>(d, st);
   } else {

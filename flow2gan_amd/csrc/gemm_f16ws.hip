@@ -8,6 +8,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gemm_f16_checks.h"
 #include "gemm_f16_common.h"
 
 namespace {
@@ -164,36 +165,16 @@ __global__ __launch_bounds__(512, 1) void gemm_h3ws_kernel(const f2g_gemm_desc d
 
 }  // namespace
 
-// Form 2 at precision 4 with a WINDOW operand B of stride 3: f2g_h3wt_ok's conditions (gemm_f16wt.hip) with step0 == 3,
-// whole map rows per sequence (seq_stride % unit == 0: a sequence has HpIn = seq_stride / unit map rows, not P0), and
-// windows that overhang a sequence by at most pad0 rows at either end -- 3 (P0 - 1) + 5 - pad0 <= HpIn + pad0, what
-// every layer with Hp = Hout + 4, pad0 = 6, 3 Hout <= Hin + 2 meets; a stride-1 geometry with step0 flipped to 3
-// does not.  1 = runs as handed over, 2 = once both fp32 operands are replaced by their f2g_split_f16x2_cols images
-// (the gradient's, and ONE of the whole map), 0 = not for this kernel.
+// Form 2 at precision 4 with a WINDOW operand B of stride 3: f2g_h3wt_ok's conditions (gemm_f16wt.hip) with step0 == 3
+// and the map rows of h3_tapw3_map_rows (gemm_f16_checks.h).  The images: the gradient's, and ONE of the whole map.
 int f2g_h3ws_ok(const f2g_gemm_desc& d) {
   const f2g_operand& A = d.A;
   const f2g_operand& B = d.B;
-  const f2g_epilogue& E = d.E;
-  if (d.form != 2 || d.precision != 4 || !A.base || !B.base || !E.C) return 0;
-  if (!E.atomic || E.P0o > 0 || E.bias || E.res) return 0;
-  if ((E.scale != 0.f && E.scale != 1.f) || E.colsum || E.colsum_alpha || E.colsum_part_ld > 0 ||
-      E.lrelu_slope != 0.f || E.mask_src || E.aux || E.prelu_slope || E.c_bf16 || E.x3_out || E.accumulate ||
-      A.lrelu_src || A.alpha || B.lrelu_src || B.alpha)
-    return 0;
-  if (!host_plain(A) || A.rows < 1 || A.cols < 128 || (A.cols % 128) || A.rows != B.rows || !al16(A.base) ||
-      (A.seq_stride & 3) || A.seq_stride < A.cols)
-    return 0;
-  if (B.P1 != 1 || B.L1 != 1 || B.P0 < 1 || B.step0 != 3 || B.unit < 128 || (B.unit % 128) || !B.unbounded ||
-      B.reflect || !al16(B.base))
-    return 0;
-  if (B.cols != 5 * B.unit || B.seglen < B.cols || (B.rows % B.P0) || B.pad0 < 0 || B.pad0 > 8) return 0;
-  if (B.seq_stride < B.unit || (B.seq_stride % B.unit)) return 0;
-  const long long HpIn = B.seq_stride / B.unit;
-  if (3ll * (B.P0 - 1) + 5 - B.pad0 > HpIn + B.pad0) return 0;
-  const long long xrows = (long long)(B.rows / B.P0) * HpIn;
-  if (xrows * B.unit * 4 >= 0x7ff00000ll || (long long)A.rows * A.seq_stride * 4 >= 0x7ff00000ll) return 0;
-  return f16_images_status(A, B, 6);
+  if (!h3_tapw_ok(d, 3) || A.cols < 128 || (A.cols % 128) || B.unit < 128 || (B.unit % 128)) return 0;
+  const long long HpIn = h3_tapw3_map_rows(B);
+  return HpIn && h3_tapw_extents_ok(A, B, HpIn) ? f16_images_status(A, B, 6) : 0;
 }
+
 
 int f2g_launch_h3ws(const f2g_gemm_desc& d, hipStream_t st) {
   const int M = d.A.cols, K = d.A.rows, Cin = d.B.unit;

@@ -53,6 +53,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gemm_f16_checks.h"
 #include "gemm_f16_common.h"
 #include "split_f16.h"
 
@@ -263,35 +264,17 @@ int h3wsn_blocks(long long units) {
 }  // namespace
 
 // Form 2 at precision 4 with an operand marked split = 8: BOTH operands are so marked and carry no rscale (there are no
-// images); f2g_h3ws_ok's epilogue (gemm_f16ws.hip: a bare atomic add); A plain with 128 columns; B under unbounded
-// stride-3 windows of five positions over 32 channels, whole map rows per sequence, windows that overhang a sequence by
-// at most pad0 rows at either end, byte extents below 2^31 - 2^20.  1 = runs as handed over, 0 = not for this kernel
-// (there is no 2: nothing has to be made first).
+// images); f2g_h3ws_ok's conditions (gemm_f16ws.hip) with A of 128 columns and B over 32 channels.  1 = runs as handed
+// over, 0 = not for this kernel (there is no 2: nothing has to be made first).
 int f2g_h3wsn_ok(const f2g_gemm_desc& d) {
   const f2g_operand& A = d.A;
   const f2g_operand& B = d.B;
-  const f2g_epilogue& E = d.E;
-  if (d.form != 2 || d.precision != 4 || !A.base || !B.base || !E.C) return 0;
   if (A.split != 8 || B.split != 8 || A.rscale || B.rscale) return 0;
-  if (!E.atomic || E.P0o > 0 || E.bias || E.res) return 0;
-  if ((E.scale != 0.f && E.scale != 1.f) || E.colsum || E.colsum_alpha || E.colsum_part_ld > 0 ||
-      E.lrelu_slope != 0.f || E.mask_src || E.aux || E.prelu_slope || E.c_bf16 || E.x3_out || E.accumulate ||
-      A.lrelu_src || A.alpha || B.lrelu_src || B.alpha)
-    return 0;
-  if (!host_plain(A) || A.rows < 1 || A.cols != 128 || A.rows != B.rows || !al16(A.base) || (A.seq_stride & 3) ||
-      A.seq_stride < A.cols)
-    return 0;
-  if (B.P1 != 1 || B.L1 != 1 || B.P0 < 1 || B.step0 != 3 || B.unit != 32 || !B.unbounded || B.reflect ||
-      !al16(B.base))
-    return 0;
-  if (B.cols != 5 * B.unit || B.seglen < B.cols || (B.rows % B.P0) || B.pad0 < 0 || B.pad0 > 8) return 0;
-  if (B.seq_stride < B.unit || (B.seq_stride % B.unit) || E.ldc < B.cols) return 0;
-  const long long HpIn = B.seq_stride / B.unit;
-  if (3ll * (B.P0 - 1) + 5 - B.pad0 > HpIn + B.pad0) return 0;
-  const long long xrows = (long long)(B.rows / B.P0) * HpIn;
-  if (xrows * B.unit * 4 >= 0x7ff00000ll || (long long)A.rows * A.seq_stride * 4 >= 0x7ff00000ll) return 0;
-  return 1;
+  if (!h3_tapw_ok(d, 3) || A.cols != 128 || B.unit != 32 || d.E.ldc < B.cols) return 0;
+  const long long HpIn = h3_tapw3_map_rows(B);
+  return HpIn && h3_tapw_extents_ok(A, B, HpIn) ? 1 : 0;
 }
+
 
 int f2g_launch_h3wsn(const f2g_gemm_desc& d, hipStream_t st) {
   constexpr int TAPS = 5, STRIDE = 3;

@@ -7,6 +7,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "gemm_f16_checks.h"
 #include "gemm_f16_common.h"
 
 namespace {
@@ -159,31 +160,16 @@ __global__ __launch_bounds__(512, 1) void gemm_h3wt_kernel(const f2g_gemm_desc d
 
 // Form 2 at precision 4 with a WINDOW operand B: f2g_leanw6t_ok's conditions for a stride-1 layer (gemm_x6p.hip) --
 // A a plain matrix of whole 128-column tiles, B unbounded stride-1 windows of 5 positions x unit channels (unit a
-// multiple of 128) over one contiguous map, a bare atomic epilogue, 31-bit byte extents -- over f2g_split_f16x2_cols
-// images of the gradient and of the whole map.  1 = runs as handed over, 2 = once both fp32 operands are replaced by
-// those images, 0 = not for this kernel.
+// multiple of 128) over one contiguous map (h3_tapw_ok, gemm_f16_checks.h) -- over f2g_split_f16x2_cols images of the
+// gradient and of the whole map.
 int f2g_h3wt_ok(const f2g_gemm_desc& d) {
   const f2g_operand& A = d.A;
   const f2g_operand& B = d.B;
-  const f2g_epilogue& E = d.E;
-  if (d.form != 2 || d.precision != 4 || !A.base || !B.base || !E.C) return 0;
-  if (!E.atomic || E.P0o > 0 || E.bias || E.res) return 0;
-  if ((E.scale != 0.f && E.scale != 1.f) || E.colsum || E.colsum_alpha || E.colsum_part_ld > 0 ||
-      E.lrelu_slope != 0.f || E.mask_src || E.aux || E.prelu_slope || E.c_bf16 || E.x3_out || E.accumulate ||
-      A.lrelu_src || A.alpha || B.lrelu_src || B.alpha)
-    return 0;
-  if (!host_plain(A) || A.rows < 1 || A.cols < 128 || (A.cols % 128) || A.rows != B.rows || !al16(A.base) ||
-      (A.seq_stride & 3) || A.seq_stride < A.cols)
-    return 0;
-  if (B.P1 != 1 || B.L1 != 1 || B.P0 < 1 || B.step0 != 1 || B.unit < 128 || (B.unit % 128) || !B.unbounded ||
-      B.reflect || !al16(B.base))
-    return 0;
-  if (B.cols != 5 * B.unit || B.seglen < B.cols || (B.rows % B.P0) || B.pad0 < 0 || B.pad0 > 8) return 0;
+  if (!h3_tapw_ok(d, 1) || A.cols < 128 || (A.cols % 128) || B.unit < 128 || (B.unit % 128)) return 0;
   if (B.seq_stride != (long long)B.P0 * B.unit) return 0;     // (one flat row index for the whole buffer)
-  const long long xrows = (long long)(B.rows / B.P0) * B.P0;
-  if (xrows * B.unit * 4 >= 0x7ff00000ll || (long long)A.rows * A.seq_stride * 4 >= 0x7ff00000ll) return 0;
-  return f16_images_status(A, B, 6);
+  return h3_tapw_extents_ok(A, B, B.P0) ? f16_images_status(A, B, 6) : 0;
 }
+
 
 int f2g_launch_h3wt(const f2g_gemm_desc& d, hipStream_t st) {
   const int M = d.A.cols, K = d.A.rows, Cin = d.B.unit;

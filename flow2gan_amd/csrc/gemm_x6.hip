@@ -828,18 +828,16 @@ extern "C" int f2g_gemm_x6_ok(const f2g_gemm_desc* d) {
 }
 
 // Rows of the partial column-sum matrices (E.colsum_part_ld > 0) the launch of `d` writes: one per 64 output
-// rows of whole tiles -- or 0 when the kernel x6_choose picks has no wide epilogue.
+// rows of whole tiles -- or 0 when the kernel that takes it (x6_choose; at precision 4 the fp16x3 route) has no wide
+// epilogue.
 extern "C" int32_t f2g_gemm_colsum_part_rows(const f2g_gemm_desc* dp) {
   if (!dp || (dp->precision != 3 && dp->precision != 4) || dp->form != 0) return 0;
   f2g_gemm_desc d = *dp;
   if (d.E.colsum_part_ld <= 0) d.E.colsum_part_ld = 4;          // (alignment of the pointers is the caller's)
-  // precision 4: the tap-walking kernels alone have the wide epilogue (gemm_f16p.hip, gemm_f16p3.hip; 256-row tiles)
-  // (gemm_f16p3n.hip: 128-row tiles; gemm_f16pn.hip, the other user of split = 8, has the thin epilogue: no partial
-  // rows -- f2g_h3p3n_ok declines its stride-1 windows)
-  // (gemm_f16n.hip: A marked split = 9, gemm_h3_kernel's generic epilogue -- no partial rows)
-  if (d.precision == 4 && d.A.split == 9) return 0;
-  if (d.precision == 4 && d.A.split == 8) return f2g_h3p3n_ok(d) ? 2 * ((d.A.rows + 127) / 128) : 0;
-  if (d.precision == 4) return f2g_h3p_ok(d, nullptr) || f2g_h3p3_ok(d) ? 4 * ((d.A.rows + 255) / 256) : 0;
+  if (d.precision == 4) {      // the fp16x3 kernel the descriptor belongs to says how tall its tiles are (gemm_f16.hip)
+    const int tile = f2g_gemm_h3_part_tile(d);
+    return tile ? tile / 64 * ((d.A.rows + tile - 1) / tile) : 0;
+  }
   if (!x6_wide(d)) return 0;
   const int M = d.A.rows;
   switch (x6_choose(d).kind) {

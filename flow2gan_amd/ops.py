@@ -6,7 +6,7 @@ Tensors are channels-last "rows" matrices: a 2-D contiguous fp32 tensor (rows, l
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+from typing import Callable, NamedTuple, Optional
 
 import torch
 
@@ -1015,141 +1015,144 @@ def _f16_cols_window_operand(o: Operand) -> Operand:
     return _image_operand(o, buf, xrows * Cin, 6)
 
 
+class _F16Route(NamedTuple):
+    """One fp16x3 route of gemm().  `threshold` and `counter` NAME module attributes (the FP16X3_* tunables and launch
+    counters further down, where each route's shapes and measurements are written up: tests, tools and F2G_OPTS set and
+    read them directly, so they are looked up per call)."""
+    threshold: str          # the route is open from this many ...
+    by_width: int           # ... 1: output columns (Bm.rows), 0: rows of A
+    counter: str
+    claims: Callable        # (A, Bm, atomic, split_k, x3_out) -> bool: what the Python side requires of the call
+    images: tuple           # per operand: the builder of the fp16 image the kernel reads, None = the fp32 operand
+    marks: tuple = (0, 0)   # Operand.split of d.A / d.B while the library is asked: 8 / 9 = scaled inside the kernel
+    needs: int = 2          # f2g_gemm_f16_ok's answer: 2 = runs once the images are made, 1 = as it is (no image)
+    x3_out: bool = False    # wide epilogue: asked through _ask_with_x3_out, the output's three-piece image is written
+
+
+# The routes by (form, shape of the operand that may lie under windows) -- form 0: forward, and data gradients over a
+# cached transpose, the operand is A; form 2: weight gradients, it is Bm; shape 0: a plain matrix, 1 / 3: win1d windows
+# of that stride (_fp16x3_route has the test) -- in the order they are tried: the first whose threshold, predicate and
+# library answer agree takes the launch.  Routes under different keys never compete.  Under one key the order is
+# behaviour: the route that reads the fp32 operand itself (no image pass, nothing allocated per call) stands in front of
+# the image route over the same shapes -- PLAINN before PLAIN, TAPN before TAP (two-tap windows over 128 channels),
+# TAP3N before TAP3, TAPW3N before TAPW3 -- and what its kernel declines falls through to the image route with the marks
+# cleared.
+_FP16X3_ROUTES = {(0, 0): (
+    # PLAINN, gemm_h3n_kernel: the fp32 activation matrix itself, marked split = 9; the weight's cached image
+    _F16Route("FP16X3_PLAINN_MIN_N", 1, "FP16X3_PLAINN_LAUNCHES",
+              lambda A, Bm, atomic, split_k, x3_out: A.cols >= FP16X3_MIN_K and split_k <= 1,
+              (None, _f16_operand), marks=(9, 0)),
+    # PLAIN, gemm_h3_kernel: two plain matrices (a data gradient arrives as form 0 over the cached transpose) as
+    # f2g_split_f16x2 images -- the weight's from the derived-weight cache, the activation's made per call
+    _F16Route("FP16X3_MIN_N", 1, "FP16X3_LAUNCHES",
+              lambda A, Bm, atomic, split_k, x3_out: A.cols >= FP16X3_MIN_K and split_k <= 1,
+              (_f16_operand, _f16_operand)),
+), (0, 1): (
+    # TAPN, gemm_h3pn_kernel: 2 or 1 positions of the fp32 128-channel map itself, marked split = 8, onto <= 32 columns;
+    # the weight's cached f2g_split_f16x2_seq image.  Thin epilogue: no three-piece image of the output
+    _F16Route("FP16X3_TAPN_MIN_ROWS", 0, "FP16X3_TAPN_LAUNCHES",
+              lambda A, Bm, atomic, split_k, x3_out:
+              not atomic and split_k <= 1 and A.unit == 128 and A.cols in (128, 256) and Bm.rows <= 32 and not x3_out
+              and _f16_seq_window_ok(A),
+              (None, _f16_seq_operand), marks=(8, 0)),
+    # TAP, gemm_h3p_kernel: 5 or 2 positions over f2g_split_f16x2_seq images, one scale per sequence -- the map's made
+    # per call, the weight's cached.  Reductions from X6_MIN_K on: the launches the bf16x6 mode gives to its image
+    # kernels.  The bf16x6 kernels' wide epilogue: the output's three-piece image is written as there
+    _F16Route("FP16X3_TAP_MIN_ROWS", 0, "FP16X3_TAP_LAUNCHES",
+              lambda A, Bm, atomic, split_k, x3_out:
+              not atomic and split_k <= 1 and A.cols in (5 * A.unit, 2 * A.unit) and A.cols >= X6_MIN_K
+              and _f16_seq_window_ok(A),
+              (_f16_seq_operand, _f16_seq_operand), x3_out=True),
+), (0, 3): (
+    # TAP3N, gemm_h3p3n_kernel: 5 positions of the fp32 32-channel map itself (K = 160), marked split = 8; wide epilogue
+    _F16Route("FP16X3_TAP3N_MIN_ROWS", 0, "FP16X3_TAP3N_LAUNCHES",
+              lambda A, Bm, atomic, split_k, x3_out:
+              not atomic and split_k <= 1 and A.unit == 32 and A.cols == 160 and _f16_seq_window_ok(A),
+              (None, _f16_seq_operand), marks=(8, 0), x3_out=True),
+    # TAP3, gemm_h3p3_kernel: 5 positions over a multiple of 128 channels: TAP's images, scales and epilogue
+    _F16Route("FP16X3_TAP3_MIN_ROWS", 0, "FP16X3_TAP3_LAUNCHES",
+              lambda A, Bm, atomic, split_k, x3_out:
+              not atomic and split_k <= 1 and A.cols == 5 * A.unit and A.unit % 128 == 0 and _f16_seq_window_ok(A),
+              (_f16_seq_operand, _f16_seq_operand), x3_out=True),
+), (2, 0): (
+    # WGRAD, gemm_h3w_kernel: two plain K-major activation matrices as f2g_split_f16x2_cols images, made per call
+    _F16Route("FP16X3_WGRAD_MIN_ROWS", 0, "FP16X3_WGRAD_LAUNCHES",
+              lambda A, Bm, atomic, split_k, x3_out: atomic and A.lrelu_src is None,
+              (_f16_cols_operand, _f16_cols_operand)),
+), (2, 3): (
+    # TAPW3N, gemm_h3wsn_kernel: 128 gradient columns against 32 channels, both fp32 operands marked split = 8.  No
+    # images: the library answers 1 or 0 (there is nothing to make first)
+    _F16Route("FP16X3_TAPW3N_MIN_ROWS", 0, "FP16X3_TAPW3N_LAUNCHES",
+              lambda A, Bm, atomic, split_k, x3_out:
+              atomic and A.lrelu_src is None and A.P0 == 1 and A.P1 == 1 and A.cols == 128 and Bm.unbounded
+              and Bm.unit == 32 and Bm.cols == 5 * Bm.unit,
+              (None, None), marks=(8, 8), needs=1),
+    # TAPW3, gemm_h3ws_kernel: a multiple of 128 channels; tap and stride only select rows of the map, so TAPW's two
+    # column images serve as they are
+    _F16Route("FP16X3_TAPW3_MIN_ROWS", 0, "FP16X3_TAPW3_LAUNCHES",
+              lambda A, Bm, atomic, split_k, x3_out:
+              atomic and A.lrelu_src is None and A.P0 == 1 and A.P1 == 1 and Bm.unbounded and Bm.cols == 5 * Bm.unit
+              and Bm.unit % 128 == 0 and _f16_cols_window_ok(Bm),
+              (_f16_cols_operand, _f16_cols_window_operand)),
+), (2, 1): (
+    # TAPW, gemm_h3wt_kernel: the taps shift ROWS of the map, so one scale per COLUMN of the whole map serves every tap:
+    # both f2g_split_f16x2_cols images are made per call (the gradient's into a buffer of its own)
+    _F16Route("FP16X3_TAPW_MIN_ROWS", 0, "FP16X3_TAPW_LAUNCHES",
+              lambda A, Bm, atomic, split_k, x3_out:
+              atomic and A.lrelu_src is None and A.P0 == 1 and A.P1 == 1 and Bm.unbounded and Bm.cols == 5 * Bm.unit
+              and _f16_cols_window_ok(Bm),
+              (_f16_cols_operand, _f16_cols_window_operand)),
+)}
+
+
+def _fp16x3_route(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offset: int, x3_out: bool, prelu_out):
+    """The fp16x3 route that takes the launch, or None (it goes the bf16x6 way).  Host work only: each open route whose
+    predicate holds sets its marks and asks the library about `d` as it will be launched (d.precision = 4;
+    f2g_gemm_f16_ok decides which kernel that is); a decline clears the marks and the next route is tried.  On return
+    d carries the chosen route's marks and E.x3_out; no image is built."""
+    if not (GEMM_PRECISION == 3 and FP16X3) or A.split != 0 or Bm.split != 0 or out.dtype != torch.float32:
+        return None
+    o = A if form == 0 else Bm
+    shape = 0 if o.P0 == 1 and o.P1 == 1 else o.step0 if o.P1 == 1 and o.P0 > 1 else None
+    tunables, sizes = globals(), (A.rows, Bm.rows)
+    for r in _FP16X3_ROUTES.get((form, shape), ()):
+        threshold, by_width, _, claims, _, (mark_a, mark_b), needs, wide = r
+        if sizes[by_width] < tunables[threshold] or not claims(A, Bm, atomic, split_k, x3_out):
+            continue
+        d.precision = 4
+        if mark_a:
+            d.A.split = mark_a
+        if mark_b:
+            d.B.split = mark_b
+        ask = lambda: L.lib.f2g_gemm_f16_ok(C.byref(d)) == needs
+        if _ask_with_x3_out(d, out, out_offset, x3_out, prelu_out, ask) if wide else ask():
+            return r
+        if mark_a or mark_b:
+            d.A.split = d.B.split = 0
+    return None
+
+
 def _fp16x3_gemm(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offset: int, x3_out: bool,
                  prelu_out) -> bool:
-    """The fp16x3 routes of gemm(), tried in order: each states what the Python side requires of the call, then asks
-    the library about `d` as it will be launched (d.precision = 4; f2g_gemm_f16_ok decides which kernel that is).
-    True: one took the launch -- d.A / d.B are its images, its counter went up.  False: the launch goes the bf16x6
-    way (d.precision may be left at 4: gemm() sets it)."""
-    global FP16X3_LAUNCHES, FP16X3_WGRAD_LAUNCHES, FP16X3_TAP_LAUNCHES, FP16X3_TAPW_LAUNCHES, FP16X3_TAP3_LAUNCHES
-    global FP16X3_TAPW3_LAUNCHES, FP16X3_TAP3N_LAUNCHES, FP16X3_TAPN_LAUNCHES, FP16X3_TAPW3N_LAUNCHES
-    global FP16X3_PLAINN_LAUNCHES
-    if not (GEMM_PRECISION == 3 and FP16X3) or A.split != 0 or Bm.split != 0 or out.dtype != torch.float32:
+    """The fp16x3 routes of gemm().  True: one took the launch -- d.A / d.B are its images (or the marked fp32
+    operands), its counter went up.  False: the launch goes the bf16x6 way (d.precision may be left at 4: gemm() sets
+    it)."""
+    r = _fp16x3_route(d, A, Bm, out, form, atomic, split_k, out_offset, x3_out, prelu_out)
+    if r is None:
         return False
-
-    def takes():
-        d.precision = 4
-        return L.lib.f2g_gemm_f16_ok(C.byref(d)) == 2
-    a_plain, b_plain = A.P0 == 1 and A.P1 == 1, Bm.P0 == 1 and Bm.P1 == 1
-    wgrad = form == 2 and atomic and A.lrelu_src is None
-    if form == 0 and a_plain and A.cols >= FP16X3_MIN_K and Bm.rows >= FP16X3_PLAINN_MIN_N and split_k <= 1:
-        # fp16x3 over the fp32 activation matrix ITSELF: NO image of A -- d.A stays the caller's operand, marked
-        # split = 9, and gemm_h3n_kernel scales it under one running scale per 128-row tile and splits it while
-        # staging; nothing is allocated per call.  The weight's f2g_split_f16x2 image comes from the derived-weight
-        # cache.  What the library declines falls through with the mark cleared (the image route below, then bf16x6)
-        d.A.split = 9
-        if takes():
-            d.B = _f16_operand(Bm)
-            FP16X3_PLAINN_LAUNCHES += 1
-            return True
-        d.A.split = 0
-    if form == 0 and a_plain and A.cols >= FP16X3_MIN_K and Bm.rows >= FP16X3_MIN_N and split_k <= 1 and takes():
-        # fp16x3: two plain matrices (a data gradient arrives here as form 0 over the cached transpose) as
-        # f2g_split_f16x2 images -- the weight's from the derived-weight cache, the activation's made here.  The
-        # library is asked first, with the descriptor as it will be launched; what it declines goes the bf16x6 way
-        d.A, d.B = _f16_operand(A), _f16_operand(Bm)
-        FP16X3_LAUNCHES += 1
-        return True
-    if wgrad and b_plain and A.rows >= FP16X3_WGRAD_MIN_ROWS and takes():
-        # fp16x3 weight gradient: both operands are PLAIN activation matrices, K-major -- their f2g_split_f16x2_cols
-        # images (one scale per column) are made here, per call; what the library declines goes the bf16x6 way
-        d.A, d.B = _f16_cols_operand(A), _f16_cols_operand(Bm)
-        FP16X3_WGRAD_LAUNCHES += 1
-        return True
-    if wgrad and a_plain and A.cols == 128 and Bm.P1 == 1 and Bm.P0 > 1 and Bm.step0 == 3 and Bm.unbounded \
-            and Bm.unit == 32 and Bm.cols == 5 * Bm.unit and A.rows >= FP16X3_TAPW3N_MIN_ROWS:
-        # fp16x3 weight gradient of the STRIDE-3 five-tap layer over 32 channels onto 128 (the MPD's 32 -> 128 layer): NO
-        # images -- d.A and d.B stay the caller's fp32 gradient matrix and map, both marked split = 8, and
-        # gemm_h3wsn_kernel scales each under one running scale per block and splits it while staging; nothing is
-        # allocated per call.  The library answers 1 or 0 (there is nothing to make first); what it declines goes the
-        # bf16x6 way
-        d.A.split = d.B.split = 8
-        d.precision = 4
-        if L.lib.f2g_gemm_f16_ok(C.byref(d)) == 1:
-            FP16X3_TAPW3N_LAUNCHES += 1
-            return True
-        d.A.split = d.B.split = 0
-    if wgrad and a_plain and Bm.P1 == 1 and Bm.P0 > 1 and Bm.step0 == 1 and Bm.unbounded \
-            and Bm.cols == 5 * Bm.unit and A.rows >= FP16X3_TAPW_MIN_ROWS and _f16_cols_window_ok(Bm) and takes():
-        # fp16x3 tap-walking weight gradient (the MPD's stride-1 1024-channel layer): the gradient as a plain K-major
-        # matrix, the map under unbounded stride-1 windows of five positions.  The taps shift ROWS of the map, so one
-        # scale per COLUMN of the whole map serves every tap: both f2g_split_f16x2_cols images are made here, per
-        # call (the gradient's into a buffer of its own -- the data gradient reads the fp32 values again); what the
-        # library declines goes the bf16x6 way
-        d.A, d.B = _f16_cols_operand(A), _f16_cols_window_operand(Bm)
-        FP16X3_TAPW_LAUNCHES += 1
-        return True
-    if wgrad and a_plain and Bm.P1 == 1 and Bm.P0 > 1 and Bm.step0 == 3 and Bm.unbounded \
-            and Bm.cols == 5 * Bm.unit and Bm.unit % 128 == 0 and A.rows >= FP16X3_TAPW3_MIN_ROWS \
-            and _f16_cols_window_ok(Bm) and takes():
-        # fp16x3 tap-walking weight gradient of a STRIDE-3 five-tap layer (the MPD's 128 -> 512 and 512 -> 1024
-        # layers): tap and stride only select rows of the map, so the stride-1 route's two column images serve as they
-        # are -- the gradient's, and one of the whole map -- on gemm_h3ws_kernel.  What the library declines goes the
-        # bf16x6 way
-        d.A, d.B = _f16_cols_operand(A), _f16_cols_window_operand(Bm)
-        FP16X3_TAPW3_LAUNCHES += 1
-        return True
-    if form == 0 and A.P1 == 1 and A.P0 > 1 and A.step0 == 1 and A.unit == 128 and A.cols in (128, 256) \
-            and Bm.rows <= 32 and A.rows >= FP16X3_TAPN_MIN_ROWS and not atomic and split_k <= 1 and not x3_out \
-            and _f16_seq_window_ok(A):
-        # fp16x3 over stride-1 windows of 2 or 1 positions of a contiguous 128-channel halo map onto at most 32 columns
-        # (the stride-residue data gradients of the MPD's 32 -> 128 layer): NO image of the map -- d.A stays the
-        # caller's fp32 map, marked split = 8, and gemm_h3pn_kernel scales it per sequence segment and splits it while
-        # staging; nothing is allocated per call.  The weight's f2g_split_f16x2_seq image comes from the
-        # derived-weight cache.  What the library declines goes the bf16x6 way
-        d.A.split = 8
-        if takes():
-            d.B = _f16_seq_operand(Bm)
-            FP16X3_TAPN_LAUNCHES += 1
-            return True
-        d.A.split = 0
-    if form == 0 and A.P1 == 1 and A.P0 > 1 and A.step0 == 1 and A.cols in (5 * A.unit, 2 * A.unit) \
-            and A.rows >= FP16X3_TAP_MIN_ROWS and A.cols >= X6_MIN_K and not atomic and split_k <= 1 \
-            and _f16_seq_window_ok(A):
-        # fp16x3 over stride-1 windows of 5 or 2 positions of a contiguous halo map (the MPD's 1024-channel layer, its
-        # data gradient, the residue data gradients of the stride-3 layers): f2g_split_f16x2_seq images, one scale per
-        # sequence -- the map's made here, per call, the weight's from the derived-weight cache.  Reductions from
-        # X6_MIN_K on: the launches the bf16x6 mode gives to its image kernels (a shorter one reads the fp32 map as
-        # it is there, without any image pass).  The kernel has the bf16x6 kernels' wide epilogue, so the output's
-        # three-piece image is written as there (its consumers stay the bf16x6 kernels).  What the library declines
-        # goes the bf16x6 way
-        if _ask_with_x3_out(d, out, out_offset, x3_out, prelu_out, takes):
-            d.A, d.B = _f16_seq_operand(A), _f16_seq_operand(Bm)
-            FP16X3_TAP_LAUNCHES += 1
-            if x3_out and d.E.x3_out:
-                out._f2g_x3 = out._f2g_x3_buf
-            return True
-        d.E.x3_out = None
-    if form == 0 and A.P1 == 1 and A.P0 > 1 and A.step0 == 3 and A.unit == 32 and A.cols == 160 \
-            and A.rows >= FP16X3_TAP3N_MIN_ROWS and not atomic and split_k <= 1 and _f16_seq_window_ok(A):
-        # fp16x3 over stride-3 windows of 5 positions of a contiguous 32-channel halo map (the MPD's 32 -> 128 forward
-        # layer, K = 160): NO image of the map -- d.A stays the caller's fp32 map, marked split = 8, and
-        # gemm_h3p3n_kernel scales it per sequence segment and splits it while staging; nothing is allocated per
-        # call.  The weight's f2g_split_f16x2_seq image comes from the derived-weight cache.  The output's three-piece
-        # image is written as on the other tap-walking routes (layer 128 -> 512 still reads it).  What the library
-        # declines goes the bf16x6 way
-        d.A.split = 8
-        if _ask_with_x3_out(d, out, out_offset, x3_out, prelu_out, takes):
-            d.B = _f16_seq_operand(Bm)
-            FP16X3_TAP3N_LAUNCHES += 1
-            if x3_out and d.E.x3_out:
-                out._f2g_x3 = out._f2g_x3_buf
-            return True
-        d.A.split = 0
-        d.E.x3_out = None
-    if form == 0 and A.P1 == 1 and A.P0 > 1 and A.step0 == 3 and A.cols == 5 * A.unit and A.unit % 128 == 0 \
-            and A.rows >= FP16X3_TAP3_MIN_ROWS and not atomic and split_k <= 1 and _f16_seq_window_ok(A):
-        # fp16x3 over stride-3 windows of 5 positions of a contiguous halo map with a multiple of 128 channels (the
-        # MPD's 128 -> 512 and 512 -> 1024 forward layers): the stride-1 route's images, scales, epilogue and x3_out
-        # image on gemm_h3p3_kernel.  What the library declines goes the bf16x6 way
-        if _ask_with_x3_out(d, out, out_offset, x3_out, prelu_out, takes):
-            d.A, d.B = _f16_seq_operand(A), _f16_seq_operand(Bm)
-            FP16X3_TAP3_LAUNCHES += 1
-            if x3_out and d.E.x3_out:
-                out._f2g_x3 = out._f2g_x3_buf
-            return True
-        d.E.x3_out = None
-    return False
+    # (both images are built before either temporary operand is dropped: d.A = ... copies the fields, and an image
+    # whose operand is gone may be handed out again by the allocator -- to the other image)
+    image_a, image_b = r.images
+    new_a = image_a(A) if image_a is not None else None
+    new_b = image_b(Bm) if image_b is not None else None
+    if new_a is not None:
+        d.A = new_a
+    if new_b is not None:
+        d.B = new_b
+    globals()[r.counter] += 1
+    if x3_out and r.x3_out and d.E.x3_out:
+        out._f2g_x3 = out._f2g_x3_buf
+    return True
 
 
 CONV32_X6 = opt("conv32_x6", True)    # bf16x6 mode: fp32-class direct MRD convs (bench.py reads it)
