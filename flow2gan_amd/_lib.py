@@ -95,6 +95,14 @@ class DwconvBwd(C.Structure):
     ]
 
 
+class DwblockBwd(C.Structure):  # == f2g_dwblock_bwd_desc
+    _fields_ = [
+        ("n", DwnormBwd), ("gx", C.c_void_p), ("ldgx", C.c_int64), ("gres", C.c_void_p), ("ldgres", C.c_int64),
+        ("gamma", C.c_void_p), ("g_w", C.c_void_p), ("g_b", C.c_void_p), ("g_gamma", C.c_void_p),
+        ("partials", C.c_void_p),
+    ]
+
+
 class Conv32Desc(C.Structure):  # == f2g_conv32_desc
     _fields_ = [("x", C.c_void_p), ("x_seq", C.c_int64), ("x_line", C.c_int64),
                 ("S", C.c_int32), ("H", C.c_int32), ("Win", C.c_int32), ("Wout", C.c_int32),
@@ -171,6 +179,7 @@ _SIGS = {
     "f2g_dwnorm_fwd": [C.POINTER(DwnormFwd)],
     "f2g_dwnorm_bwd": [C.POINTER(DwnormBwd)],
     "f2g_dwconv_bwd": [C.POINTER(DwconvBwd)],
+    "f2g_dwblock_bwd": [C.POINTER(DwblockBwd)],
     "f2g_biasnorm_fwd": [_P, _L, _P, _L, _I, _I, _P, _P],
     "f2g_biasnorm_bwd": [_P, _L, _P, _L, _P, _L, _I, _I, _P, _P, _P, _P],
     "f2g_istft_ola": [_P, _L, _P, _I, _I, _I, _I, _I, _P, _P, _F, _I],
@@ -249,7 +258,8 @@ EXPORTS = sorted(list(_SIGS) + ["f2g_version", "f2g_last_error", "f2g_gemm_last_
                                  "f2g_gemm_lean_ok", "f2g_gemm_wgrad_lean", "f2g_fused_mlp_ok",
                                  "f2g_dwnorm_bwd_workspace", "f2g_split_bf16x3_bytes", "f2g_gemm_x6_ok",
                                  "f2g_gemm_colsum_part_rows", "f2g_gemm_f16_ok", "f2g_set_option", "f2g_get_option",
-                                 "f2g_dwconv_bwd_workspace", "f2g_sadam_chunk_elems"])
+                                 "f2g_dwconv_bwd_workspace", "f2g_sadam_chunk_elems",
+                                 "f2g_dwblock_bwd_ok", "f2g_dwblock_bwd_workspace"])
 
 
 class F2GError(RuntimeError):
@@ -270,6 +280,10 @@ def _load():
         fn = getattr(lib, name)
         fn.argtypes = [C.c_int32] * 4
         fn.restype = C.c_int64
+    lib.f2g_dwblock_bwd_workspace.argtypes = [C.c_int32] * 3
+    lib.f2g_dwblock_bwd_workspace.restype = C.c_int64
+    lib.f2g_dwblock_bwd_ok.argtypes = [C.c_int32] * 4
+    lib.f2g_dwblock_bwd_ok.restype = C.c_int
     lib.f2g_gemm_lean_ok.argtypes = [C.POINTER(GemmDesc)]
     lib.f2g_gemm_lean_ok.restype = C.c_int
     lib.f2g_gemm_wgrad_lean.argtypes = [C.POINTER(GemmDesc)]

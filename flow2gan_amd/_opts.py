@@ -38,7 +38,9 @@ layers' weight gradient on the fp16x3 kernel that keeps one running scale per op
 fp16x3_conv33_fwd, fp16x3_conv33_dgrad (F2G_GEMM=fp16x3: the MRD (3, 3) fifth layer's forward / data gradient on the
 fp16x3 kernel that scales each whole-row tile's patch inside the kernel, csrc/conv33h3.hip; both off by default),
 fp16x3_conv33_wgrad (that layer's weight gradient on the fp16x3 kernel that keeps one running scale per operand and
-block over its walk of whole-row tiles, csrc/conv33h3w.hip; off by default).
+block over its walk of whole-row tiles, csrc/conv33h3w.hip; off by default), dw_bwd_fused (fused.block_bwd runs the
+BiasNorm and depthwise-conv backward passes of a ConvNeXt block as one launch that keeps du on chip, f2g_dwblock_bwd,
+where the library takes the shape; off by default).
 
 Environment switches that remain on their own (user-facing, or needed before anything is imported):
 F2G_GEMM (arithmetic of the GEMMs), F2G_STREAMS (launch lanes), F2G_DETERMINISTIC (no splits on the library's

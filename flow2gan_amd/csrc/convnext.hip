@@ -892,7 +892,493 @@ int launch_dwnorm(const f2g_dwnorm_bwd_desc& d, hipStream_t st) {
   return f2g_check_launch();
 }
 
+// ---- BiasNorm backward + depthwise-conv backward in ONE launch (f2g_dwblock_bwd) -----------------
+//
+// The pair above moves seven tensor streams per block and du exists only to be written and read back
+// once.  Here a block owns BB_T consecutive frames of one batch item and all C channels, tile after
+// tile (tpb tiles: the parameter-gradient sums stay in registers over them), and du lives in LDS:
+//   phase 1  the arithmetic of the 4-frame vector BiasNorm backward above: wave w takes the tile's frames
+//            4w .. 4w+3, then the four waves share the 3 + 3 halo frames (2, 1, 2, 1); each writes its
+//            du rows to the [BB_T + 6][C] LDS tile.  Halo frames give du and nothing else.
+//   phase 2  the arithmetic of the vector depthwise backward above: a thread owns 4 channels and BB_T / SEG
+//            frames (SEG = 4, 2, 1 frame segments at 1, 2, 3 channel chunks, so that 256 threads
+//            cover C x BB_T), reads its du rows from LDS as float4, x again (cache hits) and gres,
+//            writes gx, keeps gw[4][7], gb, gg in registers.
+//   flush    one partial row per block, [beta C | te C | log_scale 1 | g_w 7C | g_b C | g_gamma C],
+//            summed by blockbwd_reduce_kernel in a fixed order: no atomics anywhere.
+// BB_T is a multiple of 4, so the up <= 4 frames of a condition row never straddle two waves.
+constexpr int BB_T = 16;
+constexpr int BB_ROWS = BB_T + 2 * HALO;
+constexpr int BB_MAX_TILES = 8;        // tiles per block at most
+constexpr int BB_BLOCKS = 768;         // ... chosen so that about this many blocks remain (3 per CU)
+
+int bb_tiles_per_block(int B, int F) {
+  const long long tiles = (F + BB_T - 1) / BB_T;
+  const long long m = (long long)B * tiles / BB_BLOCKS;
+  return (int)(m < 1 ? 1 : (m > BB_MAX_TILES ? BB_MAX_TILES : m));
+}
+int bb_blocks_per_item(int B, int F) {
+  const int tiles = (F + BB_T - 1) / BB_T, tpb = bb_tiles_per_block(B, F);
+  return (tiles + tpb - 1) / tpb;
+}
+constexpr int bb_segs(int nch) { return nch == 1 ? 4 : (nch == 2 ? 2 : 1); }
+// LDS floats: taps + biases (9C) and the du tile while the tiles run, the two flush areas after them
+size_t bb_lds_floats(int C, int nch) {
+  const size_t run = (size_t)(9 + BB_ROWS) * C, flush = (size_t)4 * (2 * C + 1) + (size_t)bb_segs(nch) * 9 * C;
+  return run > flush ? run : flush;
+}
+
+// FW consecutive frames from fs on (the first nvalid of them count) of batch item b: du -> the LDS tile
+// whose row 0 is frame tf0 - HALO; owned frames also add to the block's gradient sums and write g_cproj.
+template <int NCH, int FW>
+__device__ __forceinline__ void bb_norm_rows(const f2g_dwnorm_bwd_desc& D, const float* wl, const float* bl,
+                                             float* dl, int tf0, int fs, int nvalid, bool owned, int b,
+                                             int lim, const int (&c4)[NCH], const bool (&cok)[NCH],
+                                             const float (&te1)[NCH][4], const float (&bt)[NCH][4],
+                                             float escale, float (&gbeta)[NCH][4], float (&gte)[NCH][4],
+                                             float& glam) {
+  const f2g_dwnorm_fwd_desc& P = D.f;
+  const int F = P.F, C = P.C;
+  if (fs >= F || fs + nvalid <= 0) return;      // (the same for the whole wave)
+  const long long rb = (long long)b * F;
+  // every global read of these frames, back to back; row indices clamped, rows zeroed at use
+  float xr[NCH][FW + 6][4];
+#pragma unroll
+  for (int r = 0; r < FW + 6; ++r) {
+    int f = fs - HALO + r;
+    f = f < 0 ? 0 : (f > F - 1 ? F - 1 : f);
+    const float* xrow = P.x + (rb + f) * P.ldx;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) ld4(xr[k][r], xrow + c4[k]);
+  }
+  float gz[FW][NCH][4];
+#pragma unroll
+  for (int i = 0; i < FW; ++i) {
+    int f = fs + i;
+    f = f < 0 ? 0 : (f > F - 1 ? F - 1 : f);
+    const float* grow = D.gz + (rb + f) * D.ldgz;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) ld4(gz[i][k], grow + c4[k]);
+  }
+  const bool need_cp = owned && P.cproj && D.g_te && P.Fc > 0;   // the condition rows enter g_te alone
+  float cp[FW][NCH][4];
+#pragma unroll
+  for (int i = 0; i < FW; ++i) {
+    int fc = P.cproj ? (fs + i) / P.up : 0;
+    const bool has = need_cp && fc < P.Fc && fs + i < F;
+    fc = has ? fc : 0;
+    const float* cprow = need_cp ? P.cproj + ((long long)b * P.Fc + fc) * P.ldcp : P.x;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      ld4(cp[i][k], cprow + c4[k]);
+      if (!has) { cp[i][k][0] = cp[i][k][1] = cp[i][k][2] = cp[i][k][3] = 0.f; }
+    }
+  }
+#pragma unroll
+  for (int r = 0; r < FW + 6; ++r) {
+    const int f = fs - HALO + r;
+    if (f < 0 || f >= lim) {
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) xr[k][r][0] = xr[k][r][1] = xr[k][r][2] = xr[k][r][3] = 0.f;
+    }
+  }
+  // depthwise conv + sum of squares
+  float u[FW][NCH][4];
+  float ssq[FW];
+#pragma unroll
+  for (int i = 0; i < FW; ++i) ssq[i] = 0.f;
+#pragma unroll
+  for (int k = 0; k < NCH; ++k) {
+    float b4[4];
+    ld4(b4, bl + c4[k]);
+#pragma unroll
+    for (int i = 0; i < FW; ++i)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) u[i][k][e] = b4[e];
+#pragma unroll
+    for (int j = 0; j < 7; ++j) {
+      float w4[4];
+      ld4(w4, wl + j * C + c4[k]);
+#pragma unroll
+      for (int i = 0; i < FW; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) u[i][k][e] += w4[e] * xr[k][i + j][e];
+    }
+    if (cok[k]) {
+#pragma unroll
+      for (int i = 0; i < FW; ++i)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float dlt = u[i][k][e] - bt[k][e];
+          ssq[i] += dlt * dlt;
+        }
+    }
+  }
+  const float invC = 1.f / (float)C;
+  float gcp[NCH][4];
+#pragma unroll
+  for (int k = 0; k < NCH; ++k)
+#pragma unroll
+    for (int e = 0; e < 4; ++e) gcp[k][e] = 0.f;
+#pragma unroll
+  for (int i = 0; i < FW; ++i) {
+    const int f = fs + i;
+    if (i >= nvalid || f < 0 || f >= F) continue;
+    const float r = wave_sum(ssq[i]) * invC;
+    const float s = escale / sqrtf(r);
+    float dsum = 0.f;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      if (cok[k]) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float g = gz[i][k][e];
+          const float gv = g * te1[k][e];
+          gz[i][k][e] = gv;
+          dsum += gv * u[i][k][e];
+          if (owned) {
+            gte[k][e] += g * (u[i][k][e] * s + cp[i][k][e]);
+            gcp[k][e] += gv;
+          }
+        }
+      }
+    }
+    dsum = wave_sum(dsum);
+    const float coef = s * dsum / ((float)C * r);
+    if (owned) glam += s * dsum;
+    float* drow = dl + (f - (tf0 - HALO)) * C;
+#pragma unroll
+    for (int k = 0; k < NCH; ++k) {
+      if (cok[k]) {
+        float d4[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const float t = coef * (u[i][k][e] - bt[k][e]);
+          if (owned) gbeta[k][e] += t;
+          d4[e] = s * gz[i][k][e] - t;
+        }
+        st4(drow + c4[k], d4);
+      }
+    }
+    // condition gradient: the frames sharing one condition row lie inside these FW frames (up | 4, 4 | fs)
+    const bool group_end = ((f + 1) % P.up == 0) || (f == F - 1) || (i == FW - 1);
+    if (owned && D.g_cproj && group_end) {
+      const int fc = f / P.up;
+      const bool has_cp = fc < P.Fc;
+      float* grow = D.g_cproj + ((long long)b * P.Fc + (has_cp ? fc : 0)) * P.ldcp;
+#pragma unroll
+      for (int k = 0; k < NCH; ++k) {
+        if (cok[k] && has_cp) {
+          float o[4] = {0.f, 0.f, 0.f, 0.f};
+          if (!D.g_cproj_store) ld4(o, grow + c4[k]);
+#pragma unroll
+          for (int e = 0; e < 4; ++e) o[e] += gcp[k][e];
+          st4(grow + c4[k], o);
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) gcp[k][e] = 0.f;
+      }
+    }
+  }
+}
+
+// (one wave per SIMD: a budget of 256 registers -- two -- spills at every chunk count, also with 2 + 2 owned frames
+// per wave and 4-frame rounds in phase 2)
+template <int NCH>
+__global__ __launch_bounds__(256, 1) void blockbwd_kernel(const f2g_dwblock_bwd_desc Q, int tpb) {
+  extern __shared__ __attribute__((aligned(16))) float sm[];
+  const f2g_dwnorm_bwd_desc& D = Q.n;
+  const f2g_dwnorm_fwd_desc& P = D.f;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int F = P.F, C = P.C;
+  float* wl = sm;                // [7][C] taps
+  float* bl = sm + 7 * C;        // depthwise bias
+  float* tl = sm + 8 * C;        // BiasNorm bias
+  float* dl = sm + 9 * C;        // [BB_ROWS][C] du of the tile and its halo
+  const int b = blockIdx.y;
+  const int len_b = P.lens ? P.lens[b] : F;
+  const int lim = len_b < F ? len_b : F;
+  const long long rb = (long long)b * F;
+  const float escale = expf(P.log_scale[0]);
+
+  // taps -> LDS, transposed (7 taps: the (C, 1, 7) block is 7C/4 float4s)
+  {
+    const int nq = 7 * C / 4;
+    for (int i4 = threadIdx.x; i4 < nq; i4 += 256) {
+      const float4 q = reinterpret_cast<const float4*>(P.w_dw)[i4];
+      const float v[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const unsigned i = 4u * i4 + e, c = i / 7u, j = i - 7u * c;
+        wl[j * C + c] = v[e];
+      }
+    }
+    for (int i = threadIdx.x; i < C; i += 256) {
+      bl[i] = P.b_dw ? P.b_dw[i] : 0.f;
+      tl[i] = P.beta[i];
+    }
+  }
+  // phase 1's channels: 4 consecutive ones per 256-channel chunk
+  int c4[NCH];
+  bool cok[NCH];
+  float te1[NCH][4], bt[NCH][4], gbeta[NCH][4], gte[NCH][4];
+  float glam = 0.f;
+#pragma unroll
+  for (int k = 0; k < NCH; ++k) {
+    const int c = 256 * k + 4 * lane;
+    cok[k] = c < C;
+    c4[k] = cok[k] ? c : 0;
+    ld4(te1[k], (P.te ? P.te + (long long)b * P.ldte : P.x) + c4[k]);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      te1[k][e] = P.te ? 1.f + te1[k][e] : 1.f;
+      gbeta[k][e] = 0.f;
+      gte[k][e] = 0.f;
+    }
+  }
+  // phase 2's channels and frames: 4 channels x FRS frames of every tile, in rounds of FR frames
+  constexpr int SEG = bb_segs(NCH), FRS = BB_T / SEG, FR = FRS < 8 ? FRS : 8;
+  const int seg = threadIdx.x / (64 * NCH);
+  const int pc = 4 * (threadIdx.x - seg * 64 * NCH);
+  const bool pok = seg < SEG && pc < C;
+  const int pc4 = pok ? pc : 0;
+  float gam[4] = {1.f, 1.f, 1.f, 1.f};
+  if (Q.gamma) ld4(gam, Q.gamma + pc4);
+  float gw[4][7], gb[4], gg[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    gb[e] = 0.f; gg[e] = 0.f;
+#pragma unroll
+    for (int j = 0; j < 7; ++j) gw[e][j] = 0.f;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < NCH; ++k) ld4(bt[k], tl + c4[k]);
+  float w[7][4];   // [tap][channel]
+#pragma unroll
+  for (int j = 0; j < 7; ++j) ld4(w[j], wl + j * C + pc4);
+
+  for (int t = 0; t < tpb; ++t) {
+    const int tf0 = (blockIdx.x * tpb + t) * BB_T;
+    if (tf0 >= F) break;
+    // ---- phase 1: du of frames tf0 - 3 .. tf0 + BB_T + 2 -> LDS (the halo first: it stores nothing to global
+    // memory, so the owned frames' loads may be issued under its arithmetic)
+    {
+      const int hs = wave == 0 ? tf0 - 3 : (wave == 1 ? tf0 - 1 : (wave == 2 ? tf0 + BB_T : tf0 + BB_T + 2));
+      bb_norm_rows<NCH, 2>(D, wl, bl, dl, tf0, hs, (wave & 1) ? 1 : 2, false, b, lim, c4, cok, te1, bt, escale,
+                           gbeta, gte, glam);
+    }
+    bb_norm_rows<NCH, 4>(D, wl, bl, dl, tf0, tf0 + 4 * wave, 4, true, b, lim, c4, cok, te1, bt, escale, gbeta,
+                         gte, glam);
+    __syncthreads();
+    // ---- phase 2: gx and the depthwise parameter gradients from the LDS tile
+    if (pok) {
+#pragma unroll 1
+      for (int rd = 0; rd < FRS / FR; ++rd) {
+        const int fs = tf0 + seg * FRS + rd * FR;
+        if (fs >= F) break;
+        float xr[FR + 6][4], gr[FR][4], du[FR + 6][4];
+#pragma unroll
+        for (int r = 0; r < FR + 6; ++r) {
+          int f = fs - 3 + r;
+          f = f < 0 ? 0 : (f > F - 1 ? F - 1 : f);
+          ld4(xr[r], P.x + (rb + f) * P.ldx + pc4);
+        }
+#pragma unroll
+        for (int i = 0; i < FR; ++i) {
+          int f = fs + i;
+          f = f > F - 1 ? F - 1 : f;
+          ld4(gr[i], (Q.gres ? Q.gres + (rb + f) * Q.ldgres : P.x + (rb + f) * P.ldx) + pc4);
+        }
+#pragma unroll
+        for (int r = 0; r < FR + 6; ++r) {
+          const int f = fs - 3 + r;
+          ld4(du[r], dl + (fs - tf0 + r) * C + pc4);       // row fs - 3 + r - (tf0 - 3), always inside the tile
+          if (f < 0 || f >= F) { du[r][0] = du[r][1] = du[r][2] = du[r][3] = 0.f; }
+        }
+        // residual-scale gradient uses the UNMASKED input row
+#pragma unroll
+        for (int i = 0; i < FR; ++i) {
+          const bool in = fs + i < F && Q.gres;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            gr[i][e] = in ? gr[i][e] : 0.f;
+            gg[e] += gr[i][e] * xr[i + 3][e];
+          }
+        }
+#pragma unroll
+        for (int r = 0; r < FR + 6; ++r) {
+          const int f = fs - 3 + r;
+          if (f < 0 || f >= lim) { xr[r][0] = xr[r][1] = xr[r][2] = xr[r][3] = 0.f; }
+        }
+#pragma unroll
+        for (int i = 0; i < FR; ++i) {
+          const int f = fs + i;
+          float dx[4];
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            float a = 0.f;
+#pragma unroll
+            for (int j = 0; j < 7; ++j) a += w[j][e] * du[i + 6 - j][e];
+            a = f >= len_b ? 0.f : a;
+            dx[e] = a + gam[e] * gr[i][e];
+            const float duc = du[i + 3][e];
+            gb[e] += duc;
+#pragma unroll
+            for (int j = 0; j < 7; ++j) gw[e][j] += duc * xr[i + j][e];
+          }
+          if (f < F) st4(Q.gx + (rb + f) * Q.ldgx + pc4, dx);
+        }
+      }
+    }
+    __syncthreads();   // the next tile overwrites the du rows (and the flush below the whole of LDS)
+  }
+  // ---- flush: the 4 waves' BiasNorm sums and the SEG segments' depthwise sums -> one partial row
+  const int W1 = 2 * C + 1;
+  float* ra = sm;                 // [4][2C + 1]
+  float* rc = sm + 4 * W1;        // [SEG][9][C]
+#pragma unroll
+  for (int k = 0; k < NCH; ++k) {
+    if (cok[k]) {
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        ra[wave * W1 + c4[k] + e] = gbeta[k][e];
+        ra[wave * W1 + C + c4[k] + e] = gte[k][e];
+      }
+    }
+  }
+  if (lane == 0) ra[wave * W1 + 2 * C] = glam;
+  if (pok) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+#pragma unroll
+      for (int j = 0; j < 7; ++j) rc[(seg * 9 + j) * C + pc4 + e] = gw[e][j];
+      rc[(seg * 9 + 7) * C + pc4 + e] = gb[e];
+      rc[(seg * 9 + 8) * C + pc4 + e] = gg[e];
+    }
+  }
+  __syncthreads();
+  const int W = 11 * C + 1;
+  float* prow = Q.partials + ((long long)b * gridDim.x + blockIdx.x) * W;
+  for (int i = threadIdx.x; i < W; i += 256) {
+    float s = 0.f;
+    if (i < W1) {
+      s = (ra[i] + ra[W1 + i]) + (ra[2 * W1 + i] + ra[3 * W1 + i]);
+    } else {
+      const unsigned k = i - W1;
+      unsigned q, c;       // q: tap 0..6, 7 the bias sum, 8 the residual-scale sum
+      if (k < 7u * C) { c = k / 7u; q = k - 7u * c; } else { q = 7u + (k - 7u * C) / C; c = (k - 7u * C) % C; }
+#pragma unroll
+      for (int sg = 0; sg < SEG; ++sg) s += rc[(sg * 9 + q) * C + c];
+    }
+    prow[i] = s;
+  }
+}
+
+// second stage: a block takes 16 columns of the partial rows, its 16 row slices sum in a fixed order.
+// grid.y == 0: every column but the time embedding's, over all B * nxb rows, the slices combined through
+// LDS; grid.y == 1: the time-embedding columns, a slice summing the nxb rows of its items one by one.
+// Every output element has one owner: plain +=.
+__global__ __launch_bounds__(256) void blockbwd_reduce_kernel(const float* partials, int B, int nxb, int C,
+                                                              float* g_beta, float* g_te, long long ldte,
+                                                              float* g_log_scale, float* g_w, float* g_b,
+                                                              float* g_gamma) {
+  __shared__ float red[16][16];
+  const int W = 11 * C + 1;
+  const int col = threadIdx.x & 15, sl = threadIdx.x >> 4;
+  const int q = blockIdx.x * 16 + col;
+  const bool is_te = q >= C && q < 2 * C;
+  auto rows_sum = [&](const float* p, int first, int step, int nr) {
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int r = first;
+    for (; r + 3 * step < nr; r += 4 * step) {
+      s0 += p[(long long)r * W];
+      s1 += p[(long long)(r + step) * W];
+      s2 += p[(long long)(r + 2 * step) * W];
+      s3 += p[(long long)(r + 3 * step) * W];
+    }
+    for (; r < nr; r += step) s0 += p[(long long)r * W];
+    return (s0 + s1) + (s2 + s3);
+  };
+  if (blockIdx.y == 1) {
+    if (!is_te || !g_te) return;
+    for (int bi = sl; bi < B; bi += 16)
+      g_te[(long long)bi * ldte + (q - C)] += rows_sum(partials + (long long)bi * nxb * W + q, 0, 1, nxb);
+    return;
+  }
+  const bool mine = q < W && !is_te;
+  red[sl][col] = mine ? rows_sum(partials + q, sl, 16, B * nxb) : 0.f;
+  __syncthreads();
+  if (sl != 0 || !mine) return;
+  float s = 0.f;
+#pragma unroll
+  for (int i = 0; i < 16; ++i) s += red[i][col];
+  float* o;
+  if (q < C) o = g_beta ? g_beta + q : nullptr;
+  else if (q == 2 * C) o = g_log_scale;
+  else if (q < 9 * C + 1) o = g_w ? g_w + (q - 2 * C - 1) : nullptr;
+  else if (q < 10 * C + 1) o = g_b ? g_b + (q - 9 * C - 1) : nullptr;
+  else o = g_gamma ? g_gamma + (q - 10 * C - 1) : nullptr;
+  if (o) *o += s;
+}
+
+template <int NCH>
+int launch_blockbwd(const f2g_dwblock_bwd_desc& d, dim3 grid, int tpb, size_t smem, hipStream_t st) {
+  static bool attr_done = false;
+  if (!attr_done) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(blockbwd_kernel<NCH>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize,
+                              (int)(bb_lds_floats(256 * NCH, NCH) * sizeof(float)));
+    attr_done = true;
+  }
+  hipLaunchKernelGGL((blockbwd_kernel<NCH>), grid, dim3(256), smem, st, d, tpb);
+  return f2g_check_launch();
+}
+
 }  // namespace
+
+extern "C" int f2g_dwblock_bwd_ok(int32_t C, int32_t K, int32_t up, int32_t has_cond) {
+  if (K != 7 || C < 4 || C > 64 * CPL || (C % 4) != 0) return 0;
+  return (!has_cond || up == 1 || up == 2 || up == 4) ? 1 : 0;
+}
+
+extern "C" int64_t f2g_dwblock_bwd_workspace(int32_t B, int32_t F, int32_t C) {
+  if (B <= 0 || F <= 0 || C <= 0) return 0;
+  return (int64_t)B * bb_blocks_per_item(B, F) * (11 * (int64_t)C + 1);
+}
+
+extern "C" int f2g_dwblock_bwd(const f2g_dwblock_bwd_desc* d, f2g_stream_t stream) {
+  if (!d) return F2G_EINVAL;
+  const f2g_dwnorm_bwd_desc& n = d->n;
+  const f2g_dwnorm_fwd_desc& f = n.f;
+  if (!f.x || !n.gz || !d->gx || !f.w_dw || !f.beta || !f.log_scale || !d->partials || n.du) return F2G_EINVAL;
+  if (!f2g_dwblock_bwd_ok(f.C, f.K, f.up, f.cproj != nullptr)) return F2G_EINVAL;
+  const void* ptrs[] = {f.x, n.gz, d->gx, f.w_dw, f.b_dw, f.beta, f.log_scale, f.lens, f.cproj, f.te, n.g_cproj,
+                        n.g_te, n.g_beta, n.g_log_scale, d->gres, d->gamma, d->g_w, d->g_b, d->g_gamma,
+                        d->partials};
+  for (const void* p : ptrs)
+    if (((uintptr_t)p) & 15) return F2G_EINVAL;
+  if ((f.ldx % 4) || (n.ldgz % 4) || (d->ldgx % 4) || (d->gres && (d->ldgres % 4)) ||
+      (f.cproj && (f.ldcp % 4)) || ((f.te || n.g_te) && (f.ldte % 4)))
+    return F2G_EINVAL;
+  if (d->gx == f.x || d->gx == n.gz || d->gx == d->gres) return F2G_EINVAL;
+  if (f.B <= 0 || f.F <= 0) return F2G_OK;
+  const int nch = (f.C + 255) / 256;
+  const int tpb = bb_tiles_per_block(f.B, f.F), nxb = bb_blocks_per_item(f.B, f.F);
+  const dim3 grid(nxb, f.B);
+  const size_t smem = bb_lds_floats(f.C, nch) * sizeof(float);
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if (nch == 1) { g_cn_last = "blockbwd<nch=1>"; rc = launch_blockbwd<1>(*d, grid, tpb, smem, st); }
+  else if (nch == 2) { g_cn_last = "blockbwd<nch=2>"; rc = launch_blockbwd<2>(*d, grid, tpb, smem, st); }
+  else { g_cn_last = "blockbwd<nch=3>"; rc = launch_blockbwd<3>(*d, grid, tpb, smem, st); }
+  if (rc) return rc;
+  const int W = 11 * f.C + 1;
+  hipLaunchKernelGGL(blockbwd_reduce_kernel, dim3((W + 15) / 16, 2), dim3(256), 0, st, d->partials, f.B,
+                     nxb, f.C, n.g_beta, n.g_te, (long long)f.ldte, n.g_log_scale, d->g_w, d->g_b,
+                     d->gres ? d->g_gamma : nullptr);
+  return f2g_check_launch();
+}
 
 extern "C" int64_t f2g_dwnorm_bwd_workspace(int32_t B, int32_t F, int32_t C, int32_t up) {
   const int FW = up == 4 ? 4 : 2;
@@ -974,6 +1460,7 @@ extern "C" int f2g_biasnorm_bwd(const float* x, int64_t ldx, const float* gy, in
 }
 
 // "dwnorm4<bwd=1,fw=4,nch=2>", "dwnorm<bwd=0,fw=2>", "dwconv4_bwd", "dwconv_bwd", "biasnorm_fwd" or
-// "biasnorm_bwd": the kernel instance the last f2g_dwnorm_* / f2g_dwconv_bwd / f2g_biasnorm_* call
-// launched (the second-stage reductions are not reported); "" before the first launch
+// "biasnorm_bwd", or "blockbwd<nch=2>" (f2g_dwblock_bwd): the kernel instance the last f2g_dwnorm_* /
+// f2g_dwconv_bwd / f2g_dwblock_bwd / f2g_biasnorm_* call launched (the second-stage reductions are not
+// reported); "" before the first launch
 extern "C" const char* f2g_convnext_last_launch(void) { return g_cn_last; }

@@ -199,14 +199,23 @@ def block_bwd(bp: _Blk, x, z, a, gout, B, F, lens, limit_norm: bool, limit_scale
         # dz = da W1  (z is dead after the weight gradient above: reuse it)
         gemm(mat(a, rows, Hh), mat(bp.w1.reshape(Hh, Cc)), z, form=1)
     share.drop()
-    du = ops.empty(rows, Cc, device=dev)
-    ops.dwnorm_bwd(x, z, du, B, F, Cc, bp.K, lens, bp.w_dw, bp.b_dw, bp.beta,
-                   bp.log_scale.reshape(1), cproj, ldcp, Fc, up, cp_off, te, ldte, te_off,
-                   g_cproj=g_cproj, g_te=g_te, g_beta=g_beta, g_log_scale=g_ls,
-                   g_cproj_store=g_cproj_store)
-    gx = ops.empty(rows, Cc, device=dev)
-    ops.dwconv_bwd(du, x, gx, B, F, Cc, bp.K, lens, bp.w_dw, gres=gout, gamma=bp.gamma.reshape(Cc),
-                   g_w=g_wdw, g_b=g_bdw, g_gamma=g_gamma)
+    if ops.DW_BWD_FUSED and ops.dwblock_bwd_ok(Cc, bp.K, up, cproj is not None):
+        # one launch, du stays on chip (z holds dz)
+        gx = ops.empty(rows, Cc, device=dev)
+        ops.dwblock_bwd(x, z, gx, B, F, Cc, bp.K, lens, bp.w_dw, bp.b_dw, bp.beta,
+                        bp.log_scale.reshape(1), cproj, ldcp, Fc, up, cp_off, te, ldte, te_off,
+                        g_cproj=g_cproj, g_te=g_te, g_beta=g_beta, g_log_scale=g_ls,
+                        g_cproj_store=g_cproj_store, gres=gout, gamma=bp.gamma.reshape(Cc),
+                        g_w=g_wdw, g_b=g_bdw, g_gamma=g_gamma)
+    else:
+        du = ops.empty(rows, Cc, device=dev)
+        ops.dwnorm_bwd(x, z, du, B, F, Cc, bp.K, lens, bp.w_dw, bp.b_dw, bp.beta,
+                       bp.log_scale.reshape(1), cproj, ldcp, Fc, up, cp_off, te, ldte, te_off,
+                       g_cproj=g_cproj, g_te=g_te, g_beta=g_beta, g_log_scale=g_ls,
+                       g_cproj_store=g_cproj_store)
+        gx = ops.empty(rows, Cc, device=dev)
+        ops.dwconv_bwd(du, x, gx, B, F, Cc, bp.K, lens, bp.w_dw, gres=gout, gamma=bp.gamma.reshape(Cc),
+                       g_w=g_wdw, g_b=g_bdw, g_gamma=g_gamma)
     if limit_norm:
         ops.limit_grad(g_ls, bp.log_scale.reshape(1), -1.5, 1.5)
     if limit_scale:

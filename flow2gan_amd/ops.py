@@ -1961,6 +1961,50 @@ def dwconv_bwd(du, x, gx, B, F, Cc, K, lens, w_dw, gres=None, gamma=None, g_w=No
     return gx
 
 
+# fused.block_bwd: dwnorm_bwd + dwconv_bwd in one launch (f2g_dwblock_bwd) where the library takes the shape; off
+# by default (tests and tools/dwblock_bwd_shapes.py flip it)
+DW_BWD_FUSED = opt("dw_bwd_fused", False)
+DWBLOCK_T = 16      # frames per tile of f2g_dwblock_bwd (csrc/convnext.hip: BB_T)
+
+
+def dwblock_bwd_ok(Cc, K, up=1, has_cond=False) -> bool:
+    return bool(L.lib.f2g_dwblock_bwd_ok(Cc, K, up, 1 if has_cond else 0))
+
+
+def dwblock_bwd(x, gz, gx, B, F, Cc, K, lens, w_dw, b_dw, beta, log_scale, cproj=None, ldcp=0, Fc=0, up=1,
+                cp_off=0, te=None, ldte=0, te_off=0, g_cproj=None, g_te=None, g_beta=None, g_log_scale=None,
+                g_cproj_store=False, gres=None, gamma=None, g_w=None, g_b=None, g_gamma=None, workspace=None):
+    """dwnorm_bwd followed by dwconv_bwd on its du, in one launch that keeps du on chip (arguments as theirs).
+    Refuses what f2g_dwblock_bwd_ok refuses: there is no fallback here (fused.block_bwd routes).
+    workspace: f2g_dwblock_bwd_workspace(B, F, Cc) floats of the caller's (tests); allocated here otherwise."""
+    d = L.DwblockBwd()
+    d.n.f = _dw_desc(x, x.stride(0), None, 0, B, F, Cc, K, lens, w_dw, b_dw, beta, log_scale, cproj, ldcp, Fc,
+                     up, cp_off, te, ldte, te_off, None)
+    d.n.gz, d.n.ldgz = ptr(gz), gz.stride(0)
+    d.n.g_cproj = None if g_cproj is None else ptr(g_cproj) + 4 * cp_off
+    d.n.g_cproj_store = 1 if (g_cproj_store and g_cproj is not None) else 0
+    d.n.g_te = None if g_te is None else ptr(g_te) + 4 * te_off
+    d.n.g_beta, d.n.g_log_scale = ptr(g_beta), ptr(g_log_scale)
+    d.gx, d.ldgx = ptr(gx), gx.stride(0)
+    d.gres = ptr(gres)
+    d.ldgres = gres.stride(0) if gres is not None else 0
+    d.gamma = ptr(gamma)
+    d.g_w, d.g_b, d.g_gamma = ptr(g_w), ptr(g_b), ptr(g_gamma)
+    if workspace is None:
+        workspace = torch.empty(max(L.lib.f2g_dwblock_bwd_workspace(B, F, Cc), 1), device=x.device,
+                                dtype=torch.float32)
+    d.partials = ptr(workspace)
+    if GEMM_TIMER is not None:
+        # algorithmic bytes: read x, gz and gres, write gx; condition rows and their gradient rows once per
+        # `up` frames each (as dwnorm_bwd accounts them)
+        nb = 4.0 * B * F * Cc * (4.0 + ((1.0 / up if cproj is not None else 0.0)
+                                      + (1.0 / up if g_cproj is not None else 0.0)))
+        GEMM_TIMER.time_hbm(lambda: call("f2g_dwblock_bwd", C.byref(d)), nb, "dwblock_bwd")
+    else:
+        call("f2g_dwblock_bwd", C.byref(d))
+    return gx
+
+
 def biasnorm_fwd(x, y, rows, Cc, beta, log_scale):
     call("f2g_biasnorm_fwd", ptr(x), x.stride(0), ptr(y), y.stride(0), rows, Cc, ptr(beta),
          ptr(log_scale))

@@ -513,6 +513,33 @@ typedef struct {
 int f2g_dwconv_bwd(const f2g_dwconv_bwd_desc* d, f2g_stream_t stream);
 int64_t f2g_dwconv_bwd_workspace(int32_t B, int32_t F, int32_t C, int32_t K);
 
+/* f2g_dwnorm_bwd and f2g_dwconv_bwd in ONE launch (modules.py:473-485, A.3/A.4): du stays on chip, the
+ * launch reads x, gz, gres and writes gx.  Everything f2g_dwnorm_bwd computes from `n` (g_cproj in either
+ * mode, g_te, g_beta, g_log_scale) and everything f2g_dwconv_bwd computes (gx, g_w, g_b, g_gamma), with the
+ * same masking: du is defined for every frame 0 <= f < F (frames past lens included) and 0 outside.  The
+ * parameter-gradient sums go through `partials` (one row per block, summed by a second launch in a fixed
+ * order: no atomics, bit-reproducible) and are ADDED to g_beta / g_te / g_log_scale / g_w / g_b / g_gamma
+ * (each may be NULL; g_gamma is left alone without gres).
+ * Accepts only K == 7, C % 4 == 0, 4 <= C <= 768 and, with a condition input, up in {1, 2, 4}
+ * (f2g_dwblock_bwd_ok); every non-NULL pointer 16-byte aligned, every row stride a multiple of 4 floats,
+ * partials non-NULL, n.du NULL, gx different from x, gz and gres.  Anything else is F2G_EINVAL before any
+ * launch: the entry point refuses and never falls back.  B <= 0 or F <= 0: F2G_OK, nothing launched. */
+typedef struct {
+  f2g_dwnorm_bwd_desc n; /* as for f2g_dwnorm_bwd; n.du must be NULL, n.partials is ignored */
+  float* gx;
+  int64_t ldgx;
+  const float* gres; /* gradient of the block output (residual path), may be NULL */
+  int64_t ldgres;
+  const float* gamma; /* ChannelScale (C), may be NULL (then 1) */
+  float* g_w;
+  float* g_b;
+  float* g_gamma;
+  float* partials; /* f2g_dwblock_bwd_workspace(B,F,C) floats, required */
+} f2g_dwblock_bwd_desc;
+int f2g_dwblock_bwd_ok(int32_t C, int32_t K, int32_t up, int32_t has_cond);
+int64_t f2g_dwblock_bwd_workspace(int32_t B, int32_t F, int32_t C);
+int f2g_dwblock_bwd(const f2g_dwblock_bwd_desc* d, f2g_stream_t stream);
+
 /* BiasNorm alone (modules.py:286-416), channels-last, in place allowed (y may equal x). */
 int f2g_biasnorm_fwd(const float* x, int64_t ldx, float* y, int64_t ldy, int32_t rows, int32_t C,
                      const float* beta, const float* log_scale, f2g_stream_t stream);
@@ -1047,9 +1074,11 @@ int f2g_fused_block_multi(const f2g_dwnorm_fwd_desc* dw, const f2g_fused_mlp_des
  * order handed over). */
 const char* f2g_fused_last_launch(void);
 /* The same for the HBM-bound ConvNeXt kernels (f2g_dwnorm_fwd / f2g_dwnorm_bwd / f2g_dwconv_bwd /
- * f2g_biasnorm_fwd / f2g_biasnorm_bwd): the kernel instance the last of them launched, "" before the first.
+ * f2g_dwblock_bwd / f2g_biasnorm_fwd / f2g_biasnorm_bwd): the kernel instance the last of them launched, "" before
+ * the first.
  * "dwnorm4<bwd=B,fw=W,nch=N>" (float4 rows: W frames per wave, N 256-channel chunks per lane),
- * "dwnorm<bwd=B,fw=W>" (any C, any alignment), "dwconv4_bwd", "dwconv_bwd", "biasnorm_fwd", "biasnorm_bwd".
+ * "dwnorm<bwd=B,fw=W>" (any C, any alignment), "dwconv4_bwd", "dwconv_bwd", "biasnorm_fwd", "biasnorm_bwd",
+ * "blockbwd<nch=N>" (f2g_dwblock_bwd: N 256-channel chunks).
  * A host-side static set where the kernel is launched; tests and diagnostics, not thread safe. */
 const char* f2g_convnext_last_launch(void);
 
