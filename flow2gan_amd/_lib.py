@@ -44,6 +44,9 @@ class Epilogue(C.Structure):
         ("mask_src", C.c_void_p), ("fm_ref", C.c_void_p), ("fm_wdev", C.c_void_p),
         ("mask_slope", C.c_float), ("fm_w", C.c_float),
         ("x3_out", C.c_void_p), ("colsum_part_ld", C.c_int64),
+        # gemm_h3pn3_kernel alone (0 = off): output column n stands for channel n % col_fold of `colsum`; elements from
+        # offset seq_live of their sequence's row range on are neither stored nor summed (include/flow2gan_hip.h)
+        ("col_fold", C.c_int32), ("seq_live", C.c_int64),
     ]
 
 

@@ -32,7 +32,9 @@ windows of five positions of a 32-channel halo map -- the MPD's 32 -> 128 forwar
 scales the fp32 map per sequence segment inside the kernel, without an image pass; off by default),
 fp16x3_tapn_min_rows (the fewest output rows at which a GEMM over stride-1 windows of two or one positions of a
 128-channel halo map onto at most 32 columns -- the stride-residue data gradients of that layer -- takes the fp16x3
-kernel that scales the fp32 map per sequence segment inside the kernel; off by default), fp16x3_conv32_fwd, fp16x3_conv32_dgrad (F2G_GEMM=fp16x3: the MRD (3, 9) band layers' forward / data gradient on the
+kernel that scales the fp32 map per sequence segment inside the kernel; off by default), fp16x3_tapn3_min_rows (the
+fewest output rows, S * ceil(Hin / 3), at which that layer's data gradient is ONE launch over 96 columns for its three
+stride residues, which reads the gradient map once instead of three times; off by default), fp16x3_conv32_fwd, fp16x3_conv32_dgrad (F2G_GEMM=fp16x3: the MRD (3, 9) band layers' forward / data gradient on the
 fp16x3 kernels that scale each tile's patch inside the kernel; both off by default), fp16x3_conv32_wgrad (the same
 layers' weight gradient on the fp16x3 kernel that keeps one running scale per operand and block; off by default),
 fp16x3_conv33_fwd, fp16x3_conv33_dgrad (F2G_GEMM=fp16x3: the MRD (3, 3) fifth layer's forward / data gradient on the

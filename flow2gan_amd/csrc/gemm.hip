@@ -898,6 +898,10 @@ extern "C" int f2g_gemm(const f2g_gemm_desc* dp, f2g_stream_t stream) {
     return F2G_EINVAL;
   }
   if (d.precision == 4) return f2g_gemm_h3(d, st);   // fp16x3: its own kernels or F2G_EINVAL
+  if (d.E.col_fold || d.E.seq_live) {
+    f2g_set_error("f2g_gemm: E.col_fold / E.seq_live belong to gemm_h3pn3_kernel (precision 4), never run elsewhere");
+    return F2G_EINVAL;
+  }
   if ((d.A.split >= 5 && d.A.split <= 9) || (d.B.split >= 5 && d.B.split <= 9)) {
     f2g_set_error("f2g_gemm: f2g_split_f16x2 / _cols / _seq images (split = 5 / 6 / 7) and maps or matrices scaled "
                   "inside the kernel (split = 8 / 9) belong to precision 4");

@@ -36,6 +36,8 @@ int f2g_h3p3n_ok(const f2g_gemm_desc& d);      // ... over 32 channels of the fp
 int f2g_launch_h3p3n(const f2g_gemm_desc& d, hipStream_t st);
 int f2g_h3pn_ok(const f2g_gemm_desc& d);       // ... stride-1 windows of 2 or 1 positions of the fp32 map, N <= 32
 int f2g_launch_h3pn(const f2g_gemm_desc& d, hipStream_t st);
+int f2g_h3pn3_ok(const f2g_gemm_desc& d);      // ... the three residues' windows of 2 positions at once, N == 96, cut and folded
+int f2g_launch_h3pn3(const f2g_gemm_desc& d, hipStream_t st);
 int f2g_h3wt_ok(const f2g_gemm_desc& d);       // form 2, unbounded stride-1 windows of 5 positions over column images
 int f2g_launch_h3wt(const f2g_gemm_desc& d, hipStream_t st);
 int f2g_h3ws_ok(const f2g_gemm_desc& d);       // ... stride-3 windows over a multiple of 128 channels

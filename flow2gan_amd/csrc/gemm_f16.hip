@@ -405,8 +405,8 @@ int f2g_launch_h3w(const f2g_gemm_desc& d, hipStream_t st) {
 // The fp16x3 kernels, one entry each.  h3_route_of walks the table in order: the FIRST entry whose `claims` holds -- a
 // test of the descriptor's form, marks and operand shapes alone -- is the descriptor's candidate, and that kernel's own
 // conditions (`ok`) decide.  Nothing else is asked: a descriptor one kernel declines is never offered to another.  So
-// the order is part of the rule -- the marked operands (split = 8 / 9: fp32, scaled inside the kernel) in front of the
-// shapes, a windows' stride 3 in front of "any stride", the plain kernels of each form last.
+// the order is part of the rule -- the epilogue fields only one kernel knows (E.col_fold / E.seq_live) in front of
+// everything, the marked operands (split = 8 / 9: fp32, scaled inside the kernel) in front of the shapes, a windows' stride 3 in front of "any stride", the plain kernels of each form last.
 // `ok` answers f2g_gemm_f16_ok: 0 = not for this kernel, 1 = runs as handed over (the operands the kernel's images
 // with their reciprocal scales, or marked fp32), 2 = once the fp32 operands are replaced by those images.
 // `part_tile`: the tile height the kernel's wide epilogue counts partial column sums in, one row per 64 output rows of
@@ -423,6 +423,12 @@ inline bool h3_form2_p4(const f2g_gemm_desc& d) { return d.form == 2 && d.precis
 inline bool h3_tapw_shape(const f2g_gemm_desc& d) { return h3_form2_p4(d) && host_plain(d.A) && !host_plain(d.B); }
 
 const h3_entry h3_table[] = {
+    // H3_TAPN3, gemm_h3pn3_kernel (gemm_f16pn3.hip).  It stands first and claims every descriptor that sets E.col_fold
+    // or E.seq_live, whatever its form and marks: no other kernel knows the two fields, so what this one declines is
+    // F2G_EINVAL and never reaches H3_TAPN or any entry below with the fields ignored
+    {[](const f2g_gemm_desc& d) { return d.E.col_fold != 0 || d.E.seq_live != 0; }, f2g_h3pn3_ok, f2g_launch_h3pn3, 0,
+     "form 0 over the fp32 map (A.split = 8) under stride-1 windows of 2 positions over 128 channels onto 96 columns, "
+     "three rows of a 32-channel map side by side (E.col_fold = 32, E.seq_live), against a f2g_split_f16x2_seq image"},
     // H3_TAPW3N, gemm_h3wsn_kernel (gemm_f16wsn.hip)
     {[](const f2g_gemm_desc& d) { return h3_form2_p4(d) && (d.A.split == 8 || d.B.split == 8); }, f2g_h3wsn_ok,
      f2g_launch_h3wsn, 0,

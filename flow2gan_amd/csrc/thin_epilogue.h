@@ -1,6 +1,7 @@
 // Thin epilogue of the kernels whose tile is 128 output rows x all N <= 32 columns, four waves of 32 x 32 -- the data
 // gradients that land on a 32-channel map through the row map of a stride residue.  gemm_h3pn_kernel
-// (gemm_f16pn.hip) calls it.  gemm_x6n_kernel (gemm_x6.hip) has the same steps inline, where they were written first:
+// (gemm_f16pn.hip) calls it; gemm_h3pn3_kernel (gemm_f16pn3.hip: three such column groups side by side) calls
+// row_values_cut and column_sums.  gemm_x6n_kernel (gemm_x6.hip) has the same steps inline, where they were written first:
 // calling these functions there moved it from 102 to 104 registers, so it keeps its copy and its device code stays
 // what it was.  A change to one belongs in the other.
 //
@@ -49,6 +50,37 @@ __device__ __forceinline__ float row_values(const f2g_epilogue& E, const f32x16&
     const long long off = ro + col;
     float v = acc[e] + bias;
     if (E.lrelu_slope != 0.f) v = v > 0.f ? v : E.lrelu_slope * v;
+    if (E.mask_src) {   // leaky-ReLU backward of the layer below (+ feature-matching term)
+      const float y = E.mask_src[off];
+      if (E.fm_ref) {
+        const float dl = y - E.fm_ref[off];
+        v += fmw * (dl > 0.f ? 1.f : (dl < 0.f ? -1.f : 0.f));
+      }
+      v *= y > 0.f ? 1.f : E.mask_slope;
+    }
+    cs += v;
+    E.C[off] = v;
+  }
+  return cs;
+}
+
+// row_values for a tile of three 32-column groups side by side (gemm_h3pn3_kernel, gemm_f16pn3.hip: f2g_epilogue's
+// col_fold / seq_live): the 32 x 32 accumulator tile of tile rows rg * 32 .., columns col0 + li, less the elements
+// behind their row's live columns -- rowlive[row] = the columns of that row in front of E.seq_live (<= 0: none) --,
+// which are neither stored nor summed.  A function of its own: row_values above stays the code it was for its callers.
+// No bias, no leaky ReLU (the caller's host check refuses them).
+__device__ __forceinline__ float row_values_cut(const f2g_epilogue& E, const f32x16& acc, int rg, int col0, int li,
+                                                int h, const long long* rowoff, const int* rowlive) {
+  const int col = col0 + li;
+  float cs = 0.f;
+  const float fmw = E.fm_ref ? E.fm_w * (E.fm_wdev ? E.fm_wdev[0] : 1.f) : 0.f;
+#pragma unroll
+  for (int e = 0; e < 16; ++e) {
+    const int tr = rg * 32 + (e & 3) + 8 * (e >> 2) + 4 * h;
+    const long long ro = rowoff[tr];
+    if (ro < 0 || col >= rowlive[tr]) continue;
+    const long long off = ro + col;
+    float v = acc[e];
     if (E.mask_src) {   // leaky-ReLU backward of the layer below (+ feature-matching term)
       const float y = E.mask_src[off];
       if (E.fm_ref) {

@@ -154,6 +154,38 @@ def _dgrad_weight(w, stride: int, j0: int, nt: int):
     return ops.derived(w, ("dgradT", stride, j0, nt), build)
 
 
+def _dgrad_weight3(w):
+    """The three stride residues of the (5, 1) / stride 3 / pad 2 transposed conv as ONE forward GEMM operand
+    Wc[rho * Cin + ci][j * Cout + co] = w[co][ci][t(rho, j)] over the window [g[q], g[q + 1]]: t = (2, -), (3, 0),
+    (4, 1), the block (rho = 0, j = 1) zero (csrc/gemm_f16pn3.hip).  Rows rho * Cin .. are _dgrad_weight's matrix of
+    that residue; the one-tap residue's lies in the left half of its rows (a strided copy of its own permute4)."""
+    def build(t):
+        Cout, Cin, K = t.shape[0], t.shape[1], t.shape[2] * t.shape[3]
+        out = ops.empty(3 * Cin, 2 * Cout, device=t.device)
+        ops.fill_(out[:Cin], 0.0)
+        one = ops.empty(Cin, Cout, device=t.device)
+        ops.permute4(one, t, (Cin, 1, Cout, 1), (K, -3, Cin * K, 0), in_offset=2)
+        ops.copy3(out, 2 * Cout, 0, one, Cout, 0, Cin, 1, Cout)
+        for rho in (1, 2):     # (taps rho + 2 and rho - 1, in window order)
+            ops.permute4(out[rho * Cin:(rho + 1) * Cin], t, (Cin, 2, Cout, 1), (K, -3, Cin * K, 0), in_offset=rho + 2)
+        return out
+    return ops.derived(w, ("dgradT3", 3), build)
+
+
+def _conv1d_dgrad3(g_pre, S, Hout, Cout, w, Hin, gx, mask, fm, colsum) -> bool:
+    """The fp16x3 mode's ONE launch for the three stride residues of the 32 -> 128 layer's data gradient
+    (ops.FP16X3_TAPN3_MIN_ROWS; gemm_h3pn3_kernel): rows 3 q, 3 q + 1, 3 q + 2 of gx are 96 consecutive floats, all
+    fed by the window [g[q], g[q + 1]]; the floats behind a sequence's 32 Hin are cut (seq_live).  False: nothing was
+    launched (the tunable, or the library declined), the caller runs its loop."""
+    if not ops.FP16X3 or S * Hout < ops.FP16X3_TAPN3_MIN_ROWS:
+        return False
+    Cin = w.shape[1]
+    A = win1d(g_pre, S, Hout + 2 * HALO, Cout, Hout, 1, -HALO, 2)
+    rm = (Hout, (Hin + 2 * HALO) * Cin, 3 * Cin, HALO * Cin)
+    return gemm(A, mat(_dgrad_weight3(w)), gx, rowmap=rm, mask=mask, fm=fm, colsum=colsum, col_fold=Cin,
+                seq_live=Cin * Hin) is not None
+
+
 def _conv1d_dgrad(g_pre, S, Hout, Cout, w, stride, pad, Hin, mask=None, fm=None, colsum=None):
     """g_x from g_pre (S sequences of Hout rows x Cout, halo layout).  Returns g_x in the halo layout
     (S, Hin + 2*HALO, Cin).  One forward-form GEMM per stride residue against the cached re-laid weights."""
@@ -164,6 +196,9 @@ def _conv1d_dgrad(g_pre, S, Hout, Cout, w, stride, pad, Hin, mask=None, fm=None,
     # fp32 map itself; the 512-channel map's image was written for nobody: 192 KB per 256 x 128 tile)
     want_img = 2 * Cin >= ops.X6_MIN_K
     gx = _halo_rows(S, Hin, Cin, dev, x3=want_img)
+    if (K, stride, pad, Cin, Cout) == (5, 3, 2, 32, 128) and not want_img \
+            and _conv1d_dgrad3(g_pre, S, Hout, Cout, w, Hin, gx, mask, fm, colsum):
+        return gx
     for rho, j0, nt, e0, Lq in _residues(K, stride, pad, Hin):
         if Lq == 0:
             continue

@@ -457,8 +457,11 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
          alpha_n=None, colsum_alpha=None, colsum=None, lrelu: float = 0.0, scale: float = 0.0,
          accumulate: bool = False, atomic: bool = False, split_k: int = 0, out_offset: int = 0,
          rowmap=None, prelu=None, prelu_out=None, mask=None, fm=None, x3_out: bool = False,
-         true_k: Optional[int] = None, true_n: Optional[int] = None):
+         true_k: Optional[int] = None, true_n: Optional[int] = None, col_fold: int = 0, seq_live: int = 0):
     """Launch f2g_gemm.  rowmap = (P0o, seq_stride_o, row_stride_o, off_o) or None.
+    col_fold / seq_live: f2g_epilogue's fields of the same names (the one-launch data gradient over three stride
+    residues, gemm_h3pn3_kernel).  No other kernel knows them: where the fp16x3 route TAPN3 does not take such a call,
+    NOTHING is launched and None is returned -- the caller issues the launches it stands for.
     true_k / true_n: the reduction length / output width WITHOUT zero padding (the spectrum rows are
     padded to whole K slabs): what bench.py's FLOP count uses; the launch itself ignores them.
     split_k: 0 = let the library decide (forms 0/1: split-K onto a zeroed output when the tile
@@ -502,6 +505,7 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
             e.fm_ref = ptr(fm[0]) + 4 * fm[1]
             e.fm_w = float(fm[2])
             e.fm_wdev = ptr(fm[3])
+    e.col_fold, e.seq_live = col_fold, seq_live
     d.E = e
     d.form = form
     if split_k == -1:
@@ -517,6 +521,8 @@ def gemm(A: Operand, Bm: Operand, out, form: int = 0, ldc: Optional[int] = None,
     d.split_k = split_k
     d.precision = GEMM_PRECISION
     f16 = _fp16x3_gemm(d, A, Bm, out, form, atomic, split_k, out_offset, x3_out, prelu_out)
+    if (col_fold or seq_live) and not f16:
+        return None
     if GEMM_PRECISION == 3 and f16:
         if x3_out and not d.E.x3_out:
             out._f2g_x3_bad = True     # (no image from this kernel: the next consumer builds its own)
@@ -1031,7 +1037,7 @@ class _F16Route(NamedTuple):
 
 # The routes by (form, shape of the operand that may lie under windows) -- form 0: forward, and data gradients over a
 # cached transpose, the operand is A; form 2: weight gradients, it is Bm; shape 0: a plain matrix, 1 / 3: win1d windows
-# of that stride (_fp16x3_route has the test) -- in the order they are tried: the first whose threshold, predicate and
+# of that stride, "fold3": stride-1 windows under E.col_fold / E.seq_live (_fp16x3_route has the test) -- in the order they are tried: the first whose threshold, predicate and
 # library answer agree takes the launch.  Routes under different keys never compete.  Under one key the order is
 # behaviour: the route that reads the fp32 operand itself (no image pass, nothing allocated per call) stands in front of
 # the image route over the same shapes -- PLAINN before PLAIN, TAPN before TAP (two-tap windows over 128 channels),
@@ -1063,6 +1069,16 @@ _FP16X3_ROUTES = {(0, 0): (
               not atomic and split_k <= 1 and A.cols in (5 * A.unit, 2 * A.unit) and A.cols >= X6_MIN_K
               and _f16_seq_window_ok(A),
               (_f16_seq_operand, _f16_seq_operand), x3_out=True),
+), (0, "fold3"): (
+    # TAPN3, gemm_h3pn3_kernel: a call that sets col_fold / seq_live -- the three stride residues of the 32 -> 128
+    # layer's data gradient as ONE GEMM onto 96 columns, two positions of the fp32 128-channel map marked split = 8; the
+    # cached f2g_split_f16x2_seq image of the combined weight (fused_disc._dgrad_weight3).  A key of its own: such a call
+    # is offered to no other route
+    _F16Route("FP16X3_TAPN3_MIN_ROWS", 0, "FP16X3_TAPN3_LAUNCHES",
+              lambda A, Bm, atomic, split_k, x3_out:
+              not atomic and split_k <= 1 and A.unit == 128 and A.cols == 256 and Bm.rows == 96 and not x3_out
+              and _f16_seq_window_ok(A),
+              (None, _f16_seq_operand), marks=(8, 0)),
 ), (0, 3): (
     # TAP3N, gemm_h3p3n_kernel: 5 positions of the fp32 32-channel map itself (K = 160), marked split = 8; wide epilogue
     _F16Route("FP16X3_TAP3N_MIN_ROWS", 0, "FP16X3_TAP3N_LAUNCHES",
@@ -1114,6 +1130,8 @@ def _fp16x3_route(d, A, Bm, out, form: int, atomic: bool, split_k: int, out_offs
         return None
     o = A if form == 0 else Bm
     shape = 0 if o.P0 == 1 and o.P1 == 1 else o.step0 if o.P1 == 1 and o.P0 > 1 else None
+    if d.E.col_fold or d.E.seq_live:
+        shape = "fold3" if shape == 1 else None
     tunables, sizes = globals(), (A.rows, Bm.rows)
     for r in _FP16X3_ROUTES.get((form, shape), ()):
         threshold, by_width, _, claims, _, (mark_a, mark_b), needs, wide = r
@@ -1619,6 +1637,15 @@ FP16X3_TAP3N_LAUNCHES = 0  # launches gemm_h3p3n_kernel took (tests and tools)
 # FP16X3_TAP_OFF = disabled (tests and the tool lower it; F2G_OPTS=fp16x3_tapn_min_rows=1 turns it on)
 FP16X3_TAPN_MIN_ROWS = opt("fp16x3_tapn_min_rows", FP16X3_TAP_OFF)
 FP16X3_TAPN_LAUNCHES = 0   # launches gemm_h3pn_kernel took (tests and tools)
+# F2G_GEMM=fp16x3: the fewest output rows, S * ceil(Hin / 3), at which the data gradient of the MPD's 32 -> 128 layer is
+# ONE launch of gemm_h3pn3_kernel (csrc/gemm_f16pn3.hip) instead of one per stride residue: all three residues read the
+# window [g[q], g[q + 1]] of the fp32 128-channel gradient map and write 96 consecutive floats of the 32-channel halo
+# map, so the map is read once instead of three times (fused_disc._conv1d_dgrad has the call, _dgrad_weight3 the
+# combined weight).  profiles/fp16x3_tapn3_shapes.txt (tools/fp16x3_tap_shapes.py --tapn3) has what was measured.  The
+# route ships off like the other tap-walking routes: FP16X3_TAP_OFF = disabled (tests and the tool lower it;
+# F2G_OPTS=fp16x3_tapn3_min_rows=1 turns it on)
+FP16X3_TAPN3_MIN_ROWS = opt("fp16x3_tapn3_min_rows", FP16X3_TAP_OFF)
+FP16X3_TAPN3_LAUNCHES = 0  # launches gemm_h3pn3_kernel took (tests and tools)
 # fewest reduction rows at which the weight gradient of a STRIDE-3 five-tap layer over a halo map with a multiple of 128
 # channels (the MPD's 128 -> 512 and 512 -> 1024 layers; ops.wgrad over unbounded windows) goes to gemm_h3ws_kernel:
 # the gradient and the whole map pay f2g_split_f16x2_cols per call, exactly as for the stride-1 route above, against

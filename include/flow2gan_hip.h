@@ -177,6 +177,18 @@ typedef struct {
    * atomics per column otherwise -- 13-24 % of those launches.  f2g_gemm refuses the descriptor (F2G_EINVAL)
    * when the kernel it would pick cannot do this. */
   int64_t colsum_part_ld;
+  /* The fold and the cut of the ONE-launch data gradient over three stride residues (precision 4, gemm_h3pn3_kernel,
+   * csrc/gemm_f16pn3.hip; f2g_split_f16x2_seq below has the route).  Both 0 = off: every descriptor that leaves them
+   * zero means what it meant before they existed.  A descriptor that sets either one is F2G_EINVAL at every other
+   * kernel, never run elsewhere, and f2g_gemm_f16_ok answers 0 for it unless it is exactly that kernel's shape.
+   * col_fold = 32: output column n stands for channel n % 32 -- the N = 96 columns are three rows of a 32-channel map
+   * side by side --, so `colsum` has col_fold entries and entry c receives the sum over the columns c, c + 32, c + 64.
+   * seq_live > 0: live floats per output sequence.  An element whose offset inside its sequence's row range,
+   * (r % P0o) * row_stride_o + n, is >= seq_live is neither stored nor summed: the last row of a sequence whose
+   * length is no multiple of 3 computes values for map rows behind the sequence's end, which would land in the zero
+   * halo rows. */
+  int32_t col_fold;
+  int64_t seq_live;
 } f2g_epilogue;
 
 /* form: 0 = C[r,n] = sum_k A[r,k] * B[n,k]   (forward; B = weights [n][k])
@@ -412,7 +424,26 @@ int f2g_split_f16x2_cols(float* dst, float* rscale, uint32_t* work, const float*
  * unit == 128, step0 == 1, cols == 128 or 256, P1 == 1, pad0 <= 0, seq_stride % unit == 0, L0u <= seq_stride, P0 >= 8
  * (at most 17 segments and 145 staged positions per tile), 1 <= N <= 32, alignment, extents, B's row stride and the
  * x6p option as above.  f2g_gemm_f16_ok answers 1 / 2 / 0 as above; f2g_gemm_colsum_part_rows answers 0 (no partial
- * rows).  f2g_gemm_last_kernel reports "h3pn<taps=2>" or "h3pn<taps=1>", path 6. */
+ * rows).  f2g_gemm_last_kernel reports "h3pn<taps=2>" or "h3pn<taps=1>", path 6.
+ * ALL THREE residues in ONE launch (gemm_h3pn3_kernel, csrc/gemm_f16pn3.hip): with k = 5, stride 3, pad 2 and Hout =
+ * ceil(Hin / 3), rows 3 q, 3 q + 1, 3 q + 2 of the 32-channel result all read the window [g[q], g[q + 1]] -- residue 0
+ * takes g[q] through tap 2, residue 1 g[q] through tap 3 and g[q + 1] through tap 0, residue 2 g[q] through tap 4 and
+ * g[q + 1] through tap 1 -- and are 96 consecutive floats of the halo map.  So the data gradient is one forward-form
+ * GEMM with M = S * Hout rows, K = 256 over stride-1 windows of two positions, N = 96 contiguous columns, against
+ * Wc[rho * 32 + ci][j * 128 + co] = w[co][ci][t(rho, j)], t = (2, -), (3, 0), (4, 1), the block (rho = 0, j = 1) zero
+ * (never multiplied).  A: the fp32 map marked split = 8, staged as above -- every position loaded, scaled per segment
+ * and split ONCE for all three residues, the gradient map read once instead of three times.  B: the
+ * f2g_split_f16x2_seq image of Wc (split = 7 with rscale, one scale per row).  Four waves per 128-row tile, each
+ * keeping ONE residue's weight fragments in registers for the block's life (residues 1 and 2 a wave each over all rows,
+ * residue 0 two waves over half the rows each).  v = (acc0 + 2^-11 acc1) * rscale_segment[row] * rscale_b[col], then
+ * the thin epilogue at the output's own address -- mask_src, fm_ref / fm_w / fm_wdev, mask_slope, colsum -- under
+ * E.col_fold = 32 and E.seq_live = 32 Hin (f2g_epilogue has both).  Error bound and reproducibility as for
+ * gemm_h3pn_kernel (colsum atomics the one exception).  Conditions: form 0, A.split == 8, unit == 128, step0 == 1,
+ * cols == 256, P1 == 1, pad0 <= 0, seq_stride % unit == 0, L0u <= seq_stride, P0 >= 8; N == 96, col_fold == 32, P0o ==
+ * A.P0, row_stride_o == 96, seq_live % 32 == 0, 96 (P0 - 1) < seq_live <= 96 P0; alignment, extents, B's row stride and
+ * the x6p option as above.  bias, lrelu_slope, aux, res, colsum_alpha, prelu_*, scale, atomic, accumulate, c_bf16,
+ * x3_out, colsum_part_ld > 0 and split_k > 1 are F2G_EINVAL.  f2g_gemm_f16_ok answers 1 with B's image, 2 with B still
+ * fp32, 0 otherwise; f2g_gemm_colsum_part_rows answers 0.  f2g_gemm_last_kernel reports "h3pn3", path 6. */
 int f2g_split_f16x2_seq(float* dst, float* rscale, const float* src, int64_t ld, int32_t nseq, int32_t seq_floats,
                         f2g_stream_t stream);
 

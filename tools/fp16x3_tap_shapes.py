@@ -48,8 +48,18 @@ them (gemm_x6n_kernel, which splits the fp32 map inside the kernel and pays no i
 the parent commit's).  Then the stage-2 step in the fp16x3 mode with that tunable alone differing, in three alternating
 pairs.
 
+--tapn3 measures that data gradient as ONE launch (gemm_h3pn3_kernel, ops.FP16X3_TAPN3_MIN_ROWS; default output
+profiles/fp16x3_tapn3_shapes.txt), every other route staying as shipped.  The shapes are the ten data gradients of the
+32 -> 128 layer that a stage-2 step issues at B = 64 and at B = 16, taken from the calls fused_disc._conv1d_dgrad
+receives while one step runs.  Per shape three legs alternate in one process, three blocks of 12 each: the three
+launches both modes run as shipped (gemm_x6n_kernel; below ops.X6F_TALL_ROWS rows the exact-fp32 kernel -- the row
+names the kernel), the three gemm_h3pn_kernel launches, the one
+gemm_h3pn3_kernel launch; per leg the median, the range of its blocks and the bytes of the gradient map read per
+second.  "wins" / "loses": beyond BOTH legs' ranges.  Then the stage-2 step in the fp16x3 mode with that tunable alone
+differing, in three alternating pairs.
+
     python tools/fp16x3_tap_shapes.py [--out profiles/fp16x3_tap_shapes.txt] [--append] [--no-shapes] [--no-steps]
-                                      [--min-rows R] [--tap3 | --tap3n | --tapn]
+                                      [--min-rows R] [--tap3 | --tap3n | --tapn | --tapn3]
 """
 import argparse
 import os
@@ -252,21 +262,29 @@ def shapes_table(ops, dev, say):
             "more than its spread" + ("" if lost else "; no launch the library accepts loses"))
 
 
-def steps_table(ops, dev, say, min_rows, steps=4, tap3=False, route="TAP3"):
+_MODEL = []     # (gan, logmel, sampling rate): built once per run
+
+
+def stage2_of(ops, dev, batch=B):
+    """the stage-2 step (D-step, then G-step; the weight images rebuilt as after an optimizer step) of mel_24k_base at
+    `batch` clips of 1 s, as a function"""
     import flow2gan_amd
     from flow2gan_amd import harness
     from flow2gan_amd.models.config import get_gan_config, get_generator_config
     from flow2gan_amd.models.gan import GAN
-    gcfg = get_generator_config("mel_24k_base")
-    sr = gcfg["sampling_rate"]
-    torch.manual_seed(1234)
-    gen = flow2gan_amd.MelAudioGenerator(**gcfg)
-    gen.branch_dropout = 0.0
-    gan = GAN(gen, **get_gan_config("gan_multi_scale_mel_recon")).to(dev)
-    logmel = flow2gan_amd.LogMelSpectrogram(sr, gcfg["mel_n_fft"], gcfg["mel_hop_length"], gcfg["n_mels"]).to(dev)
+    if not _MODEL:
+        gcfg = get_generator_config("mel_24k_base")
+        torch.manual_seed(1234)
+        gen = flow2gan_amd.MelAudioGenerator(**gcfg)
+        gen.branch_dropout = 0.0
+        gan = GAN(gen, **get_gan_config("gan_multi_scale_mel_recon")).to(dev)
+        logmel = flow2gan_amd.LogMelSpectrogram(gcfg["sampling_rate"], gcfg["mel_n_fft"], gcfg["mel_hop_length"],
+                                                gcfg["n_mels"]).to(dev)
+        _MODEL.extend((gan, logmel, gcfg["sampling_rate"]))
+    gan, logmel, sr = _MODEL
     g = torch.Generator().manual_seed(99)
-    audio = (0.1 * torch.randn(B, sr, generator=g)).clamp_(-1, 1).to(dev)
-    lens = torch.full((B,), sr, dtype=torch.int64)
+    audio = (0.1 * torch.randn(batch, sr, generator=g)).clamp_(-1, 1).to(dev)
+    lens = torch.full((batch,), sr, dtype=torch.int64)
     g_params, d_params = list(gan.generator.parameters()), list(gan.discriminator.parameters())
 
     def stage2():
@@ -277,6 +295,115 @@ def steps_table(ops, dev, say, min_rows, steps=4, tap3=False, route="TAP3"):
             loss.backward()
             ops.bump_weight_epoch(params)
             ops.rebuild_derived(params)
+    return stage2
+
+
+def traced_dgrads(ops, dev, batch):
+    """[(S, Hout, Hin)] of every data gradient of the 32 -> 128 layer that one stage-2 step at `batch` clips issues, in
+    order -- taken from the calls fused_disc._conv1d_dgrad receives, not restated here"""
+    from flow2gan_amd import fused_disc as FD
+    seen, real = [], FD._conv1d_dgrad
+
+    def watch(g_pre, S, Hout, Cout, w, stride, pad, Hin, **kw):
+        if (w.shape[2] * w.shape[3], stride, pad, w.shape[1], Cout) == (5, 3, 2, 32, 128):
+            seen.append((S, Hout, Hin))
+        return real(g_pre, S, Hout, Cout, w, stride, pad, Hin, **kw)
+    FD._conv1d_dgrad = watch
+    try:
+        stage2_of(ops, dev, batch)()
+        torch.cuda.synchronize()
+    finally:
+        FD._conv1d_dgrad = real
+    return seen
+
+
+def time_legs(legs, blocks=3, reps=12):
+    """{leg: [per-call microseconds, one entry per block]}, the legs alternating block by block; legs = [(name, enter,
+    fn)], enter() sets the leg's mode and tunables"""
+    per = {name: [] for name, _, _ in legs}
+    for name, enter, fn in legs:            # warm-up: code objects, weight images
+        enter()
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    for _ in range(blocks):
+        for name, enter, fn in legs:
+            enter()
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            for _ in range(reps):
+                fn()
+            e.record()
+            torch.cuda.synchronize()
+            per[name].append(s.elapsed_time(e) * 1e3 / reps)
+    return per
+
+
+def tapn3_table(ops, dev, say, min_rows):
+    """the data gradient of the 32 -> 128 layer at the shapes a stage-2 step issues it, three legs alternating in one
+    process, three blocks of 12 each: the three launches both modes run as shipped (leg "x6n": gemm_x6n_kernel from
+    ops.X6F_TALL_ROWS rows on, the exact-fp32 kernel below; the row names it), the three gemm_h3pn_kernel launches, the one gemm_h3pn3_kernel launch.  No mask, no column sums (as --tapn); the output map
+    is allocated and its halo zeroed outside the timed region"""
+    from flow2gan_amd import fused_disc as FD
+    Cin, Cout = FD.MPD_CH[1], FD.MPD_CH[2]
+    say("# per data gradient: median us of 3 alternating blocks of 12, min..max of the leg's blocks, and the bytes of the "
+        "gradient map the leg's launches read per second (TB/s; the README's streaming figure is 5.5-5.8) -- x6n and "
+        "h3pn read the map three times, h3pn3 once")
+    say("batch     S  Hout   Hin    rows   x6n_us  min..max         TB/s   h3pn_us  min..max         TB/s  h3pn3_us  "
+        "min..max         TB/s  h3pn3/x6n  verdict kernel of the x6n leg")
+    verdicts = []
+    for batch in (B, 16):
+        for S, Hout, Hin in traced_dgrads(ops, dev, batch):
+            g = torch.Generator().manual_seed(S + Hin)
+            gpre = FD._halo_rows(S, Hout, Cout, dev)
+            FD.unhalo(gpre, S, Hout).copy_((torch.randn(S, Hout, Cout, generator=g) * 1e-3).to(dev))
+            gx = FD._halo_rows(S, Hin, Cin, dev)
+            w = torch.nn.Parameter((torch.randn(Cout, Cin, 5, 1, generator=g) * (5 * Cin) ** -0.5).to(dev))
+            launches = [(FD._dgrad_weight(w, 3, j0, nt), (nt - 1) - e0 - FD.HALO, nt, Lq,
+                         (Lq, (Hin + 2 * FD.HALO) * Cin, 3 * Cin, (FD.HALO + rho) * Cin))
+                        for rho, j0, nt, e0, Lq in FD._residues(5, 3, 2, Hin) if Lq]
+
+            def three(S=S, Hout=Hout, gpre=gpre, gx=gx, launches=launches):
+                for wq, pad, nt, Lq, rm in launches:
+                    ops.gemm(ops.win1d(gpre, S, Hout + 2 * FD.HALO, Cout, Lq, 1, pad, nt), ops.mat(wq), gx, rowmap=rm)
+
+            def one(S=S, Hout=Hout, Hin=Hin, gpre=gpre, gx=gx, w=w):
+                assert FD._conv1d_dgrad3(gpre, S, Hout, Cout, w, Hin, gx, None, None, None)
+
+            def enter(mode, tapn, tapn3):
+                def go():
+                    ops.set_gemm_precision(mode)
+                    ops.FP16X3_TAPN_MIN_ROWS, ops.FP16X3_TAPN3_MIN_ROWS = tapn, tapn3
+                return go
+            legs = [("x6n", enter("bf16x6", ops.FP16X3_TAP_OFF, ops.FP16X3_TAP_OFF), three),
+                    ("h3pn", enter("fp16x3", min_rows, ops.FP16X3_TAP_OFF), three),
+                    ("h3pn3", enter("fp16x3", ops.FP16X3_TAP_OFF, min_rows), one)]
+            kern = {}
+            for name, go, fn in legs:           # (which kernel each leg really runs)
+                go(), fn()
+                kern[name] = ops.L.lib.f2g_gemm_last_kernel().decode()
+            # (the first leg is whatever the bf16x6 mode launches: gemm_x6n_kernel from ops.X6F_TALL_ROWS rows on, the
+            # exact-fp32 kernels below -- the row names it)
+            assert kern["h3pn"].startswith("h3pn<") and kern["h3pn3"] == "h3pn3", kern
+            per = time_legs(legs)
+            read3 = sum(S * (l[3] + l[2] - 1) for l in launches) * Cout * 4
+            read1 = S * (Hout + 1) * Cout * 4
+            cols, med = "", {}
+            for name, nbytes in (("x6n", read3), ("h3pn", read3), ("h3pn3", read1)):
+                m = med[name] = med_spread(per[name])[0]
+                cols += f" {m:8.1f}  {min(per[name]):6.1f}..{max(per[name]):6.1f}  {nbytes / m * 1e-6:7.2f} "
+            lo, hi = (min(per["h3pn3"]), max(per["h3pn3"])), (min(per["x6n"]), max(per["x6n"]))
+            verdict = "wins" if lo[1] < hi[0] else ("loses" if lo[0] > hi[1] else "inside")
+            verdicts.append(verdict)
+            say(f"{batch:5d} {S:5d} {Hout:5d} {Hin:5d} {S * Hout:7d} {cols} {med['h3pn3'] / med['x6n']:8.3f}  {verdict:7s} {kern['x6n']}")
+            del gpre, gx
+            torch.cuda.empty_cache()
+    say(f"# data gradients: {len(verdicts)}; h3pn3 against the three x6n launches, beyond both legs' ranges: wins "
+        f"{verdicts.count('wins')}, loses {verdicts.count('loses')}, inside {verdicts.count('inside')}")
+
+
+def steps_table(ops, dev, say, min_rows, steps=4, tap3=False, route="TAP3"):
+    stage2 = stage2_of(ops, dev)
 
     legs = (("bf16x6", "bf16x6", ops.FP16X3_TAP_OFF), ("fp16x3 route off", "fp16x3", ops.FP16X3_TAP_OFF),
             ("fp16x3 route on", "fp16x3", min_rows))
@@ -332,23 +459,24 @@ def main():
     ap.add_argument("--tap3", action="store_true", help="measure the stride-3 route (legs fwd3 / fwd4) instead")
     ap.add_argument("--tap3n", action="store_true", help="measure the 32-channel stride-3 route (legs fwd2 / fwd2-) instead")
     ap.add_argument("--tapn", action="store_true", help="measure the route of the 32 -> 128 layer's residue data gradients (leg dgrad2) instead")
+    ap.add_argument("--tapn3", action="store_true", help="measure that data gradient as ONE launch over its three residues instead")
     ap.add_argument("--append", action="store_true", help="add this run's table to --out instead of replacing it")
     ap.add_argument("--no-steps", action="store_true")
     ap.add_argument("--no-shapes", action="store_true")
     ap.add_argument("--min-rows", type=int, default=1, help="ops.FP16X3_TAP_MIN_ROWS for this run (1: every launch "
                     "of the table on the new kernel)")
     args = ap.parse_args()
-    if args.tap3 + args.tap3n + args.tapn > 1:
-        ap.error("--tap3, --tap3n and --tapn are separate runs")
+    if args.tap3 + args.tap3n + args.tapn + args.tapn3 > 1:
+        ap.error("--tap3, --tap3n, --tapn and --tapn3 are separate runs")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "fp16x3_tapn_shapes.txt" if args.tapn else "fp16x3_tap3n_shapes.txt" if args.tap3n else (
+        args.out = os.path.join(ROOT, "profiles", "fp16x3_tapn3_shapes.txt" if args.tapn3 else "fp16x3_tapn_shapes.txt" if args.tapn else "fp16x3_tap3n_shapes.txt" if args.tap3n else (
             "fp16x3_tap3_shapes.txt" if args.tap3 else "fp16x3_tap_shapes.txt"))
     assert torch.cuda.is_available(), "needs an MI355X"
     from flow2gan_amd import ops
     if args.min_rows < 1 or args.min_rows >= ops.FP16X3_TAP_OFF:
         ap.error("--min-rows must enable the route: both modes would time the same bf16x6 launch otherwise")
     was_rows, was_rows3, was_rows3n = ops.FP16X3_TAP_MIN_ROWS, ops.FP16X3_TAP3_MIN_ROWS, ops.FP16X3_TAP3N_MIN_ROWS
-    was_rowsn = ops.FP16X3_TAPN_MIN_ROWS
+    was_rowsn, was_rowsn3 = ops.FP16X3_TAPN_MIN_ROWS, ops.FP16X3_TAPN3_MIN_ROWS
     dev = torch.device("cuda")
     lines = []
 
@@ -359,19 +487,24 @@ def main():
     given = [a for i, a in enumerate(sys.argv[1:], 1) if a != "--out" and sys.argv[i - 1] != "--out"]
     say("# command (the output path aside): python tools/fp16x3_tap_shapes.py " + " ".join(given))
     say(f"# tools/fp16x3_tap_shapes.py  {ops.L.version()}  "
-        + (f"FP16X3_TAPN_MIN_ROWS={args.min_rows} FP16X3_TAP3N_MIN_ROWS={was_rows3n} FP16X3_TAP3_MIN_ROWS={was_rows3} "
+        + (f"FP16X3_TAPN3_MIN_ROWS={args.min_rows} FP16X3_TAPN_MIN_ROWS={was_rowsn} FP16X3_TAP3N_MIN_ROWS={was_rows3n} "
+           f"FP16X3_TAP3_MIN_ROWS={was_rows3} FP16X3_TAP_MIN_ROWS={was_rows} " if args.tapn3 else
+           f"FP16X3_TAPN_MIN_ROWS={args.min_rows} FP16X3_TAP3N_MIN_ROWS={was_rows3n} FP16X3_TAP3_MIN_ROWS={was_rows3} "
            f"FP16X3_TAP_MIN_ROWS={was_rows} " if args.tapn else
            f"FP16X3_TAP3N_MIN_ROWS={args.min_rows} FP16X3_TAP3_MIN_ROWS={was_rows3} FP16X3_TAP_MIN_ROWS={was_rows} "
            if args.tap3n else
            f"FP16X3_TAP3_MIN_ROWS={args.min_rows} FP16X3_TAP_MIN_ROWS={was_rows} " if args.tap3 else
            f"FP16X3_TAP_MIN_ROWS={args.min_rows} ") + f"X6_MIN_K={ops.X6_MIN_K}  {torch.cuda.get_device_name(0)}")
-    say("# per-launch medians of 5 alternating blocks of 12 launches (us), "
-        + ("the fp16x3 leg has no image pass (the kernel scales the fp32 map itself)" if args.tap3n or args.tapn else
-           "the map's image pass included in the fp16x3 leg") + "; spread = (max - min) / median of a mode's blocks; ratio = fp16x3 / bf16x6 (< 1: fp16x3 faster)")
+    if not args.tapn3:      # (--tapn3 has three legs and states its own method above its table)
+        say("# per-launch medians of 5 alternating blocks of 12 launches (us), "
+            + ("the fp16x3 leg has no image pass (the kernel scales the fp32 map itself)" if args.tap3n or args.tapn else
+               "the map's image pass included in the fp16x3 leg") + "; spread = (max - min) / median of a mode's blocks; ratio = fp16x3 / bf16x6 (< 1: fp16x3 faster)")
     from test_hip_gemm_f16 import mode_name       # (the one place that names the mode in force)
     was = mode_name(ops)
     try:
-        if not args.no_shapes and args.tapn:
+        if not args.no_shapes and args.tapn3:
+            tapn3_table(ops, dev, say, args.min_rows)
+        elif not args.no_shapes and args.tapn:
             ops.FP16X3_TAPN_MIN_ROWS = args.min_rows
             shapes3_table(ops, dev, say, "FP16X3_TAPN_LAUNCHES", casesn, ((B, PERIODS), (16, PERIODS)))
         elif not args.no_shapes and args.tap3n:
@@ -384,11 +517,11 @@ def main():
             ops.FP16X3_TAP_MIN_ROWS = args.min_rows
             shapes_table(ops, dev, say)
         if not args.no_steps:
-            steps_table(ops, dev, say, args.min_rows, tap3=args.tap3 or args.tap3n or args.tapn,
-                        route="TAPN" if args.tapn else ("TAP3N" if args.tap3n else "TAP3"))
+            steps_table(ops, dev, say, args.min_rows, tap3=args.tap3 or args.tap3n or args.tapn or args.tapn3,
+                        route="TAPN3" if args.tapn3 else "TAPN" if args.tapn else ("TAP3N" if args.tap3n else "TAP3"))
     finally:
         ops.FP16X3_TAP_MIN_ROWS, ops.FP16X3_TAP3_MIN_ROWS, ops.FP16X3_TAP3N_MIN_ROWS = was_rows, was_rows3, was_rows3n
-        ops.FP16X3_TAPN_MIN_ROWS = was_rowsn
+        ops.FP16X3_TAPN_MIN_ROWS, ops.FP16X3_TAPN3_MIN_ROWS = was_rowsn, was_rowsn3
         ops.set_gemm_precision(was)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "a" if args.append else "w") as f:
