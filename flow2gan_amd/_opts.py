@@ -16,6 +16,9 @@ x6_min_k, x6_min_rows, x6_nopass_k, x6f_min_k, x6f_min_n, x6f_min_tiles, x6f_tal
 fp16x3_plainn_min_n (the fewest output columns at which such a GEMM takes the fp16x3 kernel that reads the fp32
 activation matrix itself and scales it per 128-row tile inside the kernel, without an image pass; off by default),
 fp16x3_wgrad_min_rows (the fewest reduction rows at which a weight gradient takes the fp16x3 weight-gradient kernel),
+fp16x3_wgradn_min_rows (the fewest reduction rows at which such a weight gradient takes the fp16x3 kernel that reads
+both fp32 activation matrices themselves and scales each under one running scale per block inside the kernel, without
+an image pass; tried behind fp16x3_wgrad_min_rows' image route; off by default),
 fp16x3_tap_min_rows (the fewest output rows at which a GEMM over stride-1 windows of a halo map takes the fp16x3
 tap-walking kernel; the route also asks for a reduction of at least x6_min_k, i.e. the launches the bf16x6 mode gives
 to its image kernels), fp16x3_tapw_min_rows (the fewest reduction rows at which the weight gradient of a stride-1

@@ -902,9 +902,9 @@ extern "C" int f2g_gemm(const f2g_gemm_desc* dp, f2g_stream_t stream) {
     f2g_set_error("f2g_gemm: E.col_fold / E.seq_live belong to gemm_h3pn3_kernel (precision 4), never run elsewhere");
     return F2G_EINVAL;
   }
-  if ((d.A.split >= 5 && d.A.split <= 9) || (d.B.split >= 5 && d.B.split <= 9)) {
+  if ((d.A.split >= 5 && d.A.split <= 10) || (d.B.split >= 5 && d.B.split <= 10)) {
     f2g_set_error("f2g_gemm: f2g_split_f16x2 / _cols / _seq images (split = 5 / 6 / 7) and maps or matrices scaled "
-                  "inside the kernel (split = 8 / 9) belong to precision 4");
+                  "inside the kernel (split = 8 / 9 / 10) belong to precision 4");
     return F2G_EINVAL;
   }
   if (d.precision == 3 && d.form == 2) {

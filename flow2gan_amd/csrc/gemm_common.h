@@ -45,6 +45,8 @@ int f2g_launch_h3ws(const f2g_gemm_desc& d, hipStream_t st);
 int f2g_h3wsn_ok(const f2g_gemm_desc& d);      // ... over 32 channels, both fp32 operands marked split = 8 (1 or 0)
 int f2g_launch_h3wsn(const f2g_gemm_desc& d, hipStream_t st);
 int f2g_launch_h3n(const f2g_gemm_desc& d, hipStream_t st);      // form 0, plain fp32 A marked split = 9 (h3_plain_ok)
+int f2g_h3wn_ok(const f2g_gemm_desc& d);       // form 2, two plain fp32 matrices both marked split = 10 (1 or 0)
+int f2g_launch_h3wn(const f2g_gemm_desc& d, hipStream_t st);
 
 // ---- lab switches (product builds: both 0) ---------------------------------------------------------------------
 // F2G_LABVAR (tools/micro/build_variants.sh; timing only): ablations of the bf16 lean K loop (gemm_lean.hip) --

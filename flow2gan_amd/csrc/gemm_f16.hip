@@ -349,15 +349,6 @@ inline bool h3_operand_ok(const f2g_operand& S) {
          h3_fits31((long long)S.rows * S.seq_stride);
 }
 
-// form 2 (weight gradient): what gemm_leanw6_kernel<false> takes for two plain operands, with partial tiles (any
-// M, N that are multiples of 4) and without a bf16 output
-inline bool h3w_operand_ok(const f2g_operand& S) {
-  return host_plain(S) && !S.alpha && S.rows > 0 && S.cols >= 4 && S.cols % 4 == 0 && al16(S.base) &&
-         (S.seq_stride & 3) == 0 && S.seq_stride >= S.cols &&
-         // (the kernel's 32-bit byte offsets reach one slab of 32 rows past the last row: they must not wrap)
-         h3_fits31(((long long)S.rows + 32) * S.seq_stride);
-}
-
 // gemm_h3_kernel, and gemm_h3n_kernel (gemm_f16n.hip) where A is marked split = 9 -- the fp32 matrix itself, scaled
 // per row tile inside the kernel: the same conditions, A without rscale, and the answer follows B alone
 int h3_plain_ok(const f2g_gemm_desc& d) {
@@ -406,7 +397,7 @@ int f2g_launch_h3w(const f2g_gemm_desc& d, hipStream_t st) {
 // test of the descriptor's form, marks and operand shapes alone -- is the descriptor's candidate, and that kernel's own
 // conditions (`ok`) decide.  Nothing else is asked: a descriptor one kernel declines is never offered to another.  So
 // the order is part of the rule -- the epilogue fields only one kernel knows (E.col_fold / E.seq_live) in front of
-// everything, the marked operands (split = 8 / 9: fp32, scaled inside the kernel) in front of the shapes, a windows' stride 3 in front of "any stride", the plain kernels of each form last.
+// everything, the marked operands (split = 8 / 9 / 10: fp32, scaled inside the kernel) in front of the shapes, a windows' stride 3 in front of "any stride", the plain kernels of each form last.
 // `ok` answers f2g_gemm_f16_ok: 0 = not for this kernel, 1 = runs as handed over (the operands the kernel's images
 // with their reciprocal scales, or marked fp32), 2 = once the fp32 operands are replaced by those images.
 // `part_tile`: the tile height the kernel's wide epilogue counts partial column sums in, one row per 64 output rows of
@@ -434,6 +425,11 @@ const h3_entry h3_table[] = {
      f2g_launch_h3wsn, 0,
      "form 2 + atomic over a plain fp32 matrix of 128 columns and the fp32 map under unbounded stride-3 windows of 5 "
      "positions over 32 channels, both marked split = 8 without rscale"},
+    // H3_WGRADN, gemm_h3wn_kernel (gemm_f16wn.hip): BOTH marks (split = 10; 9 is H3_PLAINN's mark on A at form 0 and
+    // keeps answering 0 at form 2); a descriptor with one operand marked stays with H3_WGRAD below, which declines it
+    {[](const f2g_gemm_desc& d) { return h3_form2_p4(d) && d.A.split == 10 && d.B.split == 10; }, f2g_h3wn_ok,
+     f2g_launch_h3wn, 0,
+     "form 2 over two plain fp32 matrices themselves, both marked split = 10 without rscale"},
     // H3_TAPW3, gemm_h3ws_kernel (gemm_f16ws.hip)
     {[](const f2g_gemm_desc& d) { return h3_tapw_shape(d) && d.B.step0 == 3; }, f2g_h3ws_ok, f2g_launch_h3ws, 0,
      "form 2 + atomic over f2g_split_f16x2_cols images of a plain matrix and of the map under unbounded stride-3 "

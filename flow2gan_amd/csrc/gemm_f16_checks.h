@@ -19,6 +19,16 @@ inline int f16_b_image_status(const f2g_operand& B, int split) {
   return B.split == 0 ? 2 : 0;
 }
 
+// form 2 (weight gradient) over two plain K-major matrices (gemm_h3w_kernel, gemm_f16.hip, and gemm_h3wn_kernel,
+// gemm_f16wn.hip): what gemm_leanw6_kernel<false> takes for two plain operands, with partial tiles (any M, N that are
+// multiples of 4) and without a bf16 output
+inline bool h3w_operand_ok(const f2g_operand& S) {
+  return host_plain(S) && !S.alpha && S.rows > 0 && S.cols >= 4 && S.cols % 4 == 0 && al16(S.base) &&
+         (S.seq_stride & 3) == 0 && S.seq_stride >= S.cols &&
+         // (the kernel's 32-bit byte offsets reach one slab of 32 rows past the last row: they must not wrap)
+         h3_fits31(((long long)S.rows + 32) * S.seq_stride);
+}
+
 // ---- form 0 over windows of a halo map (A) against a plain matrix (B) ------------------------------------------
 // Everything but the window geometry: gemm_x6p_kernel's switch and grid rule on the kernel's tiles (tile_rows x
 // tile_cols; tile_cols == 0: the blocks walk row tiles of every column), 32-bit byte extents, whole slabs and 16-byte

@@ -3,6 +3,8 @@
 // rescaling the two accumulator sets.  What a
 // kernel stages and where its fragments and scales lie stay with the kernel.  Internal linkage throughout.
 #pragma once
+#include <type_traits>
+
 #include "gemm_common.h"
 
 namespace {
@@ -45,6 +47,27 @@ __device__ __forceinline__ void h3_mfma12(f32x16 (&acc)[2][2], f32x16 (&acx)[2][
     for (int mi = 0; mi < 2; ++mi)
 #pragma unroll
       for (int ni = 0; ni < 2; ++ni) h3_term(term, acc[mi][ni], acx[mi][ni], ah[mi], al[mi], bh[ni], bl[ni]);
+}
+
+// Largest m of a wave's 64 lanes as a wave-uniform value, WITHOUT an LDS round trip (split_f16.h's f2g_wave_max is six
+// dependent ds_bpermute: several hundred cycles that would sit between a slab's last MFMA and its barrier): four DPP
+// steps inside every row of 16 lanes (the two quad permutations, the half-row and the row mirror: after them every
+// lane holds its row's maximum), then the four rows through v_readlane and scalar maxima.  Every lane is active where
+// this is called.  The same order-free integer maximum: reproducible.  (gemm_h3n_kernel, gemm_h3wn_kernel: the slab
+// maxima of the operands they scale themselves)
+__device__ __forceinline__ unsigned h3n_wave_max(unsigned m) {
+  auto step = [&](auto ctrl) {
+    const unsigned t = (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, decltype(ctrl)::value, 0xf, 0xf, false);
+    m = m > t ? m : t;
+  };
+  step(std::integral_constant<int, 0xB1>{});      // quad_perm [1, 0, 3, 2]
+  step(std::integral_constant<int, 0x4E>{});      // quad_perm [2, 3, 0, 1]
+  step(std::integral_constant<int, 0x141>{});     // row_half_mirror
+  step(std::integral_constant<int, 0x140>{});     // row_mirror
+  const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)m, 0), b = (unsigned)__builtin_amdgcn_readlane((int)m, 16);
+  const unsigned c = (unsigned)__builtin_amdgcn_readlane((int)m, 32), e = (unsigned)__builtin_amdgcn_readlane((int)m, 48);
+  const unsigned ab = a > b ? a : b, ce = c > e ? c : e;
+  return ab > ce ? ab : ce;
 }
 
 // Both accumulator sets of N tiles to zero

@@ -41,8 +41,6 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#include <type_traits>
-
 #include "gemm_f16_common.h"
 #include "split_f16.h"
 
@@ -50,26 +48,6 @@ namespace {
 
 __device__ __forceinline__ float4 h3n_f4(const u32x4 v) {
   return make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
-}
-
-// Largest m of a wave's 64 lanes as a wave-uniform value, WITHOUT an LDS round trip (split_f16.h's f2g_wave_max is six
-// dependent ds_bpermute: several hundred cycles that would sit between a slab's last MFMA and its barrier): four DPP
-// steps inside every row of 16 lanes (the two quad permutations, the half-row and the row mirror: after them every
-// lane holds its row's maximum), then the four rows through v_readlane and scalar maxima.  Every lane is active where
-// this is called.  The same order-free integer maximum: reproducible.
-__device__ __forceinline__ unsigned h3n_wave_max(unsigned m) {
-  auto step = [&](auto ctrl) {
-    const unsigned t = (unsigned)__builtin_amdgcn_update_dpp(0, (int)m, decltype(ctrl)::value, 0xf, 0xf, false);
-    m = m > t ? m : t;
-  };
-  step(std::integral_constant<int, 0xB1>{});      // quad_perm [1, 0, 3, 2]
-  step(std::integral_constant<int, 0x4E>{});      // quad_perm [2, 3, 0, 1]
-  step(std::integral_constant<int, 0x141>{});     // row_half_mirror
-  step(std::integral_constant<int, 0x140>{});     // row_mirror
-  const unsigned a = (unsigned)__builtin_amdgcn_readlane((int)m, 0), b = (unsigned)__builtin_amdgcn_readlane((int)m, 16);
-  const unsigned c = (unsigned)__builtin_amdgcn_readlane((int)m, 32), e = (unsigned)__builtin_amdgcn_readlane((int)m, 48);
-  const unsigned ab = a > b ? a : b, ce = c > e ? c : e;
-  return ab > ce ? ab : ce;
 }
 
 __global__ __launch_bounds__(256, 2) void gemm_h3n_kernel(const f2g_gemm_desc d, int M, int N, int K) {

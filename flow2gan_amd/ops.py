@@ -1030,7 +1030,7 @@ class _F16Route(NamedTuple):
     counter: str
     claims: Callable        # (A, Bm, atomic, split_k, x3_out) -> bool: what the Python side requires of the call
     images: tuple           # per operand: the builder of the fp16 image the kernel reads, None = the fp32 operand
-    marks: tuple = (0, 0)   # Operand.split of d.A / d.B while the library is asked: 8 / 9 = scaled inside the kernel
+    marks: tuple = (0, 0)   # Operand.split of d.A / d.B while the library is asked: 8 / 9 / 10 = scaled inside the kernel
     needs: int = 2          # f2g_gemm_f16_ok's answer: 2 = runs once the images are made, 1 = as it is (no image)
     x3_out: bool = False    # wide epilogue: asked through _ask_with_x3_out, the output's three-piece image is written
 
@@ -1042,7 +1042,11 @@ class _F16Route(NamedTuple):
 # behaviour: the route that reads the fp32 operand itself (no image pass, nothing allocated per call) stands in front of
 # the image route over the same shapes -- PLAINN before PLAIN, TAPN before TAP (two-tap windows over 128 channels),
 # TAP3N before TAP3, TAPW3N before TAPW3 -- and what its kernel declines falls through to the image route with the marks
-# cleared.
+# cleared.  ONE EXCEPTION: WGRADN stands BEHIND WGRAD under (2, 0).  Both ship off; what the no-image route takes is a
+# subset of what the image route takes (the same Python predicate, and f2g_h3wn_ok's conditions are h3w_ok's apart from
+# the marks), so with both thresholds reached the image route wins and the recorded decisions of
+# tests/golden/fp16x3_route_answers.json (every threshold at 1) stay as they are; with fp16x3_wgrad_min_rows at its
+# shipped "off", fp16x3_wgradn_min_rows alone opens WGRADN.
 _FP16X3_ROUTES = {(0, 0): (
     # PLAINN, gemm_h3n_kernel: the fp32 activation matrix itself, marked split = 9; the weight's cached image
     _F16Route("FP16X3_PLAINN_MIN_N", 1, "FP16X3_PLAINN_LAUNCHES",
@@ -1095,6 +1099,11 @@ _FP16X3_ROUTES = {(0, 0): (
     _F16Route("FP16X3_WGRAD_MIN_ROWS", 0, "FP16X3_WGRAD_LAUNCHES",
               lambda A, Bm, atomic, split_k, x3_out: atomic and A.lrelu_src is None,
               (_f16_cols_operand, _f16_cols_operand)),
+    # WGRADN, gemm_h3wn_kernel: the same two matrices read as fp32, both marked split = 10.  No images: the library
+    # answers 1 or 0 (there is nothing to make first), nothing is allocated per call.  Behind WGRAD (see above)
+    _F16Route("FP16X3_WGRADN_MIN_ROWS", 0, "FP16X3_WGRADN_LAUNCHES",
+              lambda A, Bm, atomic, split_k, x3_out: atomic and A.lrelu_src is None,
+              (None, None), marks=(10, 10), needs=1),
 ), (2, 3): (
     # TAPW3N, gemm_h3wsn_kernel: 128 gradient columns against 32 channels, both fp32 operands marked split = 8.  No
     # images: the library answers 1 or 0 (there is nothing to make first)
@@ -1600,6 +1609,18 @@ FP16X3_TAP_LAUNCHES = 0    # launches gemm_h3p_kernel took (tests and tools)
 # F2G_OPTS=fp16x3_plainn_min_n=1 turns it on for every pointwise shape)
 FP16X3_PLAINN_MIN_N = opt("fp16x3_plainn_min_n", FP16X3_TAP_OFF)
 FP16X3_PLAINN_LAUNCHES = 0  # launches gemm_h3n_kernel took (tests and tools)
+# F2G_GEMM=fp16x3: the fewest reduction rows at which a weight gradient over two plain activation matrices takes
+# gemm_h3wn_kernel (csrc/gemm_f16wn.hip) -- gemm_h3w_kernel reading both fp32 matrices as they are (4 bytes per element,
+# as gemm_leanw6_kernel), each scaled under one running scale per block and split INSIDE the kernel: no image pass, no
+# allocation per call.  The route is tried BEHIND the image route (FP16X3_WGRAD_MIN_ROWS above; _FP16X3_ROUTES has why),
+# which ships off, so this tunable alone opens it.  profiles/fp16x3_wgrad_noimage_shapes.txt (tools/fp16x3_wgrad_shapes.py
+# --noimage) has what was measured, three legs alternating over the 18 shapes on one box: against the image route all 18
+# win beyond the spread (0.474-0.827 of its time); against bf16x6 6 win, none loses, all 18 at 0.866-1.001; stage 1
+# 31.27 -> 30.46 ms with the tunable alone differing (74 launches per step), outside both legs' ranges, stage 2 inside
+# them.  The route ships off whatever that file says -- turning it on is a change of its
+# own: FP16X3_TAP_OFF = disabled (tests and the tool lower it; F2G_OPTS=fp16x3_wgradn_min_rows=1 turns it on).
+FP16X3_WGRADN_MIN_ROWS = opt("fp16x3_wgradn_min_rows", FP16X3_TAP_OFF)
+FP16X3_WGRADN_LAUNCHES = 0  # launches gemm_h3wn_kernel took (tests and tools)
 # fewest reduction rows at which the weight gradient of a stride-1 five-tap layer over a halo map (the MPD's
 # 1024-channel layer; ops.wgrad over unbounded windows) goes to gemm_h3wt_kernel: the gradient and the whole map pay
 # f2g_split_f16x2_cols per call (two reads and one write each: 12 bytes per element), against gemm_leanw6t_kernel's

@@ -105,7 +105,14 @@ typedef struct {
    * 9: (operand A of a precision-4, form-0 launch over a PLAIN matrix only) `base` is the fp32 matrix ITSELF, as for
    *    split = 0, `rscale` must be NULL, and the mark says: scale it per 128-row tile and split it inside the kernel
    *    (gemm_h3n_kernel; f2g_split_f16x2 below has it).  Operand B is the weight's f2g_split_f16x2 image (split = 5
-   *    with rscale).  A descriptor so marked that fails a condition of the kernel is F2G_EINVAL, never run elsewhere */
+   *    with rscale).
+   *    At form 2 the mark means nothing: f2g_gemm_f16_ok answers 0 with it on one operand or on both.
+   *    A descriptor so marked that fails a condition of the kernel is F2G_EINVAL, never run elsewhere;
+   * 10: (BOTH operands of a precision-4, FORM-2 launch over two PLAIN matrices) `base` is the fp32 K-major matrix
+   *    ITSELF, as for split = 0, `rscale` must be NULL on both, and the mark says: the weight gradient with each operand
+   *    scaled under one running scale per block and split inside the kernel (gemm_h3wn_kernel; f2g_split_f16x2_cols
+   *    below has it).  There are no images.  With only one operand so marked f2g_gemm_f16_ok answers 0.
+   *    A descriptor so marked that fails a condition of its kernel is F2G_EINVAL, never run elsewhere */
   int32_t split;
   const float* alpha;
   const float* lrelu_src;
@@ -221,6 +228,8 @@ typedef struct {
    *     tile and split inside the kernel) against B's f2g_split_f16x2 image;
    *     form 2 (weight gradient) over two plain matrices, both given as f2g_split_f16x2_cols images
    *     (split = 6 with rscale: one scale per column, which leaves the sum over rows), E.atomic when split_k > 1;
+   *     form 2 over the two plain fp32 matrices themselves, both marked split = 10 without rscale (each scaled under one
+   *     running scale per block and split inside the kernel), E.atomic when split_k > 1;
    *     form 2 with E.atomic over a plain matrix A and unbounded stride-1 windows B of 5 positions of a halo map (the
    *     taps shift ROWS of the map, so one scale per column of the whole map leaves every tap's sum), both given as
    *     f2g_split_f16x2_cols images (split = 6 with rscale);
@@ -333,6 +342,24 @@ int f2g_gemm_f16_ok(const f2g_gemm_desc* d);
  * rescale is linear: partial tiles are rescaled, then added), no window operand, no bf16 output, no x3_out, no
  * colsum_part_ld.  f2g_gemm_f16_ok answers for form 2 as for form 0 (2 = once both fp32 operands are replaced by
  * their column images), asked with precision = 4 set as for the launch: 0 at any other precision.  f2g_gemm_last_kernel reports "h3w".
+ * WITHOUT IMAGES (gemm_h3wn_kernel, csrc/gemm_f16wn.hip): both operands the plain fp32 matrices themselves, both
+ * marked split = 10 with rscale == NULL; the other conditions and the epilogue as above (equal rows, cols % 4 == 0,
+ * ld % 4 == 0, ld >= cols, 16-byte aligned bases, (rows + 32) * ld * 4 < 0x7ff00000, no `alpha`, no `lrelu_src`, no
+ * window operand; split_k > 1 with E.atomic only, no bf16 output, no x3_out, no colsum_part_ld, no prelu_slope, no
+ * mask_src, aux only with alpha_n).  The kernel is the one above with the split moved to where a staged chunk goes to
+ * LDS: every block -- a 128 x 128 output tile and one chunk of the K split -- keeps ONE MONOTONE RUNNING SCALE PER
+ * OPERAND: m_run = 0 (scale 1) at the block's first slab of 32 reduction rows; before slab T is split m_run =
+ * max(m_run, m_T) over the slab's floats of the tile's 128 columns that lie inside the matrix, a slab whose maximum is
+ * zero or not finite leaving it alone (its finite floats are split at the scale in force); s = 2^(14 - floor(log2
+ * m_run)) as for a column above; the stored sums follow every change of either scale by an exact power of two, and
+ * v = (acc0 + 2^-11 acc1) / s_a / s_b.  Error per output: 3 * 2^-22 sum_r |a||b| + 2^-28 sum_T (brun_T sum_{r in T} |a|
+ * + arun_T sum_{r in T} |b|) with arun_T / brun_T the running maxima in force at slab T: columns share their tile's
+ * scale, so a column quiet against its tile sees the second term, which the per-column scale of the image spares it.
+ * An inf or NaN in A[r, m] stays in output row m, one in B[r, n] in column n.  A block's contribution is reproducible
+ * (integer maxima, no atomics inside it).  4 bytes of HBM traffic per element, nothing allocated, no scratch words.
+ * f2g_gemm_f16_ok answers 1 for what the kernel runs and 0 for anything it declines -- never 2: there is nothing to
+ * make first -- and 0, as before, with only one operand marked; f2g_gemm_colsum_part_rows answers 0.
+ * f2g_gemm_last_kernel reports "h3wn", path 6, with the split factor.
  * ONE window operand is taken, the tap-walking weight gradient gw[co][t * unit + ci] += sum_r g[r][co] x[r + t -
  * pad0][ci] of a stride-1 five-tap layer (gemm_h3wt_kernel, what gemm_leanw6t_kernel runs at precision 3): A plain
  * with cols % 128 == 0; B with step0 == 1, P1 == 1, cols == 5 * unit, unit % 128 == 0, unbounded, seq_stride == P0 *
@@ -454,7 +481,7 @@ int f2g_split_f16x2_seq(float* dst, float* rscale, const float* src, int64_t ld,
 int f2g_gemm_last_path(void);
 /* Kernel instance the last f2g_gemm call launched (tests and diagnostics, not thread safe; "" when it
  * launched nothing), e.g. "lean<sk=1,ep=3,pm=0>" (lean kernel: stream-K, epilogue instance, operand mode),
- * "lean_tall<ep=2,pm=1>", "lean_tap<ep=3>", "narrow_wgrad4<4>", "x6f<wimg=1>", "h3<ep=all>", "h3n<ep=all>", "h3w", "h3p<taps=5>" or "generic<F1,GF,PF> split=3"
+ * "lean_tall<ep=2,pm=1>", "lean_tap<ep=3>", "narrow_wgrad4<4>", "x6f<wimg=1>", "h3<ep=all>", "h3n<ep=all>", "h3w", "h3wn", "h3p<taps=5>" or "generic<F1,GF,PF> split=3"
  * (generic MFMA tiles: form, loader modes of A and B, and the K split when > 1). */
 const char* f2g_gemm_last_kernel(void);
 
