@@ -19,9 +19,8 @@ import torch
 import torch.nn.functional as F
 
 import fp16x3_emul as emul
-from fp16x3_seq_emul import FLOOR, flush_subnormals
+from fp16x3_emul import BOUND, FLOOR
 
-BOUND = emul.BOUND
 KH, KW = 3, 9
 
 
@@ -70,9 +69,9 @@ def _untile(t, H, W):
     return t.permute(0, 1, 3, 2, 4, 5).reshape(S, nh * th, nw * tw, Cc)[:, :H, :W]
 
 
-def split_weight(w):
-    """(hi, lo) as float64 conv weights (co, ci, 3, 9) and the reciprocal scale of the WHOLE matrix"""
-    hi, lo, rs = emul.split(w.reshape(1, -1))
+def split_weight(w, flush=False):
+    """(hi, lo) as float16 conv weights (co, ci, 3, 9) and the reciprocal scale of the WHOLE matrix"""
+    hi, lo, rs = emul.split(w.reshape(1, -1), flush)
     return hi.view(w.shape), lo.view(w.shape), rs
 
 
@@ -87,9 +86,7 @@ def weight_image(w2d):
 def _split_patches(p, flush):
     """pieces of every patch under its own scale: (hi, lo) float64 like p, rs (S, tiles_h, tiles_w) float64"""
     n = p.shape[:3]
-    hi, lo, rs = emul.split(p.reshape(n[0] * n[1] * n[2], -1))
-    if flush:
-        hi, lo = flush_subnormals(hi), flush_subnormals(lo)
+    hi, lo, rs = emul.split(p.reshape(n[0] * n[1] * n[2], -1), flush)
     return hi.view(p.shape).double(), lo.view(p.shape).double(), rs.view(n).double()
 
 
@@ -107,9 +104,7 @@ def _conv_tiles(p, w, transposed):
 
 
 def _run(patches, w, H, W, transposed, flush):
-    hw, lw, rsw = split_weight(w)
-    if flush:
-        hw, lw = flush_subnormals(hw), flush_subnormals(lw)
+    hw, lw, rsw = split_weight(w, flush)
     hw, lw = hw.double(), lw.double()
     ha, la, rs = _split_patches(patches, flush)
     acc0 = _conv_tiles(ha, hw, transposed)

@@ -24,9 +24,8 @@ import torch.nn.functional as F
 
 import fp16x3_emul as emul
 from fp16x3_conv32_emul import fwd_patches, pick_tiles, wout_of
-from fp16x3_seq_emul import FLOOR, flush_subnormals
+from fp16x3_emul import BOUND, FLOOR, scale_exponents
 
-BOUND = emul.BOUND
 BLOCKS = 256
 
 
@@ -54,18 +53,7 @@ def running_max(m):
     (ntiles,) float32; a zero, inf or NaN tile maximum leaves it alone; every block starts at 0"""
     n = m.numel()
     per, blocks = partition(n)
-    counted = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
-    padded = torch.zeros(blocks * per, dtype=m.dtype)
-    padded[:n] = counted
-    return padded.view(blocks, per).cummax(dim=1).values.reshape(-1)[:n]
-
-
-def scale_exponents(run):
-    """sexp of f2g_f16_scales for the running maxima `run` (float32): s = 2^sexp, 0 for run = 0"""
-    live = run > 0
-    _, ex = torch.frexp(torch.where(live, run, torch.ones_like(run)))
-    sexp = (14 - (ex - 1)).clamp(-126, 126)
-    return torch.where(live, sexp, torch.zeros_like(sexp))
+    return emul.running_max(m, [min(b * per, n) for b in range(blocks + 1)])
 
 
 def walk(x, g):
@@ -89,11 +77,7 @@ def _split(t, sexp, flush):
     """(hi, lo) float64 of the tiles t (ntiles, ...) under the scales 2^sexp (ntiles,); flush: subnormal pieces read
     as zero (a matrix pipe that flushes its inputs)"""
     s = torch.ldexp(torch.ones(t.shape[0]), sexp).view(-1, *([1] * (t.dim() - 1)))
-    y = t * s
-    hi = y.to(torch.float16)
-    lo = ((y - hi.float()) * 2048.0).to(torch.float16)
-    if flush:
-        hi, lo = flush_subnormals(hi), flush_subnormals(lo)
+    hi, lo = emul.pieces(t * s, flush)
     return hi.double(), lo.double()
 
 

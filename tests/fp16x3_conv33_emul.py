@@ -19,9 +19,8 @@ import torch
 import torch.nn.functional as F
 
 import fp16x3_emul as emul
-from fp16x3_seq_emul import FLOOR, flush_subnormals
+from fp16x3_emul import BOUND, FLOOR
 
-BOUND = emul.BOUND
 P33 = 352
 
 
@@ -50,9 +49,9 @@ def flipped(w):
     return w.permute(1, 0, 2, 3).flip(2, 3).contiguous()
 
 
-def split_weight(w):
+def split_weight(w, flush=False):
     """(hi, lo) as conv weights like w and the reciprocal scale of the WHOLE matrix"""
-    hi, lo, rs = emul.split(w.reshape(1, -1))
+    hi, lo, rs = emul.split(w.reshape(1, -1), flush)
     return hi.view(w.shape), lo.view(w.shape), rs
 
 
@@ -67,9 +66,7 @@ def weight_image(w2d):
 def _split_patches(p, flush):
     """pieces of every patch under its own scale: (hi, lo) float64 like p, rs (S, tiles_h) float64"""
     n = p.shape[:2]
-    hi, lo, rs = emul.split(p.reshape(n[0] * n[1], -1))
-    if flush:
-        hi, lo = flush_subnormals(hi), flush_subnormals(lo)
+    hi, lo, rs = emul.split(p.reshape(n[0] * n[1], -1), flush)
     return hi.view(p.shape).double(), lo.view(p.shape).double(), rs.view(n).double()
 
 
@@ -84,9 +81,7 @@ def _conv_tiles(p, w):
 def fwd(x, w, flush=False):
     """float64 conv (no bias, no activation) of x (S, H, W, 32) in the kernel's arithmetic -> (S, H, W, 32)"""
     S, H, W, Cc = x.shape
-    hw, lw, rsw = split_weight(w)
-    if flush:
-        hw, lw = flush_subnormals(hw), flush_subnormals(lw)
+    hw, lw, rsw = split_weight(w, flush)
     hw, lw = hw.double(), lw.double()
     _, p = patches(x)
     ha, la, rs = _split_patches(p, flush)

@@ -25,11 +25,10 @@ import torch
 import torch.nn.functional as F
 
 import fp16x3_emul as emul
-from fp16x3_conv32w_emul import _split, scale_exponents
+from fp16x3_conv32w_emul import _split
 from fp16x3_conv33_emul import patches, pick_rows
-from fp16x3_seq_emul import FLOOR
+from fp16x3_emul import BOUND, FLOOR, scale_exponents
 
-BOUND = emul.BOUND
 BLOCKS = 256
 
 
@@ -59,10 +58,10 @@ def running_max(m):
     every block starts at 0"""
     n = m.numel()
     grid, steps = partition(n)
-    counted = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
     padded = torch.zeros(steps * grid, dtype=m.dtype)
-    padded[:n] = counted
-    return padded.view(steps, grid).cummax(dim=0).values.reshape(-1)[:n]
+    padded[:n] = m
+    # (block, step) is the walk order: every block one segment
+    return emul.running_max(padded.view(steps, grid).t(), [0, steps]).t().reshape(-1)[:n]
 
 
 def walk(x, g):

@@ -22,10 +22,8 @@ The sums are exact (float64) where the kernel accumulates in fp32.  A's scales d
 import torch
 
 import fp16x3_emul as emul
-from fp16x3_conv32w_emul import scale_exponents
-from fp16x3_seq_emul import FLOOR, flush_subnormals
+from fp16x3_emul import BOUND, FLOOR, scale_exponents
 
-BOUND = emul.BOUND
 TILE = 128              # output rows / columns of a block
 SLAB = 32               # reduction rows of a slab
 
@@ -60,11 +58,7 @@ def running_max(m, R, split_k=1):
     maximum leaves it alone; every K chunk starts at 0"""
     kchunk, chunks = kchunk_of(R, split_k)
     per = kchunk // SLAB
-    counted = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
-    out = torch.empty_like(counted)
-    for z in range(chunks):
-        out[:, z * per:(z + 1) * per] = counted[:, z * per:(z + 1) * per].cummax(dim=1).values
-    return out
+    return emul.running_max(m, [min(z * per, m.shape[1]) for z in range(chunks + 1)])
 
 
 def walk(a, b, split_k=1):
@@ -86,11 +80,7 @@ def _rows_of(per_slab, x):
 
 def _pieces(x, sexp, flush):
     """(hi, lo) float64 of x (R, cols) under the scales 2^sexp (R, cols: constant over a tile's slab)"""
-    y = x.float() * torch.ldexp(torch.ones(x.shape), sexp)
-    hi = y.to(torch.float16)
-    lo = ((y - hi.float()) * 2048.0).to(torch.float16)
-    if flush:
-        hi, lo = flush_subnormals(hi), flush_subnormals(lo)
+    hi, lo = emul.pieces(x.float() * torch.ldexp(torch.ones(x.shape), sexp), flush)
     return hi.double(), lo.double()
 
 
@@ -174,3 +164,32 @@ def gpu_cases():
     out += [(p, s, 1) for s in MAGNITUDE_SHAPES for p in PATTERNS]
     out += [("normal", MAGNITUDE_SHAPES[1], SPLIT_K), ("rising", MAGNITUDE_SHAPES[1], SPLIT_K)]
     return out
+
+
+def refusals(spare):
+    """name -> [(object, field, value)] ("+": added to the field): every descriptor the kernel declines, one change of
+    the base descriptor each (tests/test_hip_gemm_f16_wgradn.py launches the same list)"""
+    big_rows = 0x7ff00000 // (4 * 136) - 32 + 1            # (rows + 32) * ld * 4 >= 0x7ff00000 at ld = 136
+    return {
+        "only_a": [("B", "split", 0)], "only_b": [("A", "split", 0)],
+        "rscale_a": [("A", "rscale", spare)], "rscale_b": [("B", "rscale", spare)],
+        "cols_mod_4": [("A", "cols", 130)], "ld_mod_4": [("B", "seq_stride+", 2)], "ld_lt_cols": [("A", "seq_stride", 128)],
+        "base_plus_4": [("A", "base+", 4)], "rows_differ": [("B", "rows+", -1)],
+        "b_window": [("B", "P0", 8), ("B", "step0", 1)],
+        "alpha": [("A", "alpha", spare)], "lrelu_src": [("A", "lrelu_src", spare)],
+        "c_bf16": [("E", "c_bf16", 1)], "x3_out": [("E", "x3_out", spare)], "colsum_part_ld": [("E", "colsum_part_ld", 4)],
+        "prelu_slope": [("E", "prelu_slope", spare)], "mask_src": [("E", "mask_src", spare)],
+        "aux_without_alpha_n": [("E", "aux", spare), ("E", "ldaux", 256)],
+        "split_k_without_atomic": [("d", "split_k", 2), ("E", "atomic", 0)],
+        "extent": [("A", "rows", big_rows), ("B", "rows", big_rows)],
+    }
+
+
+def apply(d, sets):
+    for o, field, v in sets:
+        obj = {"A": d.A, "B": d.B, "E": d.E, "d": d}[o]
+        if field.endswith("+"):
+            field = field[:-1]
+            v = getattr(obj, field) + v
+        setattr(obj, field, v)
+    return d

@@ -21,8 +21,7 @@ builders at the end are shared by the CPU and the GPU tests, which therefore see
 import torch
 
 import fp16x3_emul as emul
-from fp16x3_conv32w_emul import scale_exponents
-from fp16x3_seq_emul import BOUND, FLOOR, flush_subnormals
+from fp16x3_emul import BOUND, FLOOR, scale_exponents
 
 TILE, SLAB = 128, 32
 
@@ -40,8 +39,7 @@ def slab_maxima(A):
 def running_max(m):
     """the running maximum in force at every slab: m (tiles, slabs) -> the same shape; a zero, inf or NaN slab maximum
     leaves it alone; every tile starts at 0"""
-    counted = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
-    return counted.cummax(dim=1).values
+    return emul.running_max(m, [0, m.shape[1]])
 
 
 def walk(A):
@@ -61,9 +59,7 @@ def gemm(A, W, flush=False):
     flush: subnormal pieces read as zero (a matrix pipe that flushes its inputs)"""
     M, K = A.shape
     sexp = _rows(walk(A)["sexp"], M)                              # (M, slabs)
-    hb, lb, rb = emul.split(W)
-    if flush:
-        hb, lb = flush_subnormals(hb), flush_subnormals(lb)
+    hb, lb, rb = emul.split(W, flush)
     hb, lb = hb.double(), lb.double()
     acc0 = torch.zeros(M, W.shape[0], dtype=torch.float64)
     acc1 = torch.zeros_like(acc0)
@@ -74,11 +70,7 @@ def gemm(A, W, flush=False):
         f = torch.ldexp(one, sexp[:, t] - prev)[:, None]          # s_new / s_old: an exact power of two
         acc0, acc1 = acc0 * f, acc1 * f
         prev = sexp[:, t]
-        y = A[:, k].float() * torch.ldexp(torch.ones(M), sexp[:, t])[:, None]
-        hi = y.to(torch.float16)
-        lo = ((y - hi.float()) * 2048.0).to(torch.float16)
-        if flush:
-            hi, lo = flush_subnormals(hi), flush_subnormals(lo)
+        hi, lo = emul.pieces(A[:, k].float() * torch.ldexp(torch.ones(M), sexp[:, t])[:, None], flush)
         hi, lo = hi.double(), lo.double()
         acc0 = acc0 + hi @ hb[:, k].t()
         acc1 = acc1 + hi @ lb[:, k].t() + lo @ hb[:, k].t()

@@ -27,10 +27,8 @@ import torch
 
 import fp16x3_emul as emul
 from fp16x3_colswin3_emul import gathered, rows_of, windows3
-from fp16x3_conv32w_emul import scale_exponents
-from fp16x3_seq_emul import FLOOR, flush_subnormals
+from fp16x3_emul import BOUND, FLOOR, running_max, scale_exponents      # running_max(m, bounds = partition(units))
 
-BOUND = emul.BOUND
 R = 16                  # gradient rows of a slab
 STEP, TAPS = 3, 5
 XR = (R - 1) * STEP + TAPS
@@ -73,16 +71,6 @@ def slab_maxima(g, x, nseq, hp_in, hp, pad):
     return mx, mg
 
 
-def running_max(m, bounds):
-    """the running maximum in force at every slab: m (units,) float32 slab maxima in walk order, bounds = partition(units)
-    -> (units,) float32; a zero, inf or NaN slab maximum leaves it alone; every block starts at 0"""
-    counted = torch.where(torch.isfinite(m), m, torch.zeros_like(m))
-    out = torch.empty_like(counted)
-    for a, b in zip(bounds[:-1], bounds[1:]):
-        out[a:b] = counted[a:b].cummax(dim=0).values
-    return out
-
-
 def walk(g, x, nseq, hp_in, hp, pad):
     """the running maxima xrun, grun (units,) and the scale exponents sx, sg (units,) in force at each slab, and the
     partition `bounds`"""
@@ -94,11 +82,7 @@ def walk(g, x, nseq, hp_in, hp, pad):
 
 def _pieces(t, sexp, flush):
     """(hi, lo) float64 of the rows t (rows, C) under the scales 2^sexp (rows,); flush: subnormal pieces read as zero"""
-    y = t.float() * torch.ldexp(torch.ones(t.shape[0]), sexp)[:, None]
-    hi = y.to(torch.float16)
-    lo = ((y - hi.float()) * 2048.0).to(torch.float16)
-    if flush:
-        hi, lo = flush_subnormals(hi), flush_subnormals(lo)
+    hi, lo = emul.pieces(t.float() * torch.ldexp(torch.ones(t.shape[0]), sexp)[:, None], flush)
     return hi.double(), lo.double()
 
 

@@ -26,9 +26,8 @@ that stands for the division by a segment's length -- so that the host test can 
 import torch
 
 import fp16x3_emul as emul
+from fp16x3_emul import BOUND, FLOOR
 
-BOUND = emul.BOUND
-FLOOR = 2.0 ** -28
 NSEG, TILE = 17, 128        # the kernel's table of segments per tile and its tile
 
 

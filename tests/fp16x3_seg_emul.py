@@ -21,9 +21,8 @@ A scale never spans two sequences and a window never leaves its sequence, so eve
 import torch
 
 import fp16x3_emul as emul
+from fp16x3_emul import BOUND, FLOOR
 
-BOUND = emul.BOUND
-FLOOR = 2.0 ** -28
 TAPS, STEP = 5, 3
 
 

@@ -3,14 +3,13 @@ arithmetic, images, scales and bound of tests/fp16x3_seq_emul.py -- a window nev
 stride, so one power-of-two scale per sequence leaves every output row's sum exactly -- with the window stride added.
 
   window     row (s, p) = positions first + step * p ... + taps of sequence s
-  bound      3 * 2^-22 |a| |b| per product + 2^-28 amax_seq sum_k |w[n,k]| per output (fp16x3_seq_emul.BOUND, FLOOR)
+  bound      3 * 2^-22 |a| |b| per product + 2^-28 amax_seq sum_k |w[n,k]| per output (fp16x3_emul.BOUND, FLOOR)
 """
 import torch
 
 import fp16x3_seq_emul as seq
+from fp16x3_emul import BOUND, FLOOR
 
-BOUND = seq.BOUND
-FLOOR = seq.FLOOR
 split = seq.split
 image = seq.image
 
@@ -26,10 +25,8 @@ def gemm(x, w, P0, taps, step, first=0, flush=False):
     """float64 windows(x) w^T in the kernel's arithmetic (the fp32 accumulation replaced by exact sums); x (S, Hp, C)
     the map, w (N, taps * C) the weights"""
     S, Hp, Cc = x.shape
-    ha, la, ra = split(x.reshape(S, Hp * Cc))
-    hb, lb, rb = split(w)
-    if flush:
-        ha, la, hb, lb = (seq.flush_subnormals(t) for t in (ha, la, hb, lb))
+    ha, la, ra = split(x.reshape(S, Hp * Cc), flush)
+    hb, lb, rb = split(w, flush)
     ha, la = (windows(t.view(S, Hp, Cc).double(), P0, taps, step, first) for t in (ha, la))
     hb, lb = hb.double(), lb.double()
     acc0 = ha @ hb.t()

@@ -12,14 +12,12 @@ positions x channels) or a row of the weight matrix -- and the GEMM over stride-
 import torch
 
 import fp16x3_emul as emul
-
-BOUND = emul.BOUND
-FLOOR = 2.0 ** -28
+from fp16x3_emul import BOUND, FLOOR
 
 
-def split(x):
+def split(x, flush=False):
     """(hi, lo, rscale) of the runs x (nruns, n): fp16x3_emul.split with one scale per run"""
-    return emul.split(x.reshape(x.shape[0], -1))
+    return emul.split(x.reshape(x.shape[0], -1), flush)
 
 
 def image(x):
@@ -37,19 +35,12 @@ def windows(x, P0, taps, first=0):
     return torch.stack([x[:, first + t:first + t + P0] for t in range(taps)], 2).reshape(S * P0, taps * Cc)
 
 
-def flush_subnormals(h):
-    """an fp16 tensor with its subnormal values replaced by zero (a matrix pipe that flushes its inputs)"""
-    return torch.where(h.float().abs() < 2.0 ** -14, torch.zeros_like(h), h)
-
-
 def gemm(x, w, P0, taps, first=0, flush=False):
     """float64 windows(x) w^T in the kernel's arithmetic (the fp32 accumulation replaced by exact sums); x (S, Hp, C)
     the map, w (N, taps * C) the weights"""
     S, Hp, Cc = x.shape
-    ha, la, ra = split(x.reshape(S, Hp * Cc))
-    hb, lb, rb = split(w)
-    if flush:
-        ha, la, hb, lb = (flush_subnormals(t) for t in (ha, la, hb, lb))
+    ha, la, ra = split(x.reshape(S, Hp * Cc), flush)
+    hb, lb, rb = split(w, flush)
     ha, la = (windows(t.view(S, Hp, Cc).double(), P0, taps, first) for t in (ha, la))
     hb, lb = hb.double(), lb.double()
     acc0 = ha @ hb.t()

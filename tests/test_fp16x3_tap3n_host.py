@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def _inputs(P0, seed, extra=2):
     """a map of enough sequences for three 128-row groups, sequences over 60 decades (as
-    tests/test_hip_gemm_f16_tap.py: case), and the layer's weights"""
+    tests/fp16x3_gpu.py: case), and the layer's weights"""
     S = max(3, -(-300 // P0))
     Hp = emul.STEP * (P0 - 1) + emul.TAPS + extra
     g = torch.Generator().manual_seed(seed)

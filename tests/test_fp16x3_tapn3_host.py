@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import fp16x3_res3_emul as emul
+from fp16x3_res3_emul import REFUSALS
 
 CIN, COUT = 32, 128
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -216,34 +217,6 @@ def test_the_library_answers_for_the_kernels_descriptor(host_lib):
     assert ok(_descriptor(ops, keep, S=256, P0=128, Hin=384)) == 1
     _lib.set_option("x6p", 0)
     assert ok(_descriptor(ops, keep, S=256, P0=128, Hin=384)) == 0
-
-
-def _set(obj, **kw):
-    def change(d):
-        for k, v in kw.items():
-            setattr(getattr(d, obj) if obj else d, k, v)
-    return change
-
-
-REFUSALS = {
-    # the epilogue terms the kernel does not have (p: any valid pointer)
-    "bias": lambda p: _set("E", bias=p), "lrelu_slope": lambda p: _set("E", lrelu_slope=0.1),
-    "aux": lambda p: _set("E", aux=p, ldaux=96, alpha_n=p), "res": lambda p: _set("E", res=p, ldres=96),
-    "colsum_alpha": lambda p: _set("E", colsum_alpha=p), "prelu_slope": lambda p: _set("E", prelu_slope=p),
-    "prelu_out": lambda p: _set("E", prelu_out=p, ld_prelu_out=96), "scale": lambda p: _set("E", scale=2.0),
-    "atomic": lambda p: _set("E", atomic=1), "accumulate": lambda p: _set("E", accumulate=1),
-    "c_bf16": lambda p: _set("E", c_bf16=1), "x3_out": lambda p: _set("E", x3_out=p),
-    "colsum_part_ld": lambda p: _set("E", colsum_part_ld=96), "split_k": lambda p: _set("", split_k=2),
-    # the fold and the cut
-    "col_fold=0": lambda p: _set("E", col_fold=0), "col_fold=16": lambda p: _set("E", col_fold=16),
-    "seq_live=0": lambda p: _set("E", seq_live=0), "seq_live%32": lambda p: _set("E", seq_live=32 * 299 + 8),
-    "seq_live short": lambda p: _set("E", seq_live=96 * 99), "seq_live long": lambda p: _set("E", seq_live=96 * 100 + 32),
-    "P0o": lambda p: _set("E", P0o=99), "no row map": lambda p: _set("E", P0o=0), "row_stride_o": lambda p: _set("E", row_stride_o=128),
-    # the operand
-    "step0": lambda p: _set("A", step0=3), "pad0": lambda p: _set("A", pad0=1), "unmarked": lambda p: _set("A", split=0),
-    "image of A": lambda p: _set("A", split=7, rscale=p), "misaligned": lambda p: _set("A", base=p + 4),
-    "form 2": lambda p: _set("", form=2), "precision 3": lambda p: _set("", precision=3),
-}
 
 
 @pytest.mark.parametrize("what", sorted(REFUSALS))

@@ -16,9 +16,9 @@ import torch
 
 import fp16x3_route_cases as route_cases
 import fp16x3_runk_emul as emul
+from fp16x3_gpu import TOL              # (the GPU file's own)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-TOL = 1.8e-6            # tests/test_hip_gemm_f16.py: TOL (the GPU file imports it from there and compares)
 CASES = emul.gpu_cases()
 IDS = [f"{p}-{'x'.join(map(str, s))}-k{k}" for p, s, k in CASES]
 
@@ -128,35 +128,6 @@ def descriptor(ops, keep, R=160, M=132, N=160, ld_pad=4):
     return d
 
 
-def refusals(spare):
-    """name -> [(object, field, value)] ("+": added to the field): every descriptor the kernel declines, one change of
-    the base descriptor each (tests/test_hip_gemm_f16_wgradn.py launches the same list)"""
-    big_rows = 0x7ff00000 // (4 * 136) - 32 + 1            # (rows + 32) * ld * 4 >= 0x7ff00000 at ld = 136
-    return {
-        "only_a": [("B", "split", 0)], "only_b": [("A", "split", 0)],
-        "rscale_a": [("A", "rscale", spare)], "rscale_b": [("B", "rscale", spare)],
-        "cols_mod_4": [("A", "cols", 130)], "ld_mod_4": [("B", "seq_stride+", 2)], "ld_lt_cols": [("A", "seq_stride", 128)],
-        "base_plus_4": [("A", "base+", 4)], "rows_differ": [("B", "rows+", -1)],
-        "b_window": [("B", "P0", 8), ("B", "step0", 1)],
-        "alpha": [("A", "alpha", spare)], "lrelu_src": [("A", "lrelu_src", spare)],
-        "c_bf16": [("E", "c_bf16", 1)], "x3_out": [("E", "x3_out", spare)], "colsum_part_ld": [("E", "colsum_part_ld", 4)],
-        "prelu_slope": [("E", "prelu_slope", spare)], "mask_src": [("E", "mask_src", spare)],
-        "aux_without_alpha_n": [("E", "aux", spare), ("E", "ldaux", 256)],
-        "split_k_without_atomic": [("d", "split_k", 2), ("E", "atomic", 0)],
-        "extent": [("A", "rows", big_rows), ("B", "rows", big_rows)],
-    }
-
-
-def apply(d, sets):
-    for o, field, v in sets:
-        obj = {"A": d.A, "B": d.B, "E": d.E, "d": d}[o]
-        if field.endswith("+"):
-            field = field[:-1]
-            v = getattr(obj, field) + v
-        setattr(obj, field, v)
-    return d
-
-
 @pytest.fixture(scope="module")
 def lib():
     from flow2gan_amd import _lib
@@ -180,20 +151,20 @@ def test_the_library_answers_for_the_descriptor(lib):
                 "split_k": [("d", "split_k", 3)], "bias": [("E", "bias", p)], "scale": [("E", "scale", 0.75)],
                 "aux+alpha_n": [("E", "aux", p), ("E", "ldaux", 256), ("E", "alpha_n", p)]}
     for name, sets in accepted.items():
-        assert ok(apply(descriptor(ops, keep), sets)) == 1, name
-    for name, sets in refusals(p).items():
-        d = apply(descriptor(ops, keep), sets)
+        assert ok(emul.apply(descriptor(ops, keep), sets)) == 1, name
+    for name, sets in emul.refusals(p).items():
+        d = emul.apply(descriptor(ops, keep), sets)
         assert ok(d) == 0, name
         assert lib.f2g_gemm_colsum_part_rows(C.byref(d)) == 0, name
     for prec in (0, 1, 2, 3):
-        assert ok(apply(descriptor(ops, keep), [("d", "precision", prec)])) == 0
+        assert ok(emul.apply(descriptor(ops, keep), [("d", "precision", prec)])) == 0
     for form in (0, 1):
-        assert ok(apply(descriptor(ops, keep), [("d", "form", form)])) == 0
+        assert ok(emul.apply(descriptor(ops, keep), [("d", "form", form)])) == 0
     # the mark of gemm_h3n_kernel's operand A (split = 9) means nothing at form 2, on one operand or on both, as before
     for marks in ((9, 9), (9, 10), (10, 9), (9, 0), (0, 9)):
-        assert ok(apply(descriptor(ops, keep), [("A", "split", marks[0]), ("B", "split", marks[1])])) == 0, marks
+        assert ok(emul.apply(descriptor(ops, keep), [("A", "split", marks[0]), ("B", "split", marks[1])])) == 0, marks
     # unmarked, the descriptor is the image route's as before: 2 = once both column images are made
-    assert ok(apply(descriptor(ops, keep), [("A", "split", 0), ("B", "split", 0)])) == 2
+    assert ok(emul.apply(descriptor(ops, keep), [("A", "split", 0), ("B", "split", 0)])) == 2
 
 
 # ------------------------------------------------------------------ ops.gemm's chooser

@@ -14,39 +14,24 @@ Shapes are (S, H, Win); gw is (32, 27 * 32) [co][tap][ci].
 """
 import ctypes as C
 import functools
-import math
-import types
 
 import pytest
 import torch
 
 import fp16x3_conv32w_emul as emul
+from fp16x3_gpu import EINVAL, TOL, fp16x3_mode, library, subdisc_against_oracle
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-TOL = 1.8e-6
-EINVAL = -1
-
-
-def mode_name(ops):
-    return "fp16x3" if ops.FP16X3 else {0: "fp32", 1: "bf16x3", 2: "bf16", 3: "bf16x6"}[ops.GEMM_PRECISION]
 
 
 @pytest.fixture
 def ops():
     """the fp16x3 mode with the weight-gradient tunable on; mode and band-conv tunables restored afterwards"""
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from flow2gan_amd import ops as o
-    was = mode_name(o), o.FP16X3_CONV32_FWD, o.FP16X3_CONV32_DGRAD, o.FP16X3_CONV32_WGRAD
-    o.set_gemm_precision("fp16x3")
-    o.FP16X3_CONV32_WGRAD = True
-    try:
+    with fp16x3_mode(library(), "FP16X3_CONV32_FWD", "FP16X3_CONV32_DGRAD", "FP16X3_CONV32_WGRAD") as o:
+        o.FP16X3_CONV32_WGRAD = True
         yield o
-    finally:
-        o.FP16X3_CONV32_FWD, o.FP16X3_CONV32_DGRAD, o.FP16X3_CONV32_WGRAD = was[1:]
-        o.set_gemm_precision(was[0])
 
 
 def g(t):
@@ -283,41 +268,11 @@ def test_mrd_window_against_oracle(ops):
     """one resolution's sub-discriminator at the shapes of tests/test_hip_disc_autograd.py with all three band-conv
     tunables on: scores, feature maps, the input gradient and every parameter gradient against the oracle at that
     file's tolerance; the weight-gradient counter moves with the tunable on and stands still with it off"""
-    import test_hip_disc_autograd as T
     ops.FP16X3_CONV32_FWD = ops.FP16X3_CONV32_DGRAD = True
-    do, dh = T._models("mrd")
-    sub_o, sub_h = do.discriminators[0], dh.discriminators[0]
-    _, y_hat = T._inputs()
-
-    def loss_of(score, fmap):
-        gen = torch.Generator().manual_seed(77)
-        loss = torch.relu(1 + score).mean()
-        for m in fmap:
-            loss = loss + (m * torch.randn(m.shape, generator=gen).to(m.device)).sum() / math.sqrt(m.numel())
-        return loss
-
-    def hip_run():
-        for p in sub_h.parameters():
-            p.grad = None
-        yh = y_hat.to(DEV).requires_grad_(True)
-        n0 = ops.FP16X3_CONV32_WGRAD_LAUNCHES
-        score, fmap = sub_h(yh)
-        loss_of(score, fmap).backward()
-        torch.cuda.synchronize()
-        return score, fmap, yh.grad, ops.FP16X3_CONV32_WGRAD_LAUNCHES - n0
-
-    score, fmap, gx, nw = hip_run()
-    print(f"[conv32 fp16x3 wgrad] window {sub_h.window_length}: {nw} weight-gradient launches")
+    r = subdisc_against_oracle(ops, "mrd", ("FP16X3_CONV32_WGRAD_LAUNCHES",),
+                               "mrd window, fp16x3 band convolutions with the weight gradient")
+    nw = r.fwd[0] + r.bwd[0]
+    print(f"[conv32 fp16x3 wgrad] window {r.sub.window_length}: {nw} weight-gradient launches")
     assert nw > 0
-    sides = T._hip_sides(types.SimpleNamespace(discriminators=[sub_h]), "mrd", y_hat.to(DEV))[0]
-    yo = y_hat.clone().requires_grad_(True)
-    do.zero_grad(set_to_none=True)
-    so, fo = T._with_sides(sides, lambda: sub_o(yo))
-    loss_of(so, fo).backward()
-    pairs = [("score", score, so.detach())] + [(f"fmap.{i}", m, fo[i].detach()) for i, m in enumerate(fmap)]
-    pairs += [("y_hat", gx, yo.grad)]
-    pairs += [(k, p.grad, dict(sub_o.named_parameters())[k].grad) for k, p in sub_h.named_parameters()]
-    do.zero_grad(set_to_none=True)
-    T._compare(pairs, "mrd window, fp16x3 band convolutions with the weight gradient")
     ops.FP16X3_CONV32_WGRAD = False
-    assert hip_run()[3] == 0
+    assert r.rerun() == ((0,), (0,))

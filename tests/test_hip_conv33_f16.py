@@ -15,45 +15,29 @@ tile-wide scale (tests/fp16x3_conv33_emul.py), + 1.8e-6 |bias|.  Column sums: 1e
 """
 import ctypes as C
 import functools
-import math
-import types
 
 import pytest
 import torch
 import torch.nn.functional as F
 
 import fp16x3_conv33_emul as emul
+from fp16x3_gpu import EINVAL, TOL, fp16x3_mode, image_follows_weight, library, subdisc_against_oracle
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-TOL = 1.8e-6
-EINVAL = -1
 SLOPE = 0.1
 BLOCKS = 256            # persistent blocks of a launch: grid = min(tiles, 256)
-
-
-def mode_name(ops):
-    return "fp16x3" if ops.FP16X3 else {0: "fp32", 1: "bf16x3", 2: "bf16", 3: "bf16x6"}[ops.GEMM_PRECISION]
 
 
 @pytest.fixture
 def ops():
     """the fp16x3 mode with both (3, 3) tunables on; mode and tunables restored afterwards"""
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from flow2gan_amd import ops as o
     names = ("FP16X3_CONV33_FWD", "FP16X3_CONV33_DGRAD", "FP16X3_CONV32_FWD", "FP16X3_CONV32_DGRAD",
              "FP16X3_CONV32_WGRAD")
-    was = mode_name(o), [getattr(o, n) for n in names]
-    o.set_gemm_precision("fp16x3")
-    o.FP16X3_CONV33_FWD = o.FP16X3_CONV33_DGRAD = True
-    try:
+    with fp16x3_mode(library(), *names) as o:
+        o.FP16X3_CONV33_FWD = o.FP16X3_CONV33_DGRAD = True
         yield o
-    finally:
-        for n, v in zip(names, was[1]):
-            setattr(o, n, v)
-        o.set_gemm_precision(was[0])
 
 
 def g(t):
@@ -445,19 +429,10 @@ def test_weight_image_follows_its_weight(ops):
             assert torch.equal(buf[9216:], want_rs), f"{what}: the cached scale is stale"
         return y.clone(), gx.clone()
 
-    first = launch_and_check("first launch")
-    version = w._version
-    w.data.copy_(w.detach() * 37.0 + 0.01)                  # (the matrix's scale must move too)
-    assert w._version == version
-    ops.bump_weight_epoch([w])
-    replayed = ops.rebuild_derived([w])
-    assert replayed >= 2 or not ops.EAGER_REBUILD
-    second = launch_and_check("after the raw-pointer update")
-    assert not torch.equal(first[0], second[0]) and not torch.equal(first[1], second[1])
-    with torch.no_grad():
-        w.mul_(-0.37)
-    third = launch_and_check("after the in-place update")
-    assert not torch.equal(second[0], third[0]) and not torch.equal(second[1], third[1])
+    def update(w):
+        w.data.copy_(w.detach() * 37.0 + 0.01)              # (the matrix's scale must move too)
+
+    image_follows_weight(ops, w, launch_and_check, update=update, min_replays=2)
 
 
 # ------------------------------------------------------------------ 10. one MRD resolution against the CPU oracle
@@ -465,42 +440,11 @@ def test_mrd_resolution_against_oracle(ops):
     """one resolution's sub-discriminator at the shapes of tests/test_hip_disc_autograd.py, the (3, 9) and the (3, 3)
     fp16x3 tunables all on: scores, feature maps, the input gradient and every parameter gradient against the oracle
     at that file's tolerance; both (3, 3) counters move with the tunables on and stand still with them off"""
-    import test_hip_disc_autograd as T
     ops.FP16X3_CONV32_FWD = ops.FP16X3_CONV32_DGRAD = ops.FP16X3_CONV32_WGRAD = True
-    do, dh = T._models("mrd")
-    sub_o, sub_h = do.discriminators[0], dh.discriminators[0]
-    _, y_hat = T._inputs()
-
-    def loss_of(score, fmap):
-        gen = torch.Generator().manual_seed(77)
-        loss = torch.relu(1 + score).mean()
-        for m in fmap:
-            loss = loss + (m * torch.randn(m.shape, generator=gen).to(m.device)).sum() / math.sqrt(m.numel())
-        return loss
-
-    def hip_run():
-        for p in sub_h.parameters():
-            p.grad = None
-        yh = y_hat.to(DEV).requires_grad_(True)
-        n = ops.FP16X3_CONV33_FWD_LAUNCHES, ops.FP16X3_CONV33_DGRAD_LAUNCHES
-        score, fmap = sub_h(yh)
-        loss_of(score, fmap).backward()
-        torch.cuda.synchronize()
-        return score, fmap, yh.grad, ops.FP16X3_CONV33_FWD_LAUNCHES - n[0], ops.FP16X3_CONV33_DGRAD_LAUNCHES - n[1]
-
-    score, fmap, gx, nf, nd = hip_run()
-    print(f"[conv33 fp16x3] window {sub_h.window_length}: {nf} forward and {nd} data-gradient launches")
+    counters = ("FP16X3_CONV33_FWD_LAUNCHES", "FP16X3_CONV33_DGRAD_LAUNCHES")
+    r = subdisc_against_oracle(ops, "mrd", counters, "mrd resolution, fp16x3 band convolutions")
+    nf, nd = (f + b for f, b in zip(r.fwd, r.bwd))
+    print(f"[conv33 fp16x3] window {r.sub.window_length}: {nf} forward and {nd} data-gradient launches")
     assert nf > 0 and nd > 0
-    sides = T._hip_sides(types.SimpleNamespace(discriminators=[sub_h]), "mrd", y_hat.to(DEV))[0]
-    yo = y_hat.clone().requires_grad_(True)
-    do.zero_grad(set_to_none=True)
-    so, fo = T._with_sides(sides, lambda: sub_o(yo))
-    loss_of(so, fo).backward()
-    pairs = [("score", score, so.detach())] + [(f"fmap.{i}", m, fo[i].detach()) for i, m in enumerate(fmap)]
-    pairs += [("y_hat", gx, yo.grad)]
-    pairs += [(k, p.grad, dict(sub_o.named_parameters())[k].grad) for k, p in sub_h.named_parameters()]
-    do.zero_grad(set_to_none=True)
-    T._compare(pairs, "mrd resolution, fp16x3 band convolutions")
     ops.FP16X3_CONV33_FWD = ops.FP16X3_CONV33_DGRAD = False
-    _, _, _, nf, nd = hip_run()
-    assert (nf, nd) == (0, 0)
+    assert r.rerun() == ((0, 0), (0, 0))

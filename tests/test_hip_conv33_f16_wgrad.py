@@ -15,42 +15,26 @@ Shapes are (S, H, W); gw is (32, 9 * 32) [co][tap][ci].
 """
 import ctypes as C
 import functools
-import math
-import types
 
 import pytest
 import torch
 
 import fp16x3_conv33w_emul as emul
+from fp16x3_gpu import EINVAL, TOL, fp16x3_mode, library, subdisc_against_oracle
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
-TOL = 1.8e-6
-EINVAL = -1
 TUNABLES = ("FP16X3_CONV32_FWD", "FP16X3_CONV32_DGRAD", "FP16X3_CONV32_WGRAD", "FP16X3_CONV33_FWD",
             "FP16X3_CONV33_DGRAD", "FP16X3_CONV33_WGRAD")
-
-
-def mode_name(ops):
-    return "fp16x3" if ops.FP16X3 else {0: "fp32", 1: "bf16x3", 2: "bf16", 3: "bf16x6"}[ops.GEMM_PRECISION]
 
 
 @pytest.fixture
 def ops():
     """the fp16x3 mode with the (3, 3) weight-gradient tunable on; mode and band-conv tunables restored afterwards"""
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from flow2gan_amd import ops as o
-    was = mode_name(o), [getattr(o, n) for n in TUNABLES]
-    o.set_gemm_precision("fp16x3")
-    o.FP16X3_CONV33_WGRAD = True
-    try:
+    with fp16x3_mode(library(), *TUNABLES) as o:
+        o.FP16X3_CONV33_WGRAD = True
         yield o
-    finally:
-        for n, v in zip(TUNABLES, was[1]):
-            setattr(o, n, v)
-        o.set_gemm_precision(was[0])
 
 
 def g(t):
@@ -338,42 +322,12 @@ def test_mrd_resolution_against_oracle(ops):
     """one resolution's sub-discriminator at the shapes of tests/test_hip_disc_autograd.py with all six band-conv
     tunables on: scores, feature maps, the input gradient and every parameter gradient against the oracle at that
     file's tolerance; the (3, 3) weight-gradient counter moves with the tunable on and stands still with it off"""
-    import test_hip_disc_autograd as T
     for n in TUNABLES:
         setattr(ops, n, True)
-    do, dh = T._models("mrd")
-    sub_o, sub_h = do.discriminators[0], dh.discriminators[0]
-    _, y_hat = T._inputs()
-
-    def loss_of(score, fmap):
-        gen = torch.Generator().manual_seed(77)
-        loss = torch.relu(1 + score).mean()
-        for m in fmap:
-            loss = loss + (m * torch.randn(m.shape, generator=gen).to(m.device)).sum() / math.sqrt(m.numel())
-        return loss
-
-    def hip_run():
-        for p in sub_h.parameters():
-            p.grad = None
-        yh = y_hat.to(DEV).requires_grad_(True)
-        n0 = ops.FP16X3_CONV33_WGRAD_LAUNCHES
-        score, fmap = sub_h(yh)
-        loss_of(score, fmap).backward()
-        torch.cuda.synchronize()
-        return score, fmap, yh.grad, ops.FP16X3_CONV33_WGRAD_LAUNCHES - n0
-
-    score, fmap, gx, nw = hip_run()
-    print(f"[conv33 fp16x3 wgrad] window {sub_h.window_length}: {nw} (3, 3) weight-gradient launches")
+    r = subdisc_against_oracle(ops, "mrd", ("FP16X3_CONV33_WGRAD_LAUNCHES",),
+                               "mrd resolution, fp16x3 band convolutions with the (3, 3) weight gradient")
+    nw = r.fwd[0] + r.bwd[0]
+    print(f"[conv33 fp16x3 wgrad] window {r.sub.window_length}: {nw} (3, 3) weight-gradient launches")
     assert nw > 0
-    sides = T._hip_sides(types.SimpleNamespace(discriminators=[sub_h]), "mrd", y_hat.to(DEV))[0]
-    yo = y_hat.clone().requires_grad_(True)
-    do.zero_grad(set_to_none=True)
-    so, fo = T._with_sides(sides, lambda: sub_o(yo))
-    loss_of(so, fo).backward()
-    pairs = [("score", score, so.detach())] + [(f"fmap.{i}", m, fo[i].detach()) for i, m in enumerate(fmap)]
-    pairs += [("y_hat", gx, yo.grad)]
-    pairs += [(k, p.grad, dict(sub_o.named_parameters())[k].grad) for k, p in sub_h.named_parameters()]
-    do.zero_grad(set_to_none=True)
-    T._compare(pairs, "mrd resolution, fp16x3 band convolutions with the (3, 3) weight gradient")
     ops.FP16X3_CONV33_WGRAD = False
-    assert hip_run()[3] == 0
+    assert r.rerun() == ((0,), (0,))

@@ -6,46 +6,28 @@ of the derived-weight cache following their weights.
 Tolerance of the GEMM cases: |got - want| <= 1.8e-6 * (|A| |B|^T + |epilogue terms|) per element = the suite's 1e-6
 for exact-class fp32 accumulation plus the arithmetic's 3 * 2^-22 = 7.2e-7 per product."""
 import ctypes as C
-import random
 
 import pytest
 import torch
 
 import fp16x3_emul as emul
+from fp16x3_gpu import (EINVAL, TOL, as_image, assert_declined, cached_image, f16_ok, fp16x3_mode, image_follows_weight,
+                        ops, ran, same_bits, stage1_against_oracle)
+from fp16x3_gpu import mode_name    # noqa: F401 -- tools/fp16x3_*_shapes.py read the mode's name from this module
 from test_hip_gemm_routes import (DEV, EPI, NAN, SENT, Out, Vec, check, expect, last_kernel, launch, make_desc,
                                   plain, products, rnd, run, win1)
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1.8e-6
 NAME = "h3<ep=all>"
-EINVAL = -1
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from flow2gan_amd import ops as o
-    return o
-
-
-def mode_name(ops):
-    return "fp16x3" if ops.FP16X3 else {0: "fp32", 1: "bf16x3", 2: "bf16", 3: "bf16x6"}[ops.GEMM_PRECISION]
 
 
 @pytest.fixture
 def fp16x3(ops):
-    """the mode with the kernel reachable from K = 32 and one output column on; restored through
-    set_gemm_precision"""
-    was, was_k, was_n = mode_name(ops), ops.FP16X3_MIN_K, ops.FP16X3_MIN_N
-    ops.set_gemm_precision("fp16x3")
-    ops.FP16X3_MIN_K, ops.FP16X3_MIN_N = 32, 1
-    try:
+    """the mode with the kernel reachable from K = 32 and one output column on"""
+    with fp16x3_mode(ops, "FP16X3_MIN_K", "FP16X3_MIN_N"):
+        ops.FP16X3_MIN_K, ops.FP16X3_MIN_N = 32, 1
         yield ops
-    finally:
-        ops.FP16X3_MIN_K, ops.FP16X3_MIN_N = was_k, was_n
-        ops.set_gemm_precision(was)
 
 
 # ------------------------------------------------------------------ split kernel
@@ -112,26 +94,10 @@ def test_split_declines_what_it_cannot_keep_in_registers(ops):
 
 
 # ------------------------------------------------------------------ GEMM against float64
-def as_image(ops, op):
-    """replace the fp32 operand `op` (test_hip_gemm_routes.Op over a NaN-poisoned buffer) by its f2g_split_f16x2
-    image: a copy of the buffer -- poison included -- whose rows' K columns the split kernel rewrote"""
-    o = op.o
-    op.img = op.flat.clone()
-    op.rs = torch.full((o.rows + 8,), NAN, device=DEV)
-    ops.call("f2g_split_f16x2", op.img.data_ptr() + 4 * op.off, op.rs.data_ptr() + 16,
-             op.flat.data_ptr() + 4 * op.off, o.seq_stride, o.rows, o.cols)
-    o.base, o.split, o.rscale = op.img.data_ptr() + 4 * op.off, 5, op.rs.data_ptr() + 16
-    return op
-
-
 def operands(ops, M, N, K, seed, scale_a=1.0):
     A = as_image(ops, plain(ops, rnd(M, K, seed=seed, scale=scale_a)))
     B = as_image(ops, plain(ops, rnd(N, K, seed=seed + 50, scale=K ** -0.5)))
     return A, B
-
-
-def f16_ok(ops, d):
-    return ops.L.lib.f2g_gemm_f16_ok(C.byref(d))
 
 
 @pytest.mark.parametrize("K", [32, 64, 160, 2304])
@@ -141,7 +107,7 @@ def test_gemm_shapes_against_float64(ops, M, N, K):
     """one slab, an even and an odd slab count, a long reduction; partial tiles in both directions, a single row"""
     A, B = operands(ops, M, N, K, seed=M + 3 * N + K)
     d, out = run(ops, A, B, M, N, epi=dict(bias=True), precision=4, tol=TOL, seed=K)
-    assert last_kernel(ops) == NAME and ops.L.lib.f2g_gemm_last_path() == 6
+    assert ran(ops, NAME)
     assert f16_ok(ops, d) == 1
 
 
@@ -217,13 +183,14 @@ def test_gemm_three_launches_give_the_same_bits(ops):
     M, N, K = 129, 160, 160
     A, B = operands(ops, M, N, K, seed=14)
     bias = rnd(N, seed=6)
-    bits = []
-    for _ in range(3):
+
+    def go():
         out = Out(M, N)
         launch(ops, A, B, out, precision=4, bias=bias)
         assert last_kernel(ops) == NAME
-        bits.append(out.flat.view(torch.int32).clone())
-    assert torch.equal(bits[0], bits[1]) and torch.equal(bits[0], bits[2])
+        return out.flat.view(torch.int32).clone()
+
+    same_bits(go)
 
 
 def test_gemm_rows_over_many_decades_against_float64(ops):
@@ -293,11 +260,7 @@ def test_descriptors_the_kernel_declines(ops, what):
         d.E.c_bf16 = 1
     elif what == "no_scales":
         d.A.rscale = None
-    assert f16_ok(ops, d) == (2 if what == "fp32" else 0)
-    assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
-    torch.cuda.synchronize()
-    assert last_kernel(ops) == ""
-    assert bool((out.flat[~torch.isnan(out.flat)] == SENT).all())
+    assert_declined(ops, d, out, ok=2 if what == "fp32" else 0)
     if what in ("mixed",):              # ... and the images are refused at every other precision
         for prec in (0, 1, 2, 3):
             d.precision = prec
@@ -350,14 +313,6 @@ def test_ops_gemm_takes_the_kernel_and_marks_a_requested_x3_image_bad(fp16x3):
     assert ops.FP16X3_LAUNCHES == n0 + 2 and last_kernel(ops) != NAME
 
 
-def cached_image(ops, w):
-    o = ops._f16_operand(ops.mat(w))
-    rows, K = w.shape
-    buf = o._keep[0]
-    torch.cuda.synchronize()
-    return buf[:rows * K].cpu().view(torch.int32).view(rows, K), buf[rows * K:rows * K + rows].cpu()
-
-
 def test_weight_images_follow_their_weights(fp16x3):
     """after a raw-pointer update (the optimizer's way: bump_weight_epoch + the batched rebuild_derived) and after
     an autograd-visible in-place update, the next launch reads a rebuilt image and rebuilt scales"""
@@ -377,78 +332,14 @@ def test_weight_images_follow_their_weights(fp16x3):
         assert torch.equal(img, want_img) and torch.equal(rs, want_rs), f"{what}: the cached image is stale"
         return out.clone()
 
-    first = launch_and_check("first launch")
-    # 1. raw-pointer write of every row by its own factor (the row scales must move too), as the optimizer does
-    factors = torch.logspace(-3, 3, N, device=DEV)
-    version = w._version
-    w.data.copy_(w.detach() * factors[:, None])
-    assert w._version == version            # (invisible to autograd: only the epoch tells the cache)
-    ops.bump_weight_epoch([w])
-    replayed = ops.rebuild_derived([w])
-    assert replayed >= 1 or not ops.EAGER_REBUILD
-    second = launch_and_check("after the raw-pointer update")
-    assert not torch.equal(first, second)
-    # 2. autograd-visible in-place update: rebuilt at the next use
-    with torch.no_grad():
-        w.mul_(-0.37)
-    third = launch_and_check("after the in-place update")
-    assert not torch.equal(second, third)
+    image_follows_weight(ops, w, launch_and_check)
 
 
 # ------------------------------------------------------------------ model level, against the CPU oracle
-TINY = dict(sampling_rate=24000, n_mels=100, mel_n_fft=1024, mel_hop_length=256,
-            n_ffts=(512, 256, 128), hop_lengths=(256, 128, 64), channels=(64, 32, 32),
-            time_embed_channels=32, hidden_factor=3, num_layers=(2, 1, 1),
-            cond_enc_channels=32, cond_enc_num_layers=1)
-
-
 def test_stage1_and_infer_against_oracle(fp16x3):
     """the construction of test_hip_generator.py::test_stage1_against_oracle_other_shape (B = 3, odd T) with widths
     whose pointwise reductions are all multiples of 32, at that test's tolerances; 4-step inference <= 1e-4 RMS"""
-    ops = fp16x3
-    import flow2gan_amd as f2g
-    import flow2gan_oracle as O
-    torch.manual_seed(3)
-    mo = O.MelAudioGenerator(**TINY).train()
-    mh = f2g.MelAudioGenerator(**TINY)
-    mh.load_state_dict(mo.state_dict())
-    mh = mh.to(DEV).train()
-    mo.branch_dropout = mh.branch_dropout = 0.0
-    gen = torch.Generator().manual_seed(4)
-    B, Tn = 3, 5120
-    audio = 0.1 * torch.randn(B, Tn, generator=gen)
-    lens = torch.tensor([5120, 3000, 4097])
-    mel = O.LogMelSpectrogram()(audio)
-    noise = 0.1 * torch.randn(B, Tn, generator=gen)
-    t = torch.tensor([[0.1], [0.5], [0.9]])
-    st = random.getstate()
-    random.seed(5)
-    lo = mo(mel, audio, lens, noise=noise, t=t)
-    lo.backward()
-    random.setstate(st)
-    random.seed(5)
-    n0 = ops.FP16X3_LAUNCHES
-    lh = mh(mel.to(DEV), audio.to(DEV), lens, noise=noise.to(DEV), t=t.to(DEV))
-    n1 = ops.FP16X3_LAUNCHES
-    lh.backward()
-    n2 = ops.FP16X3_LAUNCHES
-    random.setstate(st)
-    print(f"fp16x3 launches: forward {n1 - n0}, backward {n2 - n1}; loss {float(lh):.7f} oracle {float(lo):.7f}")
-    assert n1 > n0, "the forward pass never reached the fp16x3 kernel"
-    assert n2 > n1, "the backward pass never reached the fp16x3 kernel"
-    assert abs(float(lh) - float(lo)) < 2e-5 * abs(float(lo))
-    po = dict(mo.named_parameters())
-    errs = sorted(((float((p.grad.cpu() - po[n].grad).abs().max()) / (float(po[n].grad.abs().max()) + 1e-12), n)
-                   for n, p in mh.named_parameters()), reverse=True)
-    print("worst gradients:", errs[:3])
-    assert all(p.grad is not None for p in mh.parameters())
-    assert errs[0][0] < 2e-3, errs[:8]
-    mo.eval(), mh.eval()
-    with torch.no_grad():
-        nz = 0.1 * torch.randn(B, mel.shape[2] * 256, generator=gen)
-        yo = mo.infer(mel, None, 4, True, noise=nz)
-        n3 = ops.FP16X3_LAUNCHES
-        yh = mh.infer(mel.to(DEV), None, 4, True, noise=nz.to(DEV))
-    err = float((yh.cpu().double() - yo.double()).pow(2).mean().sqrt())
-    print(f"infer: {ops.FP16X3_LAUNCHES - n3} fp16x3 launches, rms {err:.3e}")
-    assert err <= 1e-4, err
+    r = stage1_against_oracle(fp16x3, ("FP16X3_LAUNCHES",), infer=True)
+    print(f"fp16x3 launches: forward {r.fwd[0]}, backward {r.bwd[0]}, inference {r.inf[0]}")
+    assert r.fwd[0] > 0, "the forward pass never reached the fp16x3 kernel"
+    assert r.bwd[0] > 0, "the backward pass never reached the fp16x3 kernel"

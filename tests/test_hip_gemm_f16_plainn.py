@@ -14,39 +14,24 @@ import torch
 
 import fp16x3_emul
 import fp16x3_runtile_emul as emul
-import test_hip_gemm_f16 as h3
+from fp16x3_gpu import (EINVAL, TOL, as_image, assert_declined, cached_image, f16_ok, fp16x3_mode, image_follows_weight,
+                        mode_name, ops, ran, same_bits, stage1_against_oracle)
 from test_hip_gemm_routes import (DEV, EPI, NAN, SENT, Out, Vec, check, expect, last_kernel, launch, make_desc, plain,
                                   products, rnd, run, win1)
 
 pytestmark = pytest.mark.gpu
 
-TOL = h3.TOL
 NAME = "h3n<ep=all>"
-EINVAL = -1
+H3_NAME = "h3<ep=all>"          # the image route's kernel (tests/test_hip_gemm_f16.py)
 CASES = [(p, s) for s in emul.SHAPES for p in emul.PATTERNS]
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from flow2gan_amd import ops as o
-    return o
 
 
 @pytest.fixture
 def plainn_route(ops):
-    """the fp16x3 mode with the new route on from one output column and K = 32; restored through
-    set_gemm_precision"""
-    was = h3.mode_name(ops)
-    keep = ops.FP16X3_MIN_K, ops.FP16X3_MIN_N, ops.FP16X3_PLAINN_MIN_N
-    ops.set_gemm_precision("fp16x3")
-    ops.FP16X3_MIN_K, ops.FP16X3_PLAINN_MIN_N = 32, 1
-    try:
+    """the fp16x3 mode with the new route on from one output column and K = 32"""
+    with fp16x3_mode(ops, "FP16X3_MIN_K", "FP16X3_MIN_N", "FP16X3_PLAINN_MIN_N"):
+        ops.FP16X3_MIN_K, ops.FP16X3_PLAINN_MIN_N = 32, 1
         yield ops
-    finally:
-        ops.FP16X3_MIN_K, ops.FP16X3_MIN_N, ops.FP16X3_PLAINN_MIN_N = keep
-        ops.set_gemm_precision(was)
 
 
 def marked(ops, x):
@@ -57,7 +42,7 @@ def marked(ops, x):
 
 
 def weights(ops, w):
-    return h3.as_image(ops, plain(ops, w.to(DEV)))
+    return as_image(ops, plain(ops, w.to(DEV)))
 
 
 def operands(ops, M, N, K, seed):
@@ -73,8 +58,8 @@ def test_gemm_against_float64(ops, pattern, shape):
     assert A.o.seq_stride > K
     out = Out(M, N)
     d = launch(ops, A, B, out, precision=4)
-    assert last_kernel(ops) == NAME and ops.L.lib.f2g_gemm_last_path() == 6
-    assert h3.f16_ok(ops, d) == 1
+    assert ran(ops, NAME)
+    assert f16_ok(ops, d) == 1
     out.guards_ok()
     want, mag = products(A, B, 0, False)
     floor = emul.tile_amax(x).to(DEV)[:, None] * w.double().abs().sum(1).to(DEV)[None, :]
@@ -112,7 +97,7 @@ def test_gemm_fused_prelu_against_float64(ops, two):
     d.E.prelu_slope = slope.data_ptr()
     if two:
         d.E.prelu_out, d.E.ld_prelu_out = pout.flat.data_ptr() + 4 * pout.base, pout.ldc
-    assert h3.f16_ok(ops, d) == 1
+    assert f16_ok(ops, d) == 1
     ops.call("f2g_gemm", C.byref(d))
     torch.cuda.synchronize()
     assert last_kernel(ops) == NAME
@@ -137,7 +122,7 @@ def test_gemm_mask_epilogue_against_float64(ops):
     cs = Vec(N, 5)
     d = make_desc(ops, A, B, out, precision=4, colsum=cs)
     d.E.mask_src, d.E.mask_slope = y.data_ptr(), 0.1
-    assert h3.f16_ok(ops, d) == 1
+    assert f16_ok(ops, d) == 1
     ops.call("f2g_gemm", C.byref(d))
     torch.cuda.synchronize()
     assert last_kernel(ops) == NAME
@@ -155,13 +140,14 @@ def test_gemm_three_launches_give_the_same_bits(ops):
     x, w = emul.inputs("rising", M, K, N)
     A, B = marked(ops, x), weights(ops, w)
     bias = rnd(N, seed=6)
-    bits = []
-    for _ in range(3):
+
+    def go():
         out = Out(M, N)
         launch(ops, A, B, out, precision=4, bias=bias)
         assert last_kernel(ops) == NAME
-        bits.append(out.flat.view(torch.int32).clone())
-    assert torch.equal(bits[0], bits[1]) and torch.equal(bits[0], bits[2])
+        return out.flat.view(torch.int32).clone()
+
+    same_bits(go)
 
 
 def test_gemm_zero_input_gives_the_epilogue_of_zero(ops):
@@ -242,14 +228,10 @@ def test_descriptors_the_kernel_declines(ops, what):
         d.B.base, d.B.split, d.B.rscale = B.flat.data_ptr() + 4 * B.off, 9, None
     elif what == "form2":
         d.form, d.E.atomic = 2, 1
-    assert h3.f16_ok(ops, d) == (2 if what == "b_fp32" else 0)
-    assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
-    torch.cuda.synchronize()
-    assert last_kernel(ops) == ""
-    assert bool((out.flat[~torch.isnan(out.flat)] == SENT).all())
+    assert_declined(ops, d, out, ok=2 if what == "b_fp32" else 0)
     if what == "b_no_scales":               # ... and the mark is refused at every other precision
         d.B.rscale = B.rs.data_ptr() + 16
-        assert h3.f16_ok(ops, d) == 1
+        assert f16_ok(ops, d) == 1
         for prec in (0, 1, 2, 3):
             d.precision = prec
             assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
@@ -260,7 +242,7 @@ def test_descriptors_the_kernel_declines(ops, what):
 def test_colsum_part_rows_is_zero_for_the_kernel(ops):
     A, B = operands(ops, 129, 160, 160, seed=20)
     d = make_desc(ops, A, B, Out(129, 160), precision=4)
-    assert h3.f16_ok(ops, d) == 1
+    assert f16_ok(ops, d) == 1
     assert ops.L.lib.f2g_gemm_colsum_part_rows(C.byref(d)) == 0
 
 
@@ -311,7 +293,7 @@ def test_ops_gemm_takes_the_route_and_counts_it(plainn_route, monkeypatch):
     # below the threshold: the image route (its own threshold allowing) takes the launch, as before the route existed
     ops.FP16X3_PLAINN_MIN_N, ops.FP16X3_MIN_N = N + 1, 1
     go()
-    assert ops.FP16X3_PLAINN_LAUNCHES == n0 + 2 and ops.FP16X3_LAUNCHES == i0 + 1 and last_kernel(ops) == h3.NAME
+    assert ops.FP16X3_PLAINN_LAUNCHES == n0 + 2 and ops.FP16X3_LAUNCHES == i0 + 1 and last_kernel(ops) == H3_NAME
     ops.FP16X3_PLAINN_MIN_N = N
     go()
     assert ops.FP16X3_PLAINN_LAUNCHES == n0 + 3 and last_kernel(ops) == NAME
@@ -321,19 +303,19 @@ def test_ops_gemm_takes_the_route_and_counts_it(plainn_route, monkeypatch):
         mp.setattr(ops, "call", watch_call)
         ops.gemm(ops.mat(x2), ops.mat(w2), out2)
         torch.cuda.synchronize()
-    assert ops.FP16X3_PLAINN_LAUNCHES == n0 + 3 and last_kernel(ops) not in (NAME, h3.NAME)
+    assert ops.FP16X3_PLAINN_LAUNCHES == n0 + 3 and last_kernel(ops) not in (NAME, H3_NAME)
     assert seen[-1][1] == 0 and images == []
     w2d = w2.detach().double()
     check(out2.double(), x2.double() @ w2d.t(), x2.double().abs() @ w2d.abs().t(), TOL, "the bf16x6 launch")
     ops.set_gemm_precision("bf16x6")
     go()
-    assert ops.FP16X3_PLAINN_LAUNCHES == n0 + 3 and last_kernel(ops) not in (NAME, h3.NAME)
+    assert ops.FP16X3_PLAINN_LAUNCHES == n0 + 3 and last_kernel(ops) not in (NAME, H3_NAME)
 
 
 def test_the_default_leaves_every_launch_as_it_was(ops):
     """with the tunable at its default the counter stays and the output of the fp16x3 mode is bit-identical to the
     image route's launch made by hand"""
-    was = h3.mode_name(ops)
+    was = mode_name(ops)
     keep = ops.FP16X3_MIN_K, ops.FP16X3_MIN_N
     assert ops.FP16X3_PLAINN_MIN_N == ops.FP16X3_TAP_OFF
     M, K, N = 300, 160, 200
@@ -346,15 +328,15 @@ def test_the_default_leaves_every_launch_as_it_was(ops):
         n0, i0 = ops.FP16X3_PLAINN_LAUNCHES, ops.FP16X3_LAUNCHES
         ops.gemm(ops.mat(x), ops.mat(w), out, bias=bias)
         torch.cuda.synchronize()
-        assert ops.FP16X3_PLAINN_LAUNCHES == n0 and ops.FP16X3_LAUNCHES == i0 + 1 and last_kernel(ops) == h3.NAME
+        assert ops.FP16X3_PLAINN_LAUNCHES == n0 and ops.FP16X3_LAUNCHES == i0 + 1 and last_kernel(ops) == H3_NAME
     finally:
         ops.FP16X3_MIN_K, ops.FP16X3_MIN_N = keep
         ops.set_gemm_precision(was)
     # today's launch, by hand: both operands as f2g_split_f16x2 images on gemm_h3_kernel
-    A, B = h3.as_image(ops, plain(ops, x)), h3.as_image(ops, plain(ops, w.detach()))
+    A, B = as_image(ops, plain(ops, x)), as_image(ops, plain(ops, w.detach()))
     ref = Out(M, N)
     launch(ops, A, B, ref, precision=4, bias=bias)
-    assert last_kernel(ops) == h3.NAME
+    assert last_kernel(ops) == H3_NAME
     assert torch.equal(ref.view()[:, :N].contiguous().view(torch.int32), out.view(torch.int32))
 
 
@@ -374,25 +356,12 @@ def test_weight_images_follow_their_weights(plainn_route):
         wd = w.detach().double()
         mag = x.double().abs() @ wd.abs().t() + emul.FLOOR / TOL * floor_a * wd.abs().sum(1)[None, :]
         check(out.double(), x.double() @ wd.t(), mag, TOL, what)
-        img, rs = h3.cached_image(ops, w)
+        img, rs = cached_image(ops, w)
         want_img, want_rs = fp16x3_emul.image(w.detach().cpu())
         assert torch.equal(img, want_img) and torch.equal(rs, want_rs), f"{what}: the cached image is stale"
         return out.clone()
 
-    first = launch_and_check("first launch")
-    factors = torch.logspace(-3, 3, N, device=DEV)
-    version = w._version
-    w.data.copy_(w.detach() * factors[:, None])
-    assert w._version == version            # (invisible to autograd: only the epoch tells the cache)
-    ops.bump_weight_epoch([w])
-    replayed = ops.rebuild_derived([w])
-    assert replayed >= 1 or not ops.EAGER_REBUILD
-    second = launch_and_check("after the raw-pointer update")
-    assert not torch.equal(first, second)
-    with torch.no_grad():
-        w.mul_(-0.37)
-    third = launch_and_check("after the in-place update")
-    assert not torch.equal(second, third)
+    image_follows_weight(ops, w, launch_and_check)
 
 
 # ------------------------------------------------------------------ model level, against the CPU oracle
@@ -401,15 +370,9 @@ def test_stage1_and_infer_against_oracle(plainn_route):
     on: the stage-1 loss, all gradients and 4-step inference; forward and backward both reach the new kernel and the
     image route takes nothing"""
     ops = plainn_route
-
-    class Counting:
-        """ops with FP16X3_LAUNCHES read as the new route's counter: the construction asserts that forward and backward
-        reached the kernel under test"""
-        def __getattr__(self, name):
-            return ops.FP16X3_PLAINN_LAUNCHES if name == "FP16X3_LAUNCHES" else getattr(ops, name)
-
-    i0 = ops.FP16X3_LAUNCHES
-    n0 = ops.FP16X3_PLAINN_LAUNCHES
-    h3.test_stage1_and_infer_against_oracle(Counting())
-    print(f"launches on the route: {ops.FP16X3_PLAINN_LAUNCHES - n0}; on the image route: {ops.FP16X3_LAUNCHES - i0}")
-    assert ops.FP16X3_PLAINN_LAUNCHES > n0 and ops.FP16X3_LAUNCHES == i0
+    r = stage1_against_oracle(ops, ("FP16X3_PLAINN_LAUNCHES", "FP16X3_LAUNCHES"), infer=True)
+    print(f"launches on the route: forward {r.fwd[0]}, backward {r.bwd[0]}, inference {r.inf[0]}; on the image route: "
+          f"{r.fwd[1] + r.bwd[1] + r.inf[1]}")
+    assert r.fwd[0] > 0, "the forward pass never reached the kernel"
+    assert r.bwd[0] > 0, "the backward pass never reached the kernel"
+    assert r.fwd[1] == r.bwd[1] == r.inf[1] == 0, "the image route took a launch"

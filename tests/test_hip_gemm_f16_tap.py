@@ -7,70 +7,36 @@ Tolerance of the GEMM cases, per element: 1.8e-6 * (|A| |B|^T + |epilogue terms|
 fp32 accumulation plus the arithmetic's 3 * 2^-22 per product, as tests/test_hip_gemm_f16.py -- plus the floor term of
 the per-sequence scale, 2^-28 amax_seq(row) sum_k |w[n,k]|, carried through the epilogue like a product's scale."""
 import ctypes as C
-import math
-import types
 
 import pytest
 import torch
 
 import fp16x3_seq_emul as emul
-from test_hip_gemm_routes import DEV, NAN, SENT, Op, Out, Vec, check, expect, last_kernel, make_desc, plain, products, rnd
+from fp16x3_gpu import (EINVAL, TOL, any_grid, assert_declined, case, f16_ok, fp16x3_mode, image_follows_weight, ops,
+                        ran, same_bits, scale_rows, subdisc_against_oracle)
+from test_hip_gemm_routes import DEV, NAN, SENT, Out, Vec, check, expect, last_kernel, make_desc, rnd
 
 pytestmark = pytest.mark.gpu
 
-TOL = 1.8e-6
-EINVAL = -1
 SHAPES = [(5, 64, 64, 128),      # 320 rows: one full and one quarter row tile
           (7, 50, 96, 128),      # a wave group's 128 rows straddle three sequences; three channel slabs
           (5, 64, 64, 160)]      # a partial column tile
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from flow2gan_amd import ops as o
-    return o
-
-
-@pytest.fixture
-def any_grid(lib_option):
-    """library option x6p = 2: the tap-walking kernels take grids that do not fill the chip"""
-    lib_option("x6p", 2)
-
-
-def mode_name(ops):
-    return "fp16x3" if ops.FP16X3 else {0: "fp32", 1: "bf16x3", 2: "bf16", 3: "bf16x6"}[ops.GEMM_PRECISION]
 
 
 @pytest.fixture
 def tap_route_rows(ops, any_grid):
     """the fp16x3 mode as shipped with the two settings the end-to-end test names: FP16X3_TAP_MIN_ROWS = 1 and the
     library option x6p = 2"""
-    was, was_rows = mode_name(ops), ops.FP16X3_TAP_MIN_ROWS
-    ops.set_gemm_precision("fp16x3")
-    ops.FP16X3_TAP_MIN_ROWS = 1
-    try:
+    with fp16x3_mode(ops, "FP16X3_TAP_MIN_ROWS", "X6_MIN_K"):
+        ops.FP16X3_TAP_MIN_ROWS = 1
         yield ops
-    finally:
-        ops.FP16X3_TAP_MIN_ROWS = was_rows
-        ops.set_gemm_precision(was)
 
 
 @pytest.fixture
 def tap_route(tap_route_rows):
     """... and reductions from 32 on (the ops.gemm cases have 64 channels: K = 320 and 128)"""
-    ops = tap_route_rows
-    was_k = ops.X6_MIN_K
-    ops.X6_MIN_K = 32
-    try:
-        yield ops
-    finally:
-        ops.X6_MIN_K = was_k
-
-
-def f16_ok(ops, d):
-    return ops.L.lib.f2g_gemm_f16_ok(C.byref(d))
+    tap_route_rows.X6_MIN_K = 32
+    return tap_route_rows
 
 
 # ------------------------------------------------------------------ the image
@@ -125,44 +91,6 @@ def test_seq_image_declines_what_it_cannot_lay_out(ops):
     torch.cuda.synchronize()
 
 
-# ------------------------------------------------------------------ operands
-def seq_image(ops, op, nseq, run, ld):
-    """replace the fp32 operand `op` (test_hip_gemm_routes.Op over a NaN-poisoned buffer) by its f2g_split_f16x2_seq
-    image: a copy of the buffer -- poison included -- whose runs the image routine rewrote"""
-    op.img = op.flat.clone()
-    op.rs = torch.full((nseq + 8,), NAN, device=DEV)
-    ops.call("f2g_split_f16x2_seq", op.img.data_ptr() + 4 * op.off, op.rs.data_ptr() + 16,
-             op.flat.data_ptr() + 4 * op.off, ld, nseq, run)
-    op.o.base, op.o.split, op.o.rscale = op.img.data_ptr() + 4 * op.off, 7, op.rs.data_ptr() + 16
-    return op
-
-
-def halo_windows(ops, x, P0, taps, step=1):
-    """stride-`step` windows of `taps` positions over the contiguous map x (S, Hp, C), NaN behind the last sequence"""
-    S, Hp, Cc = x.shape
-    flat = torch.full((S * Hp * Cc + 256 * Cc,), NAN, device=DEV)
-    flat[:S * Hp * Cc] = x.reshape(-1)
-    return Op(ops, flat, 0, 0, rows=S * P0, cols=taps * Cc, P0=P0, step0=step, pad0=0, unit=Cc, L0u=Hp * Cc,
-              seq_stride=Hp * Cc)
-
-
-def case(ops, S, P0, Cc, N, taps, seed=0, step=1, extra=0, images=True):
-    """A (windows over a map whose sequences span 60 decades: a scale taken from the wrong sequence is wrong by
-    orders of magnitude), B (the weights), the floor term of every output, float64 products and their scale"""
-    Hp = step * (P0 - 1) + taps + extra
-    x = rnd(S, Hp, Cc, seed=seed + taps) * torch.logspace(-30, 30, S, device=DEV)[:, None, None]
-    w = rnd(N, taps * Cc, seed=seed + 50, scale=(taps * Cc) ** -0.5)
-    A = halo_windows(ops, x, P0, taps, step)
-    B = plain(ops, w, pad=0)
-    if images:
-        seq_image(ops, A, S, Hp * Cc, Hp * Cc)
-        seq_image(ops, B, N, taps * Cc, B.o.seq_stride)
-    amax = x.double().abs().reshape(S, -1).amax(1).repeat_interleave(P0)
-    floor = emul.FLOOR * amax[:, None] * w.double().abs().sum(1)[None, :]
-    acc, mag = products(A, B, 0, False)
-    return types.SimpleNamespace(A=A, B=B, x=x, w=w, acc=acc, mag=mag + floor / TOL, M=S * P0, N=N, Hp=Hp)
-
-
 # ------------------------------------------------------------------ GEMM against float64
 @pytest.mark.parametrize("taps", [5, 2])
 @pytest.mark.parametrize("S,P0,Cc,N", SHAPES)
@@ -175,7 +103,7 @@ def test_forward_epilogue_against_float64(ops, any_grid, S, P0, Cc, N, taps):
     assert f16_ok(ops, d) == 1
     ops.call("f2g_gemm", C.byref(d))
     torch.cuda.synchronize()
-    assert last_kernel(ops) == f"h3p<taps={taps}>" and ops.L.lib.f2g_gemm_last_path() == 6
+    assert ran(ops, f"h3p<taps={taps}>")
     out.guards_ok()
     want, m, _, _ = expect(c.acc, c.mag, bias=bias, lrelu=0.1)
     check(out.got(), want, m, TOL, "forward")
@@ -205,7 +133,7 @@ def test_data_gradient_epilogue_against_float64(ops, any_grid, S, P0, Cc, N, tap
     assert f16_ok(ops, d) == 1
     ops.call("f2g_gemm", C.byref(d))
     torch.cuda.synchronize()
-    assert last_kernel(ops) == f"h3p<taps={taps}>" and ops.L.lib.f2g_gemm_last_path() == 6
+    assert ran(ops, f"h3p<taps={taps}>")
     out.guards_ok()
     yy, rr = y_full[out.offs].double(), ref_full[out.offs].double()
     v = c.acc + fmw * 0.5 * torch.sign(yy - rr)
@@ -298,14 +226,15 @@ def test_x3_out_of_a_row_mapped_masked_data_gradient(ops, any_grid, taps):
 
 def test_three_launches_give_the_same_bits(ops, any_grid):
     c = case(ops, *SHAPES[1], 5, seed=4)
-    bits = []
-    for _ in range(3):
+
+    def go():
         out = Out(c.M, c.N)
         d = make_desc(ops, c.A, c.B, out, precision=4)
         ops.call("f2g_gemm", C.byref(d))
         torch.cuda.synchronize()
-        bits.append(out.flat.view(torch.int32).clone())
-    assert torch.equal(bits[0], bits[1]) and torch.equal(bits[0], bits[2])
+        return out.flat.view(torch.int32).clone()
+
+    same_bits(go)
 
 
 # ------------------------------------------------------------------ refusals
@@ -321,11 +250,7 @@ def test_descriptors_the_kernel_declines(ops, lib_option, what):
     d = make_desc(ops, c.A, c.B, out, precision=4)
     if what == "no_scales":
         d.A.rscale = None
-    assert f16_ok(ops, d) == 0
-    assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
-    torch.cuda.synchronize()
-    assert last_kernel(ops) == ""
-    assert bool((out.flat[~torch.isnan(out.flat)] == SENT).all())
+    assert_declined(ops, d, out)
     for prec in (0, 1, 2, 3):           # ... and the images are refused at every other precision
         d.precision = prec
         assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
@@ -398,22 +323,7 @@ def test_weight_images_follow_their_weights(tap_route):
         assert torch.equal(img, want_img) and torch.equal(rs, want_rs), f"{what}: the cached image is stale"
         return out.clone()
 
-    first = launch_and_check("first launch")
-    # 1. raw-pointer write of every row by its own factor (the row scales must move too), as the optimizer does
-    factors = torch.logspace(-3, 3, N, device=DEV)
-    version = w._version
-    w.data.copy_(w.detach() * factors[:, None])
-    assert w._version == version            # (invisible to autograd: only the epoch tells the cache)
-    ops.bump_weight_epoch([w])
-    replayed = ops.rebuild_derived([w])
-    assert replayed >= 1 or not ops.EAGER_REBUILD
-    second = launch_and_check("after the raw-pointer update")
-    assert not torch.equal(first, second)
-    # 2. autograd-visible in-place update: rebuilt at the next use
-    with torch.no_grad():
-        w.mul_(-0.37)
-    third = launch_and_check("after the in-place update")
-    assert not torch.equal(second, third)
+    image_follows_weight(ops, w, launch_and_check)
 
 
 def test_images_of_re_laid_weights_follow_their_weights(tap_route):
@@ -448,8 +358,7 @@ def test_images_of_re_laid_weights_follow_their_weights(tap_route):
         return buf
 
     first = launch_and_check("first launch")
-    factors = torch.logspace(-3, 3, N, device=DEV)
-    w.data.copy_(w.detach() * factors[:, None, None, None])
+    scale_rows(w)
     ops.bump_weight_epoch([w])
     replayed = ops.rebuild_derived([w])
     assert replayed >= 2 or not ops.EAGER_REBUILD          # (the packed copy and the image under it)
@@ -466,43 +375,9 @@ def test_mpd_period_against_oracle(tap_route_rows):
     counts the fifth layer's forward and its data gradient (and the two-tap residues of the layer below), and
     nothing when it is off"""
     ops = tap_route_rows
-    import test_hip_disc_autograd as T
-    do, dh = T._models("mpd")
-    sub_o, sub_h = do.discriminators[0], dh.discriminators[0]
-    _, y_hat = T._inputs()
-
-    def loss_of(score, fmap):
-        gen = torch.Generator().manual_seed(77)
-        loss = torch.relu(1 + score).mean()
-        for m in fmap:
-            loss = loss + (m * torch.randn(m.shape, generator=gen).to(m.device)).sum() / math.sqrt(m.numel())
-        return loss
-
-    def hip_run():
-        for p in sub_h.parameters():
-            p.grad = None
-        yh = y_hat.to(DEV).requires_grad_(True)
-        n0 = ops.FP16X3_TAP_LAUNCHES
-        score, fmap = sub_h(yh)
-        n1 = ops.FP16X3_TAP_LAUNCHES
-        loss_of(score, fmap).backward()
-        torch.cuda.synchronize()
-        return score, fmap, yh.grad, n1 - n0, ops.FP16X3_TAP_LAUNCHES - n1
-
-    score, fmap, gx, fwd, bwd = hip_run()
-    print(f"[h3p] period {sub_h.period}: {fwd} forward and {bwd} backward launches on the route")
-    assert fwd >= 1, "the fifth layer's forward never reached the kernel"
-    assert bwd >= 1, "the fifth layer's data gradient never reached the kernel"
-    sides = T._hip_sides(types.SimpleNamespace(discriminators=[sub_h]), "mpd", y_hat.to(DEV))[0]
-    yo = y_hat.clone().requires_grad_(True)
-    do.zero_grad(set_to_none=True)
-    so, fo = T._with_sides(sides, lambda: sub_o(yo))
-    loss_of(so, fo).backward()
-    pairs = [("score", score, so.detach())] + [(f"fmap.{i}", m, fo[i].detach()) for i, m in enumerate(fmap)]
-    pairs += [("y_hat", gx, yo.grad)]
-    pairs += [(k, p.grad, dict(sub_o.named_parameters())[k].grad) for k, p in sub_h.named_parameters()]
-    do.zero_grad(set_to_none=True)
-    T._compare(pairs, "mpd period 2, fp16x3 tap route")
+    r = subdisc_against_oracle(ops, "mpd", ("FP16X3_TAP_LAUNCHES",), "mpd period 2, fp16x3 tap route")
+    print(f"[h3p] period {r.sub.period}: {r.fwd[0]} forward and {r.bwd[0]} backward launches on the route")
+    assert r.fwd[0] >= 1, "the fifth layer's forward never reached the kernel"
+    assert r.bwd[0] >= 1, "the fifth layer's data gradient never reached the kernel"
     ops.FP16X3_TAP_MIN_ROWS = ops.FP16X3_TAP_OFF
-    _, _, _, fwd, bwd = hip_run()
-    assert fwd == 0 and bwd == 0
+    assert r.rerun() == ((0,), (0,))

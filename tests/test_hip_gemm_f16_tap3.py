@@ -1,5 +1,5 @@
 """fp16x3 over STRIDE-3 windows of five positions of a halo map on the GPU (csrc/gemm_f16p3.hip, gemm_h3p3_kernel):
-against float64 over poisoned operands and guarded outputs with the helpers of tests/test_hip_gemm_f16_tap.py (which
+against float64 over poisoned operands and guarded outputs with the helpers of tests/fp16x3_gpu.py (which
 take the window stride and the extra positions behind a sequence's last window) and tests/test_hip_gemm_routes.py,
 the descriptors it must decline, the ops.gemm route with its tunable and counter, the cached weight image following
 its weight, and one period of the MPD against the CPU oracle.
@@ -12,14 +12,13 @@ staging bound is 130 + 126 / P0 <= 144 entries per residue plane (a group's 128 
 touch, one for the taps' overhang).  The descriptor that breaks it has P0 = 8; a map with 40 unread positions behind
 every sequence is accepted and computed (test_distance_between_sequences_is_free)."""
 import ctypes as C
-import math
-import types
 
 import pytest
 import torch
 
 import fp16x3_seq3_emul as emul
-from test_hip_gemm_f16_tap import EINVAL, TOL, case, f16_ok, mode_name
+from fp16x3_gpu import (EINVAL, TOL, any_grid, assert_declined, case, f16_ok, fp16x3_mode, image_follows_weight, ops,
+                        ran, same_bits, subdisc_against_oracle)
 from test_hip_gemm_routes import DEV, NAN, SENT, Out, Vec, check, expect, last_kernel, make_desc, rnd
 
 pytestmark = pytest.mark.gpu
@@ -32,31 +31,12 @@ SHAPES = [(3, 100, 128, 128, 2),     # 300 rows: one full 256-row tile and a par
           (4, 70, 256, 128, 4)]      # eight channel slabs, the largest seam
 
 
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from flow2gan_amd import ops as o
-    return o
-
-
-@pytest.fixture
-def any_grid(lib_option):
-    """library option x6p = 2: the tap-walking kernels take grids that do not fill the chip"""
-    lib_option("x6p", 2)
-
-
 @pytest.fixture
 def tap3_route(ops, any_grid):
     """the fp16x3 mode as shipped, with FP16X3_TAP3_MIN_ROWS = 1 and the library option x6p = 2"""
-    was, was_rows = mode_name(ops), ops.FP16X3_TAP3_MIN_ROWS
-    ops.set_gemm_precision("fp16x3")
-    ops.FP16X3_TAP3_MIN_ROWS = 1
-    try:
+    with fp16x3_mode(ops, "FP16X3_TAP3_MIN_ROWS"):
+        ops.FP16X3_TAP3_MIN_ROWS = 1
         yield ops
-    finally:
-        ops.FP16X3_TAP3_MIN_ROWS = was_rows
-        ops.set_gemm_precision(was)
 
 
 _CASES = {}
@@ -82,7 +62,7 @@ def forward_check(ops, c, P0, N):
     assert f16_ok(ops, d) == 1
     ops.call("f2g_gemm", C.byref(d))
     torch.cuda.synchronize()
-    assert last_kernel(ops) == NAME and ops.L.lib.f2g_gemm_last_path() == 6
+    assert ran(ops, NAME)
     out.guards_ok()
     want, m, _, _ = expect(c.acc, c.mag, bias=bias, lrelu=0.1)
     check(out.got(), want, m, TOL, "forward")
@@ -126,7 +106,7 @@ def test_column_sums_mask_and_feature_matching_against_float64(ops, any_grid, i)
     assert f16_ok(ops, d) == 1
     ops.call("f2g_gemm", C.byref(d))
     torch.cuda.synchronize()
-    assert last_kernel(ops) == NAME and ops.L.lib.f2g_gemm_last_path() == 6
+    assert ran(ops, NAME)
     out.guards_ok()
     yy, rr = y_full[out.offs].double(), ref_full[out.offs].double()
     v = c.acc + fmw * 0.5 * torch.sign(yy - rr)
@@ -186,15 +166,16 @@ def test_x3_out_of_the_row_mapped_forward(ops, any_grid):
 
 def test_three_launches_give_the_same_bits(ops, any_grid):
     c = shared_case(ops, 1)
-    bits = []
-    for _ in range(3):
+
+    def go():
         out = Out(c.M, c.N)
         d = make_desc(ops, c.A, c.B, out, precision=4)
         ops.call("f2g_gemm", C.byref(d))
         torch.cuda.synchronize()
         assert last_kernel(ops) == NAME
-        bits.append(out.flat.view(torch.int32).clone())
-    assert torch.equal(bits[0], bits[1]) and torch.equal(bits[0], bits[2])
+        return out.flat.view(torch.int32).clone()
+
+    same_bits(go)
 
 
 # ------------------------------------------------------------------ refusals
@@ -213,11 +194,7 @@ def test_descriptors_the_kernel_declines(ops, lib_option, what):
         d.A.rscale = None
     if what == "pad0":
         d.A.pad0 = 1
-    assert f16_ok(ops, d) == 0
-    assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
-    torch.cuda.synchronize()
-    assert last_kernel(ops) == ""
-    assert bool((out.flat[~torch.isnan(out.flat)] == SENT).all())
+    assert_declined(ops, d, out)
 
 
 # ------------------------------------------------------------------ ops.gemm
@@ -286,20 +263,7 @@ def test_weight_images_follow_their_weights(tap3_route):
         assert torch.equal(img, want_img) and torch.equal(rs, want_rs), f"{what}: the cached image is stale"
         return out.clone()
 
-    first = launch_and_check("first launch")
-    factors = torch.logspace(-3, 3, N, device=DEV)
-    version = w._version
-    w.data.copy_(w.detach() * factors[:, None])
-    assert w._version == version            # (invisible to autograd: only the epoch tells the cache)
-    ops.bump_weight_epoch([w])
-    replayed = ops.rebuild_derived([w])
-    assert replayed >= 1 or not ops.EAGER_REBUILD
-    second = launch_and_check("after the raw-pointer update")
-    assert not torch.equal(first, second)
-    with torch.no_grad():
-        w.mul_(-0.37)
-    third = launch_and_check("after the in-place update")
-    assert not torch.equal(second, third)
+    image_follows_weight(ops, w, launch_and_check)
 
 
 # ------------------------------------------------------------------ one period of the MPD against the CPU oracle
@@ -309,42 +273,8 @@ def test_mpd_period_against_oracle(tap3_route):
     against the oracle at that file's tolerance; the route counts one forward launch per stride-3 layer with 128 and
     512 input channels, and nothing when it is off"""
     ops = tap3_route
-    import test_hip_disc_autograd as T
-    do, dh = T._models("mpd")
-    sub_o, sub_h = do.discriminators[0], dh.discriminators[0]
-    _, y_hat = T._inputs()
-
-    def loss_of(score, fmap):
-        gen = torch.Generator().manual_seed(77)
-        loss = torch.relu(1 + score).mean()
-        for m in fmap:
-            loss = loss + (m * torch.randn(m.shape, generator=gen).to(m.device)).sum() / math.sqrt(m.numel())
-        return loss
-
-    def hip_run():
-        for p in sub_h.parameters():
-            p.grad = None
-        yh = y_hat.to(DEV).requires_grad_(True)
-        n0 = ops.FP16X3_TAP3_LAUNCHES
-        score, fmap = sub_h(yh)
-        n1 = ops.FP16X3_TAP3_LAUNCHES
-        loss_of(score, fmap).backward()
-        torch.cuda.synchronize()
-        return score, fmap, yh.grad, n1 - n0
-
-    score, fmap, gx, fwd = hip_run()
-    print(f"[h3p3] period {sub_h.period}: {fwd} forward launches on the route")
-    assert fwd >= 2, "a stride-3 layer's forward never reached the kernel"
-    sides = T._hip_sides(types.SimpleNamespace(discriminators=[sub_h]), "mpd", y_hat.to(DEV))[0]
-    yo = y_hat.clone().requires_grad_(True)
-    do.zero_grad(set_to_none=True)
-    so, fo = T._with_sides(sides, lambda: sub_o(yo))
-    loss_of(so, fo).backward()
-    pairs = [("score", score, so.detach())] + [(f"fmap.{i}", m, fo[i].detach()) for i, m in enumerate(fmap)]
-    pairs += [("y_hat", gx, yo.grad)]
-    pairs += [(k, p.grad, dict(sub_o.named_parameters())[k].grad) for k, p in sub_h.named_parameters()]
-    do.zero_grad(set_to_none=True)
-    T._compare(pairs, "mpd period 2, fp16x3 stride-3 tap route")
+    r = subdisc_against_oracle(ops, "mpd", ("FP16X3_TAP3_LAUNCHES",), "mpd period 2, fp16x3 stride-3 tap route")
+    print(f"[h3p3] period {r.sub.period}: {r.fwd[0]} forward launches on the route")
+    assert r.fwd[0] >= 2, "a stride-3 layer's forward never reached the kernel"
     ops.FP16X3_TAP3_MIN_ROWS = ops.FP16X3_TAP_OFF
-    _, _, _, fwd = hip_run()
-    assert fwd == 0
+    assert r.rerun()[0] == (0,)

@@ -1,6 +1,6 @@
 """fp16x3 over STRIDE-3 windows of five positions of a 32-channel halo map, scaled per sequence segment INSIDE the kernel
 (csrc/gemm_f16p3n.hip, gemm_h3p3n_kernel; f2g_operand.split = 8): against float64 over poisoned operands and guarded
-outputs with the helpers of tests/test_hip_gemm_f16_tap.py and tests/test_hip_gemm_routes.py, the descriptors it must
+outputs with the helpers of tests/fp16x3_gpu.py and tests/test_hip_gemm_routes.py, the descriptors it must
 decline, the ops.gemm route with its tunable and counter, the cached weight image following its weight, and one period
 of the MPD against the CPU oracle.
 
@@ -12,14 +12,13 @@ Tolerance, per element, as tests/test_hip_gemm_f16_tap.py: 1.8e-6 * (|A| |B|^T +
 2^-28 amax_seq(row) sum_k |w[n,k]| carried through the epilogue like a product's scale; a segment's maximum is at most
 its sequence's, so the per-sequence floor bounds the per-segment one (tests/fp16x3_seg_emul.py has the exact bound)."""
 import ctypes as C
-import math
-import types
 
 import pytest
 import torch
 
 import fp16x3_seq3_emul as emul
-from test_hip_gemm_f16_tap import EINVAL, TOL, case, f16_ok, mode_name, seq_image
+from fp16x3_gpu import (EINVAL, TOL, any_grid, assert_declined, case, f16_ok, fp16x3_mode, image_follows_weight, ops,
+                        ran, same_bits, seq_image, subdisc_against_oracle, watching_gemm_calls)
 from test_hip_gemm_routes import DEV, NAN, SENT, Out, Vec, check, expect, last_kernel, make_desc, rnd
 
 pytestmark = pytest.mark.gpu
@@ -32,35 +31,16 @@ SHAPES = [(3, 100, 32, 128, 2),      # 300 rows: two full 128-row tiles and a pa
           (40, 8, 32, 128, 0)]       # the most segments per tile the host rule admits
 
 
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from flow2gan_amd import ops as o
-    return o
-
-
-@pytest.fixture
-def any_grid(lib_option):
-    """library option x6p = 2: the tap-walking kernels take grids that do not fill the chip"""
-    lib_option("x6p", 2)
-
-
 @pytest.fixture
 def tap3n_route(ops, any_grid):
     """the fp16x3 mode as shipped, with FP16X3_TAP3N_MIN_ROWS = 1 and the library option x6p = 2"""
-    was, was_rows = mode_name(ops), ops.FP16X3_TAP3N_MIN_ROWS
-    ops.set_gemm_precision("fp16x3")
-    ops.FP16X3_TAP3N_MIN_ROWS = 1
-    try:
+    with fp16x3_mode(ops, "FP16X3_TAP3N_MIN_ROWS"):
+        ops.FP16X3_TAP3N_MIN_ROWS = 1
         yield ops
-    finally:
-        ops.FP16X3_TAP3N_MIN_ROWS = was_rows
-        ops.set_gemm_precision(was)
 
 
 def seg_case(ops, S, P0, Cc, N, taps=TAPS, seed=0, step=STEP, extra=0):
-    """case() of tests/test_hip_gemm_f16_tap.py with A left the fp32 map and marked split = 8, the positions no window
+    """case() of tests/fp16x3_gpu.py with A left the fp32 map and marked split = 8, the positions no window
     reads poisoned, and B replaced by its f2g_split_f16x2_seq image"""
     c = case(ops, S, P0, Cc, N, taps, seed=seed, step=step, extra=extra, images=False)
     read = step * (P0 - 1) + taps
@@ -94,7 +74,7 @@ def forward_check(ops, c, P0, N):
     assert f16_ok(ops, d) == 1
     ops.call("f2g_gemm", C.byref(d))
     torch.cuda.synchronize()
-    assert last_kernel(ops) == NAME and ops.L.lib.f2g_gemm_last_path() == 6
+    assert ran(ops, NAME)
     out.guards_ok()
     want, m, _, _ = expect(c.acc, c.mag, bias=bias, lrelu=0.1)
     check(out.got(), want, m, TOL, "forward")
@@ -136,7 +116,7 @@ def test_column_sums_mask_and_feature_matching_against_float64(ops, any_grid, i)
     assert f16_ok(ops, d) == 1
     ops.call("f2g_gemm", C.byref(d))
     torch.cuda.synchronize()
-    assert last_kernel(ops) == NAME and ops.L.lib.f2g_gemm_last_path() == 6
+    assert ran(ops, NAME)
     out.guards_ok()
     yy, rr = y_full[out.offs].double(), ref_full[out.offs].double()
     v = c.acc + fmw * 0.5 * torch.sign(yy - rr)
@@ -197,15 +177,16 @@ def test_x3_out_of_the_row_mapped_forward(ops, any_grid):
 @pytest.mark.parametrize("i", [1, 2])
 def test_three_launches_give_the_same_bits(ops, any_grid, i):
     c = shared_case(ops, i)
-    bits = []
-    for _ in range(3):
+
+    def go():
         out = Out(c.M, c.N)
         d = make_desc(ops, c.A, c.B, out, precision=4)
         ops.call("f2g_gemm", C.byref(d))
         torch.cuda.synchronize()
         assert last_kernel(ops) == NAME
-        bits.append(out.flat.view(torch.int32).clone())
-    assert torch.equal(bits[0], bits[1]) and torch.equal(bits[0], bits[2])
+        return out.flat.view(torch.int32).clone()
+
+    same_bits(go)
 
 
 # ------------------------------------------------------------------ refusals
@@ -231,11 +212,7 @@ def test_descriptors_the_kernel_declines(ops, lib_option, what):
         # A.split == 0 with unit == 32: what the parent commit answered -- its stride-3 kernel asks for unit % 128 == 0
         # (gemm_common.h: x6_tap3_ok) and a descriptor it declines is offered to no other kernel
         d.A.split = 0
-    assert f16_ok(ops, d) == 0
-    assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
-    torch.cuda.synchronize()
-    assert last_kernel(ops) == ""
-    assert bool((out.flat[~torch.isnan(out.flat)] == SENT).all())
+    assert_declined(ops, d, out)
 
 
 # ------------------------------------------------------------------ ops.gemm
@@ -256,27 +233,12 @@ def test_ops_gemm_takes_the_route_and_counts_it(tap3n_route, monkeypatch):
     w, bias = torch.nn.Parameter(rnd(N, TAPS * Cc, seed=7, scale=0.1)), rnd(N, seed=8)
     out = torch.full((S * P0, N), NAN, device=DEV)
     ops._f16_seq_operand(ops.mat(w))        # (the weight's cached image: built before the launches are watched)
-    seen, images = [], []
-    real_call, real_image = ops.call, ops.split_f16_seq
-
-    def watch_call(name, *args):
-        if name == "f2g_gemm":
-            d = args[0]._obj                # (C.byref's object: the descriptor as it is launched)
-            seen.append((d.A.base, d.A.split, bool(d.A.rscale), d.B.split, bool(d.B.rscale)))
-        return real_call(name, *args)
-
-    def watch_image(*args, **kw):
-        images.append(args)
-        return real_image(*args, **kw)
-
     def go():
         ops.gemm(ops.win1d(flat, S, Hp, Cc, P0, STEP, 0, TAPS), ops.mat(w), out, bias=bias, lrelu=0.1)
         torch.cuda.synchronize()
 
     n0, t0, t3 = ops.FP16X3_TAP3N_LAUNCHES, ops.FP16X3_TAP_LAUNCHES, ops.FP16X3_TAP3_LAUNCHES
-    with monkeypatch.context() as mp:
-        mp.setattr(ops, "call", watch_call)
-        mp.setattr(ops, "split_f16_seq", watch_image)
+    with watching_gemm_calls(ops, monkeypatch, "split_f16_seq") as (seen, images):
         go()
     assert ops.FP16X3_TAP3N_LAUNCHES == n0 + 1 and last_kernel(ops) == NAME
     # no per-call image of A: the launch reads the caller's map itself, and nothing built an image meanwhile
@@ -323,20 +285,7 @@ def test_weight_images_follow_their_weights(tap3n_route):
         assert torch.equal(img, want_img) and torch.equal(rs, want_rs), f"{what}: the cached image is stale"
         return out.clone()
 
-    first = launch_and_check("first launch")
-    factors = torch.logspace(-3, 3, N, device=DEV)
-    version = w._version
-    w.data.copy_(w.detach() * factors[:, None])
-    assert w._version == version            # (invisible to autograd: only the epoch tells the cache)
-    ops.bump_weight_epoch([w])
-    replayed = ops.rebuild_derived([w])
-    assert replayed >= 1 or not ops.EAGER_REBUILD
-    second = launch_and_check("after the raw-pointer update")
-    assert not torch.equal(first, second)
-    with torch.no_grad():
-        w.mul_(-0.37)
-    third = launch_and_check("after the in-place update")
-    assert not torch.equal(second, third)
+    image_follows_weight(ops, w, launch_and_check)
 
 
 # ------------------------------------------------------------------ one period of the MPD against the CPU oracle
@@ -345,42 +294,9 @@ def test_mpd_period_against_oracle(tap3n_route):
     gradient and every parameter gradient against the oracle at that file's tolerance; the route counts at least one
     forward launch (the 32 -> 128 layer), and nothing when it is off"""
     ops = tap3n_route
-    import test_hip_disc_autograd as T
-    do, dh = T._models("mpd")
-    sub_o, sub_h = do.discriminators[0], dh.discriminators[0]
-    _, y_hat = T._inputs()
-
-    def loss_of(score, fmap):
-        gen = torch.Generator().manual_seed(77)
-        loss = torch.relu(1 + score).mean()
-        for m in fmap:
-            loss = loss + (m * torch.randn(m.shape, generator=gen).to(m.device)).sum() / math.sqrt(m.numel())
-        return loss
-
-    def hip_run():
-        for p in sub_h.parameters():
-            p.grad = None
-        yh = y_hat.to(DEV).requires_grad_(True)
-        n0 = ops.FP16X3_TAP3N_LAUNCHES
-        score, fmap = sub_h(yh)
-        n1 = ops.FP16X3_TAP3N_LAUNCHES
-        loss_of(score, fmap).backward()
-        torch.cuda.synchronize()
-        return score, fmap, yh.grad, n1 - n0
-
-    score, fmap, gx, fwd = hip_run()
-    print(f"[h3p3n] period {sub_h.period}: {fwd} forward launches on the route")
-    assert fwd >= 1, "the 32 -> 128 layer's forward never reached the kernel"
-    sides = T._hip_sides(types.SimpleNamespace(discriminators=[sub_h]), "mpd", y_hat.to(DEV))[0]
-    yo = y_hat.clone().requires_grad_(True)
-    do.zero_grad(set_to_none=True)
-    so, fo = T._with_sides(sides, lambda: sub_o(yo))
-    loss_of(so, fo).backward()
-    pairs = [("score", score, so.detach())] + [(f"fmap.{i}", m, fo[i].detach()) for i, m in enumerate(fmap)]
-    pairs += [("y_hat", gx, yo.grad)]
-    pairs += [(k, p.grad, dict(sub_o.named_parameters())[k].grad) for k, p in sub_h.named_parameters()]
-    do.zero_grad(set_to_none=True)
-    T._compare(pairs, "mpd period 2, fp16x3 in-kernel-scaled tap route")
+    r = subdisc_against_oracle(ops, "mpd", ("FP16X3_TAP3N_LAUNCHES",),
+                               "mpd period 2, fp16x3 in-kernel-scaled tap route")
+    print(f"[h3p3n] period {r.sub.period}: {r.fwd[0]} forward launches on the route")
+    assert r.fwd[0] >= 1, "the 32 -> 128 layer's forward never reached the kernel"
     ops.FP16X3_TAP3N_MIN_ROWS = ops.FP16X3_TAP_OFF
-    _, _, _, fwd = hip_run()
-    assert fwd == 0
+    assert r.rerun()[0] == (0,)

@@ -1,6 +1,6 @@
 """fp16x3 over STRIDE-1 windows of two or one positions of a 128-channel halo map onto at most 32 columns, scaled per
 sequence segment INSIDE the kernel (csrc/gemm_f16pn.hip, gemm_h3pn_kernel<2 / 1>; f2g_operand.split = 8): against
-float64 over poisoned operands and guarded outputs with the helpers of tests/test_hip_gemm_f16_tap.py and
+float64 over poisoned operands and guarded outputs with the helpers of tests/fp16x3_gpu.py and
 tests/test_hip_gemm_routes.py, the descriptors it must decline, the ops.gemm route with its tunable and counter, the
 cached weight image following its weight, and one period of the MPD against the CPU oracle.
 
@@ -12,15 +12,14 @@ Tolerance, per element, as tests/test_hip_gemm_f16_tap.py: 1.8e-6 * (|A| |B|^T +
 2^-28 amax_seq(row) sum_k |w[n,k]| carried through the epilogue like a product's scale; a segment's maximum is at most
 its sequence's, so the per-sequence floor bounds the per-segment one (tests/fp16x3_seg1_emul.py has the exact bound)."""
 import ctypes as C
-import math
-import types
 
 import pytest
 import torch
 
 import fp16x3_seq_emul as emul
-from test_hip_gemm_f16_tap import EINVAL, TOL, case, f16_ok, mode_name, seq_image
-from test_hip_gemm_routes import DEV, NAN, SENT, Out, Vec, check, expect, last_kernel, make_desc, products, rnd
+from fp16x3_gpu import (EINVAL, TOL, any_grid, assert_declined, case, f16_ok, fp16x3_mode, image_follows_weight, ops,
+                        ran, same_bits, seq_image, subdisc_against_oracle, watching_gemm_calls)
+from test_hip_gemm_routes import DEV, NAN, Out, Vec, check, expect, last_kernel, make_desc, products, rnd
 
 pytestmark = pytest.mark.gpu
 
@@ -37,37 +36,18 @@ def name_of(taps):
     return f"h3pn<taps={taps}>"
 
 
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from flow2gan_amd import ops as o
-    return o
-
-
-@pytest.fixture
-def any_grid(lib_option):
-    """library option x6p = 2: the tap-walking kernels take grids that do not fill the chip"""
-    lib_option("x6p", 2)
-
-
 @pytest.fixture
 def tapn_route(ops, any_grid):
     """the fp16x3 mode as shipped, with FP16X3_TAPN_MIN_ROWS = 1, the library option x6p = 2, and the bf16x6 rule for
     tall 32-column GEMMs (gemm_x6n_kernel) lowered to the test's row counts"""
-    was, was_rows, was_tall = mode_name(ops), ops.FP16X3_TAPN_MIN_ROWS, ops.X6F_TALL_ROWS
-    ops.set_gemm_precision("fp16x3")
-    ops.FP16X3_TAPN_MIN_ROWS = 1
-    ops.X6F_TALL_ROWS = 1024
-    try:
+    with fp16x3_mode(ops, "FP16X3_TAPN_MIN_ROWS", "X6F_TALL_ROWS"):
+        ops.FP16X3_TAPN_MIN_ROWS = 1
+        ops.X6F_TALL_ROWS = 1024
         yield ops
-    finally:
-        ops.FP16X3_TAPN_MIN_ROWS, ops.X6F_TALL_ROWS = was_rows, was_tall
-        ops.set_gemm_precision(was)
 
 
 def seg_case(ops, S, P0, N, taps, seed=0, extra=0, front=0, Cc=CC, step=1):
-    """case() of tests/test_hip_gemm_f16_tap.py with A left the fp32 map and marked split = 8, the windows `front`
+    """case() of tests/fp16x3_gpu.py with A left the fp32 map and marked split = 8, the windows `front`
     positions into their sequences (pad0 = -front), the positions no window reads poisoned, and B replaced by its
     f2g_split_f16x2_seq image"""
     c = case(ops, S, P0, Cc, N, taps, seed=seed, step=step, extra=extra + front, images=False)
@@ -116,7 +96,7 @@ def test_bias_and_leaky_relu_through_a_stride_3_row_map(ops, any_grid, i, taps):
     assert f16_ok(ops, d) == 1
     ops.call("f2g_gemm", C.byref(d))
     torch.cuda.synchronize()
-    assert last_kernel(ops) == name_of(taps) and ops.L.lib.f2g_gemm_last_path() == 6
+    assert ran(ops, name_of(taps))
     out.guards_ok()
     want, m, _, _ = expect(c.acc, c.mag, bias=bias, lrelu=0.1)
     check(out.got(), want, m, TOL, "forward")
@@ -144,7 +124,7 @@ def test_mask_feature_matching_and_column_sums_against_float64(ops, any_grid, i,
     assert ops.L.lib.f2g_gemm_colsum_part_rows(C.byref(d)) == 0
     ops.call("f2g_gemm", C.byref(d))
     torch.cuda.synchronize()
-    assert last_kernel(ops) == name_of(taps) and ops.L.lib.f2g_gemm_last_path() == 6
+    assert ran(ops, name_of(taps))
     out.guards_ok()
     yy, rr = y_full[out.offs].double(), ref_full[out.offs].double()
     v = c.acc + fmw * 0.5 * torch.sign(yy - rr)
@@ -165,15 +145,16 @@ def test_mask_feature_matching_and_column_sums_against_float64(ops, any_grid, i,
 @pytest.mark.parametrize("i", [1, 2])
 def test_three_launches_give_the_same_bits(ops, any_grid, i, taps):
     c = shared_case(ops, i, taps)
-    bits = []
-    for _ in range(3):
+
+    def go():
         out = Out(c.M, c.N)
         d = make_desc(ops, c.A, c.B, out, precision=4)
         ops.call("f2g_gemm", C.byref(d))
         torch.cuda.synchronize()
         assert last_kernel(ops) == name_of(taps)
-        bits.append(out.flat.view(torch.int32).clone())
-    assert torch.equal(bits[0], bits[1]) and torch.equal(bits[0], bits[2])
+        return out.flat.view(torch.int32).clone()
+
+    same_bits(go)
 
 
 @pytest.mark.parametrize("taps", [2, 1])
@@ -218,11 +199,7 @@ def test_descriptors_the_kernel_declines(ops, lib_option, what):
     if what == "unmarked":
         # A.split == 0 beside B's image: the stride-1 image kernel's candidate, which asks for images of both
         d.A.split = 0
-    assert f16_ok(ops, d) == 0
-    assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
-    torch.cuda.synchronize()
-    assert last_kernel(ops) == ""
-    assert bool((out.flat[~torch.isnan(out.flat)] == SENT).all())
+    assert_declined(ops, d, out)
 
 
 # ------------------------------------------------------------------ ops.gemm
@@ -256,28 +233,13 @@ def test_ops_gemm_takes_the_route_and_counts_it(tapn_route, monkeypatch, taps):
     w = torch.nn.Parameter(rnd(N, taps * CC, seed=7, scale=0.1))
     gx, rm, rows = halo_out(S, P0, N)
     ops._f16_seq_operand(ops.mat(w))        # (the weight's cached image: built before the launches are watched)
-    seen, images = [], []
-    real_call, real_image = ops.call, ops.split_f16_seq
-
-    def watch_call(name, *args):
-        if name == "f2g_gemm":
-            d = args[0]._obj                # (C.byref's object: the descriptor as it is launched)
-            seen.append((d.A.base, d.A.split, bool(d.A.rscale), d.B.split, bool(d.B.rscale)))
-        return real_call(name, *args)
-
-    def watch_image(*args, **kw):
-        images.append(args)
-        return real_image(*args, **kw)
-
     def go():
         gx.zero_()
         ops.gemm(ops.win1d(flat, S, Hp, CC, P0, 1, -front, taps), ops.mat(w), gx, rowmap=rm)
         torch.cuda.synchronize()
 
     n0, t0, t3 = ops.FP16X3_TAPN_LAUNCHES, ops.FP16X3_TAP_LAUNCHES, ops.FP16X3_TAP3N_LAUNCHES
-    with monkeypatch.context() as mp:
-        mp.setattr(ops, "call", watch_call)
-        mp.setattr(ops, "split_f16_seq", watch_image)
+    with watching_gemm_calls(ops, monkeypatch, "split_f16_seq") as (seen, images):
         go()
     assert ops.FP16X3_TAPN_LAUNCHES == n0 + 1 and last_kernel(ops) == name_of(taps)
     # no per-call image of A: the launch reads the caller's map itself, and nothing built an image meanwhile
@@ -328,20 +290,7 @@ def test_weight_images_follow_their_weights(tapn_route):
         assert torch.equal(img, want_img) and torch.equal(rs, want_rs), f"{what}: the cached image is stale"
         return gx[rows].clone()
 
-    first = launch_and_check("first launch")
-    factors = torch.logspace(-3, 3, N, device=DEV)
-    version = w._version
-    w.data.copy_(w.detach() * factors[:, None])
-    assert w._version == version            # (invisible to autograd: only the epoch tells the cache)
-    ops.bump_weight_epoch([w])
-    replayed = ops.rebuild_derived([w])
-    assert replayed >= 1 or not ops.EAGER_REBUILD
-    second = launch_and_check("after the raw-pointer update")
-    assert not torch.equal(first, second)
-    with torch.no_grad():
-        w.mul_(-0.37)
-    third = launch_and_check("after the in-place update")
-    assert not torch.equal(second, third)
+    image_follows_weight(ops, w, launch_and_check)
 
 
 # ------------------------------------------------------------------ one period of the MPD against the CPU oracle
@@ -351,42 +300,9 @@ def test_mpd_period_against_oracle(tapn_route):
     on the route (the stride residues of the 32 -> 128 layer's data gradient), a forward none, and nothing when it is
     off"""
     ops = tapn_route
-    import test_hip_disc_autograd as T
-    do, dh = T._models("mpd")
-    sub_o, sub_h = do.discriminators[0], dh.discriminators[0]
-    _, y_hat = T._inputs()
-
-    def loss_of(score, fmap):
-        gen = torch.Generator().manual_seed(77)
-        loss = torch.relu(1 + score).mean()
-        for m in fmap:
-            loss = loss + (m * torch.randn(m.shape, generator=gen).to(m.device)).sum() / math.sqrt(m.numel())
-        return loss
-
-    def hip_run():
-        for p in sub_h.parameters():
-            p.grad = None
-        yh = y_hat.to(DEV).requires_grad_(True)
-        n0 = ops.FP16X3_TAPN_LAUNCHES
-        score, fmap = sub_h(yh)
-        n1 = ops.FP16X3_TAPN_LAUNCHES
-        loss_of(score, fmap).backward()
-        torch.cuda.synchronize()
-        return score, fmap, yh.grad, n1 - n0, ops.FP16X3_TAPN_LAUNCHES - n1
-
-    score, fmap, gx, fwd, bwd = hip_run()
-    print(f"[h3pn] period {sub_h.period}: {fwd} forward and {bwd} backward launches on the route")
-    assert fwd == 0 and bwd == 3, "the three residue data gradients of the 32 -> 128 layer"
-    sides = T._hip_sides(types.SimpleNamespace(discriminators=[sub_h]), "mpd", y_hat.to(DEV))[0]
-    yo = y_hat.clone().requires_grad_(True)
-    do.zero_grad(set_to_none=True)
-    so, fo = T._with_sides(sides, lambda: sub_o(yo))
-    loss_of(so, fo).backward()
-    pairs = [("score", score, so.detach())] + [(f"fmap.{i}", m, fo[i].detach()) for i, m in enumerate(fmap)]
-    pairs += [("y_hat", gx, yo.grad)]
-    pairs += [(k, p.grad, dict(sub_o.named_parameters())[k].grad) for k, p in sub_h.named_parameters()]
-    do.zero_grad(set_to_none=True)
-    T._compare(pairs, "mpd period 2, fp16x3 in-kernel-scaled residue data gradients")
+    r = subdisc_against_oracle(ops, "mpd", ("FP16X3_TAPN_LAUNCHES",),
+                               "mpd period 2, fp16x3 in-kernel-scaled residue data gradients")
+    print(f"[h3pn] period {r.sub.period}: {r.fwd[0]} forward and {r.bwd[0]} backward launches on the route")
+    assert r.fwd[0] == 0 and r.bwd[0] == 3, "the three residue data gradients of the 32 -> 128 layer"
     ops.FP16X3_TAPN_MIN_ROWS = ops.FP16X3_TAP_OFF
-    _, _, _, fwd, bwd = hip_run()
-    assert fwd == 0 and bwd == 0
+    assert r.rerun() == ((0,), (0,))

@@ -1,6 +1,6 @@
 """The one-launch fp16x3 data gradient over the three stride residues of the MPD's 32 -> 128 layer (csrc/gemm_f16pn3.hip,
 gemm_h3pn3_kernel; f2g_epilogue.col_fold / seq_live): against float64 per element over poisoned operands and guarded
-outputs with the helpers of tests/test_hip_gemm_routes.py, tests/test_hip_gemm_f16_tap.py and
+outputs with the helpers of tests/test_hip_gemm_routes.py, tests/fp16x3_gpu.py and
 tests/test_hip_gemm_f16_tapn.py, the descriptors it must decline, the route of fused_disc._conv1d_dgrad with its
 tunable and counter -- off by default, where the data gradient stays the three launches bit for bit --, the cached
 image of the combined weight following its weight, and one period of the MPD against the CPU oracle.
@@ -12,7 +12,6 @@ computes when Hin % 3 != 0 -- must keep their sentinel.
 Tolerance, per element, as tests/test_hip_gemm_f16_tapn.py: 1.8e-6 * (|A| |B|^T + |epilogue terms|) plus the floor
 term 2^-28 amax_seq(row) sum_k |w[n,k]| (tests/fp16x3_res3_emul.py has the bound; nothing new)."""
 import ctypes as C
-import math
 import types
 
 import pytest
@@ -20,25 +19,12 @@ import torch
 
 import fp16x3_res3_emul as res3
 import fp16x3_seq_emul as emul
-from test_fp16x3_tapn3_host import REFUSALS
-from test_hip_gemm_f16_tap import EINVAL, TOL, f16_ok, halo_windows, mode_name, seq_image
+from fp16x3_gpu import (EINVAL, TOL, any_grid, f16_ok, fp16x3_mode, halo_windows, image_follows_weight, mode_name, ops,
+                        ran, seq_image, subdisc_against_oracle)
+from fp16x3_res3_emul import REFUSALS
 from test_hip_gemm_routes import DEV, NAN, SENT, Out, Vec, check, last_kernel, make_desc, plain, products, rnd
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from flow2gan_amd import ops as o
-    return o
-
-
-@pytest.fixture
-def any_grid(lib_option):
-    """library option x6p = 2: the tap-walking kernels take grids that do not fill the chip"""
-    lib_option("x6p", 2)
 
 
 CC, CIN, N3 = 128, 32, 96
@@ -120,7 +106,7 @@ def test_three_residues_in_one_launch_against_float64(ops, any_grid, i):
     assert f16_ok(ops, d) == 1
     ops.call("f2g_gemm", C.byref(d))
     torch.cuda.synchronize()
-    assert last_kernel(ops) == NAME and ops.L.lib.f2g_gemm_last_path() == 6
+    assert ran(ops, NAME)
     check_live(c, out, c.acc, c.mag, "data gradient")
     if i == 0:
         d.B.base, d.B.split, d.B.rscale = c.B.flat.data_ptr() + 4 * c.B.off, 0, None
@@ -236,14 +222,9 @@ def test_the_fields_are_refused_at_every_other_precision(ops):
 @pytest.fixture
 def tapn3_route(ops, any_grid):
     """the fp16x3 mode as shipped, with FP16X3_TAPN3_MIN_ROWS = 1 and the library option x6p = 2"""
-    was, was_rows = mode_name(ops), ops.FP16X3_TAPN3_MIN_ROWS
-    ops.set_gemm_precision("fp16x3")
-    ops.FP16X3_TAPN3_MIN_ROWS = 1
-    try:
+    with fp16x3_mode(ops, "FP16X3_TAPN3_MIN_ROWS"):
+        ops.FP16X3_TAPN3_MIN_ROWS = 1
         yield ops
-    finally:
-        ops.FP16X3_TAPN3_MIN_ROWS = was_rows
-        ops.set_gemm_precision(was)
 
 
 def layer_case(S, Hin, seed):
@@ -372,20 +353,7 @@ def test_the_combined_weights_image_follows_its_weight(tapn3_route):
         assert torch.equal(img, want_img) and torch.equal(rs, want_rs), f"{what}: the cached image is stale"
         return got
 
-    first = launch_and_check("first launch")
-    factors = torch.logspace(-3, 3, CC, device=DEV)
-    version = w._version
-    w.data.copy_(w.detach() * factors[:, None, None, None])
-    assert w._version == version            # (invisible to autograd: only the epoch tells the cache)
-    ops.bump_weight_epoch([w])
-    replayed = ops.rebuild_derived([w])
-    assert replayed >= 1 or not ops.EAGER_REBUILD
-    second = launch_and_check("after the raw-pointer update")
-    assert not torch.equal(first, second)
-    with torch.no_grad():
-        w.mul_(-0.37)
-    third = launch_and_check("after the in-place update")
-    assert not torch.equal(second, third)
+    image_follows_weight(ops, w, launch_and_check)
 
 
 # ------------------------------------------------------------------ one period of the MPD against the CPU oracle
@@ -394,42 +362,9 @@ def test_mpd_period_against_oracle(tapn3_route):
     gradient and every parameter gradient against the oracle at that file's tolerance; a backward counts ONE launch
     on the route (the data gradient of the 32 -> 128 layer), a forward none, and nothing when it is off"""
     ops = tapn3_route
-    import test_hip_disc_autograd as T
-    do, dh = T._models("mpd")
-    sub_o, sub_h = do.discriminators[0], dh.discriminators[0]
-    _, y_hat = T._inputs()
-
-    def loss_of(score, fmap):
-        gen = torch.Generator().manual_seed(77)
-        loss = torch.relu(1 + score).mean()
-        for m in fmap:
-            loss = loss + (m * torch.randn(m.shape, generator=gen).to(m.device)).sum() / math.sqrt(m.numel())
-        return loss
-
-    def hip_run():
-        for p in sub_h.parameters():
-            p.grad = None
-        yh = y_hat.to(DEV).requires_grad_(True)
-        n0 = ops.FP16X3_TAPN3_LAUNCHES
-        score, fmap = sub_h(yh)
-        n1 = ops.FP16X3_TAPN3_LAUNCHES
-        loss_of(score, fmap).backward()
-        torch.cuda.synchronize()
-        return score, fmap, yh.grad, n1 - n0, ops.FP16X3_TAPN3_LAUNCHES - n1
-
-    score, fmap, gx, fwd, bwd = hip_run()
-    print(f"[h3pn3] period {sub_h.period}: {fwd} forward and {bwd} backward launches on the route")
-    assert fwd == 0 and bwd == 1, "one launch for the data gradient of the 32 -> 128 layer"
-    sides = T._hip_sides(types.SimpleNamespace(discriminators=[sub_h]), "mpd", y_hat.to(DEV))[0]
-    yo = y_hat.clone().requires_grad_(True)
-    do.zero_grad(set_to_none=True)
-    so, fo = T._with_sides(sides, lambda: sub_o(yo))
-    loss_of(so, fo).backward()
-    pairs = [("score", score, so.detach())] + [(f"fmap.{i}", m, fo[i].detach()) for i, m in enumerate(fmap)]
-    pairs += [("y_hat", gx, yo.grad)]
-    pairs += [(k, p.grad, dict(sub_o.named_parameters())[k].grad) for k, p in sub_h.named_parameters()]
-    do.zero_grad(set_to_none=True)
-    T._compare(pairs, "mpd period 2, fp16x3 one-launch data gradient of the 32 -> 128 layer")
+    r = subdisc_against_oracle(ops, "mpd", ("FP16X3_TAPN3_LAUNCHES",),
+                               "mpd period 2, fp16x3 one-launch data gradient of the 32 -> 128 layer")
+    print(f"[h3pn3] period {r.sub.period}: {r.fwd[0]} forward and {r.bwd[0]} backward launches on the route")
+    assert r.fwd[0] == 0 and r.bwd[0] == 1, "one launch for the data gradient of the 32 -> 128 layer"
     ops.FP16X3_TAPN3_MIN_ROWS = ops.FP16X3_TAP_OFF
-    _, _, _, fwd, bwd = hip_run()
-    assert fwd == 0 and bwd == 0
+    assert r.rerun() == ((0,), (0,))

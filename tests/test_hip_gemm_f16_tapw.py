@@ -7,23 +7,18 @@ Tolerance of the GEMM cases: tests/test_hip_gemm_f16.py's, |got - want| <= 1.8e-
 held|) per element: the taps shift rows of the map, so a power-of-two scale per column of the whole map leaves every
 tap's sum over rows exactly (tests/fp16x3_colswin_emul.py) and the per-product bound is 3 * 2^-22, beside the suite's
 1e-6 for exact-class fp32 accumulation."""
-import ctypes as C
-import math
-import types
-
 import pytest
 import torch
 
 import fp16x3_colswin_emul as win_emul
-from test_hip_gemm_f16 import TOL, mode_name
-from test_hip_gemm_f16_wgrad import as_cols_image
-from test_hip_gemm_routes import DEV, NAN, SENT, Op, Out, _halo_x, check, last_kernel, launch, make_desc, plain, products, rnd, run
+from fp16x3_gpu import HALO, TOL, assert_declined, f16_ok, fp16x3_mode, ops, ran, same_bits, subdisc_against_oracle
+from fp16x3_gpu import maps_s1 as maps
+from fp16x3_gpu import operands_s1 as operands
+from test_hip_gemm_routes import DEV, Out, _halo_x, check, last_kernel, launch, make_desc, products, rnd, run
 
 pytestmark = pytest.mark.gpu
 
 NAME = "h3wt<taps=5>"
-EINVAL = -1
-HALO = 2
 SHAPES = [(128, 128, 1, 3),        # K = 7: one partial slab, windows overhang both buffer ends
           (128, 128, 1, 28),       # K = 32: exactly one slab
           (128, 128, 3, 7),        # K = 33
@@ -32,71 +27,16 @@ SHAPES = [(128, 128, 1, 3),        # K = 7: one partial slab, windows overhang b
           (128, 256, 40, 300)]     # K = 12160: the launcher's several K chunks, rescale before the atomic add
 
 
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from flow2gan_amd import ops as o
-    return o
-
-
 @pytest.fixture
 def fp16x3(ops):
     """the fp16x3 mode; thresholds and the mode are restored afterwards (the tests assign the thresholds themselves)"""
     names = ("FP16X3_TAPW_MIN_ROWS", "FP16X3_TAP_MIN_ROWS", "FP16X3_WGRAD_MIN_ROWS", "X6_MIN_K")
-    was, vals = mode_name(ops), [getattr(ops, n) for n in names]
-    ops.set_gemm_precision("fp16x3")
-    try:
+    with fp16x3_mode(ops, *names):
         yield ops
-    finally:
-        for n, v in zip(names, vals):
-            setattr(ops, n, v)
-        ops.set_gemm_precision(was)
-
-
-def f16_ok(ops, d):
-    return ops.L.lib.f2g_gemm_f16_ok(C.byref(d))
 
 
 def is_h3wt(ops):
-    return last_kernel(ops) == NAME and ops.L.lib.f2g_gemm_last_path() == 6
-
-
-# ------------------------------------------------------------------ operands
-def as_cols_window_image(ops, op):
-    """replace the fp32 window operand `op` by the f2g_split_f16x2_cols image of its WHOLE map (xrows x unit floats,
-    halo rows included); the window fields stay as they are"""
-    o = op.o
-    xrows = (o.rows // o.P0) * (o.seq_stride // o.unit)
-    op.img = op.flat.clone()
-    op.rs = torch.full((o.unit + 8,), NAN, device=DEV)
-    op.work = torch.empty(o.unit, device=DEV, dtype=torch.int32)
-    ops.call("f2g_split_f16x2_cols", op.img.data_ptr() + 4 * op.off, op.rs.data_ptr() + 16, op.work.data_ptr(),
-             op.flat.data_ptr() + 4 * op.off, o.unit, xrows, o.unit)
-    o.base, o.split, o.rscale = op.img.data_ptr() + 4 * op.off, 6, op.rs.data_ptr() + 16
-    return op
-
-
-def maps(Cin, Cout, S, Hin, seed):
-    """the halo map x (S, Hp, Cin) and the gradient map (S, Hp, Cout), both with zero halo rows"""
-    Hp = Hin + 2 * HALO
-    x = _halo_x(S, Hin, Cin, HALO, seed)
-    gy = torch.zeros(S, Hp, Cout, device=DEV)
-    gy[:, HALO:HALO + Hin] = rnd(S, Hin, Cout, seed=seed + 1)
-    return x, gy
-
-
-def operands(ops, x, gy, images=True, step=1, taps=5):
-    """A: the gradient as a plain matrix inside a NaN buffer; B: unbounded windows of `taps` positions over the map"""
-    S, Hp, Cin = x.shape
-    Cout = gy.shape[2]
-    A = plain(ops, gy.reshape(S * Hp, Cout))
-    B = Op(ops, x.reshape(-1).contiguous(), 0, 0, rows=S * Hp, cols=taps * Cin, P0=Hp, step0=step, pad0=HALO * step,
-           unit=Cin, L0u=Hp * Cin, seq_stride=Hp * Cin, unbounded=1)
-    if images:
-        as_cols_image(ops, A)
-        as_cols_window_image(ops, B)
-    return A, B
+    return ran(ops, NAME)
 
 
 # ------------------------------------------------------------------ kernel against float64
@@ -129,13 +69,14 @@ def test_three_launches_give_the_same_bits(ops):
     x, gy = maps(Cin, Cout, S, Hin, seed=41)
     A, B = operands(ops, x, gy)
     c0 = rnd(Cout, 5 * Cin, seed=42)
-    bits = []
-    for _ in range(3):
+
+    def go():
         out = Out(Cout, 5 * Cin, c0)
         launch(ops, A, B, out, form=2, precision=4, atomic=True)
         assert is_h3wt(ops)
-        bits.append(out.flat.view(torch.int32).clone())
-    assert torch.equal(bits[0], bits[1]) and torch.equal(bits[0], bits[2])
+        return out.flat.view(torch.int32).clone()
+
+    same_bits(go)
 
 
 def test_inf_in_one_channel_stays_in_its_output_columns(ops):
@@ -190,11 +131,7 @@ def test_descriptors_the_kernel_declines(ops, what):
     precisions = (0, 1, 2, 3) if what == "other_precisions" else (4,)
     for prec in precisions:
         d.precision = prec
-        assert f16_ok(ops, d) == 0
-        assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
-        torch.cuda.synchronize()
-        assert last_kernel(ops) == ""
-    assert bool((out.flat[~torch.isnan(out.flat)] == SENT).all())
+        assert_declined(ops, d, out)
     if what == "other_precisions":      # (the descriptor itself is one the kernel runs)
         d.precision = 4
         assert f16_ok(ops, d) == 1
@@ -205,11 +142,7 @@ def test_fp32_operands_would_qualify_but_are_not_launched(ops):
     A, B = operands(ops, x, gy, images=False)
     out = Out(128, 5 * 128)
     d = make_desc(ops, A, B, out, form=2, precision=4, atomic=True)
-    assert f16_ok(ops, d) == 2
-    assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
-    torch.cuda.synchronize()
-    assert last_kernel(ops) == ""
-    assert bool((out.flat[~torch.isnan(out.flat)] == SENT).all())
+    assert_declined(ops, d, out, ok=2)
 
 
 # ------------------------------------------------------------------ ops.wgrad
@@ -270,42 +203,12 @@ def test_mpd_period_against_oracle(fp16x3, lib_option):
     ops = fp16x3
     lib_option("x6p", 2)
     ops.FP16X3_TAP_MIN_ROWS = ops.FP16X3_TAPW_MIN_ROWS = 1
-    import test_hip_disc_autograd as T
-    do, dh = T._models("mpd")
-    sub_o, sub_h = do.discriminators[0], dh.discriminators[0]
-    _, y_hat = T._inputs()
-
-    def loss_of(score, fmap):
-        gen = torch.Generator().manual_seed(77)
-        loss = torch.relu(1 + score).mean()
-        for m in fmap:
-            loss = loss + (m * torch.randn(m.shape, generator=gen).to(m.device)).sum() / math.sqrt(m.numel())
-        return loss
-
-    def hip_run():
-        for p in sub_h.parameters():
-            p.grad = None
-        yh = y_hat.to(DEV).requires_grad_(True)
-        t0, w0 = ops.FP16X3_TAP_LAUNCHES, ops.FP16X3_TAPW_LAUNCHES
-        score, fmap = sub_h(yh)
-        loss_of(score, fmap).backward()
-        torch.cuda.synchronize()
-        return score, fmap, yh.grad, ops.FP16X3_TAP_LAUNCHES - t0, ops.FP16X3_TAPW_LAUNCHES - w0
-
-    score, fmap, gx, tap, tapw = hip_run()
-    print(f"[h3wt] period {sub_h.period}: {tap} launches on the tap route, {tapw} on the tap-walking weight gradient")
+    r = subdisc_against_oracle(ops, "mpd", ("FP16X3_TAP_LAUNCHES", "FP16X3_TAPW_LAUNCHES"),
+                               "mpd period 2, fp16x3 tap route and tap-walking weight gradient")
+    tap, tapw = (f + b for f, b in zip(r.fwd, r.bwd))
+    print(f"[h3wt] period {r.sub.period}: {tap} launches on the tap route, {tapw} on the tap-walking weight gradient")
     assert tap >= 2, "the fifth layer's forward and data gradient never reached the tap route"
     assert tapw >= 1, "the fifth layer's weight gradient never reached the kernel"
-    sides = T._hip_sides(types.SimpleNamespace(discriminators=[sub_h]), "mpd", y_hat.to(DEV))[0]
-    yo = y_hat.clone().requires_grad_(True)
-    do.zero_grad(set_to_none=True)
-    so, fo = T._with_sides(sides, lambda: sub_o(yo))
-    loss_of(so, fo).backward()
-    pairs = [("score", score, so.detach())] + [(f"fmap.{i}", m, fo[i].detach()) for i, m in enumerate(fmap)]
-    pairs += [("y_hat", gx, yo.grad)]
-    pairs += [(k, p.grad, dict(sub_o.named_parameters())[k].grad) for k, p in sub_h.named_parameters()]
-    do.zero_grad(set_to_none=True)
-    T._compare(pairs, "mpd period 2, fp16x3 tap route and tap-walking weight gradient")
     ops.FP16X3_TAPW_MIN_ROWS = ops.FP16X3_TAP_OFF
-    _, _, _, tap, tapw = hip_run()
+    tap, tapw = (f + b for f, b in zip(*r.rerun()))
     assert tap >= 2 and tapw == 0

@@ -11,25 +11,18 @@ held|) per element: tap and stride only select rows of the map, so a power-of-tw
 leaves the sum over rows exactly (tests/fp16x3_colswin3_emul.py) and the per-product bound is 3 * 2^-22, beside the
 suite's 1e-6 for exact-class fp32 accumulation.  The kernel's slab is 16 gradient rows: the slab-edge shapes are Hp =
 7, 16, 17, 32."""
-import ctypes as C
-import math
-import types
-
 import pytest
 import torch
 
 import fp16x3_colswin3_emul as win3_emul
-import test_hip_gemm_f16_tapw as tapw
-from test_hip_gemm_f16 import TOL, mode_name
-from test_hip_gemm_f16_tapw import as_cols_window_image, f16_ok
-from test_hip_gemm_f16_wgrad import as_cols_image
-from test_hip_gemm_routes import DEV, SENT, Op, Out, check, last_kernel, launch, make_desc, plain, products, rnd, run
+from fp16x3_gpu import (HALO, TOL, assert_declined, f16_ok, fp16x3_mode, hout_of, maps, maps_s1, operands, operands_s1,
+                        ops, ran, same_bits, subdisc_against_oracle)
+from test_hip_gemm_routes import DEV, Out, check, last_kernel, launch, make_desc, products, rnd, run
 
 pytestmark = pytest.mark.gpu
 
 NAME = "h3ws<taps=5,step=3>"
-EINVAL = -1
-HALO, STEP = 2, 3
+STEP = 3
 SHAPES = [(128, 128, 1, 7, 0),        # Hp = 7: one partial slab, windows overhanging both buffer ends
           (128, 128, 1, 34, 0),       # Hp = 16: exactly one slab, the tightest fit 3 Hout = Hin + 2
           (128, 128, 3, 37, 0),       # Hp = 17
@@ -42,60 +35,17 @@ SHAPES = [(128, 128, 1, 7, 0),        # Hp = 7: one partial slab, windows overha
                                       # s * HpIn, not 3 * Hp
 
 
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from flow2gan_amd import ops as o
-    return o
-
-
 @pytest.fixture
 def fp16x3(ops):
     """the fp16x3 mode; thresholds and the mode are restored afterwards (the tests assign the thresholds themselves)"""
     names = ("FP16X3_TAPW3_MIN_ROWS", "FP16X3_TAPW_MIN_ROWS", "FP16X3_TAP_MIN_ROWS", "FP16X3_TAP3_MIN_ROWS",
              "FP16X3_WGRAD_MIN_ROWS", "X6_MIN_K")
-    was, vals = mode_name(ops), [getattr(ops, n) for n in names]
-    ops.set_gemm_precision("fp16x3")
-    try:
+    with fp16x3_mode(ops, *names):
         yield ops
-    finally:
-        for n, v in zip(names, vals):
-            setattr(ops, n, v)
-        ops.set_gemm_precision(was)
 
 
 def is_h3ws(ops):
-    return last_kernel(ops) == NAME and ops.L.lib.f2g_gemm_last_path() == 6
-
-
-# ------------------------------------------------------------------ operands
-def hout_of(Hin):
-    return (Hin - 1) // STEP + 1
-
-
-def maps(Cin, Cout, S, Hin, seed, extra=0):
-    """the input halo map x (S, Hin + 4 + extra, Cin) and the gradient map (S, Hout + 4, Cout), zero halo rows"""
-    Hout = hout_of(Hin)
-    x = torch.zeros(S, Hin + 2 * HALO + extra, Cin, device=DEV)
-    x[:, HALO:HALO + Hin] = rnd(S, Hin, Cin, seed=seed)
-    gy = torch.zeros(S, Hout + 2 * HALO, Cout, device=DEV)
-    gy[:, HALO:HALO + Hout] = rnd(S, Hout, Cout, seed=seed + 1)
-    return x, gy
-
-
-def operands(ops, x, gy, images=True, step=STEP, taps=5):
-    """A: the gradient as a plain matrix inside a NaN buffer; B: unbounded windows of `taps` positions, `step` apart,
-    over the map"""
-    S, HpIn, Cin = x.shape
-    Hp, Cout = gy.shape[1], gy.shape[2]
-    A = plain(ops, gy.reshape(S * Hp, Cout))
-    B = Op(ops, x.reshape(-1).contiguous(), 0, 0, rows=S * Hp, cols=taps * Cin, P0=Hp, step0=step, pad0=HALO * STEP,
-           unit=Cin, L0u=HpIn * Cin, seq_stride=HpIn * Cin, unbounded=1)
-    if images:
-        as_cols_image(ops, A)
-        as_cols_window_image(ops, B)
-    return A, B
+    return ran(ops, NAME)
 
 
 # ------------------------------------------------------------------ kernel against float64
@@ -131,13 +81,14 @@ def test_three_launches_give_the_same_bits(ops):
     x, gy = maps(Cin, Cout, S, Hin, seed=41)
     A, B = operands(ops, x, gy)
     c0 = rnd(Cout, 5 * Cin, seed=42)
-    bits = []
-    for _ in range(3):
+
+    def go():
         out = Out(Cout, 5 * Cin, c0)
         launch(ops, A, B, out, form=2, precision=4, atomic=True)
         assert is_h3ws(ops)
-        bits.append(out.flat.view(torch.int32).clone())
-    assert torch.equal(bits[0], bits[1]) and torch.equal(bits[0], bits[2])
+        return out.flat.view(torch.int32).clone()
+
+    same_bits(go)
 
 
 def test_inf_in_one_channel_stays_in_its_output_columns(ops):
@@ -176,7 +127,7 @@ def test_descriptors_the_kernel_declines(ops, what):
     Cin, Cout, S, Hin = (32 if what == "unit32" else 128), 128, 2, 82
     taps = 3 if what == "taps3" else 5
     if what == "overhang":      # a stride-1 geometry (P0 = HpIn = 32, pad0 = 2) with step0 flipped to 3 below
-        A, B = tapw.operands(ops, *tapw.maps(Cin, Cout, S, 28, seed=61))
+        A, B = operands_s1(ops, *maps_s1(Cin, Cout, S, 28, seed=61))
     else:
         A, B = operands(ops, *maps(Cin, Cout, S, Hin, seed=61), taps=taps)
     out = Out(Cout, taps * Cin)
@@ -199,11 +150,7 @@ def test_descriptors_the_kernel_declines(ops, what):
     precisions = (0, 1, 2, 3) if what == "other_precisions" else (4,)
     for prec in precisions:
         d.precision = prec
-        assert f16_ok(ops, d) == 0
-        assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
-        torch.cuda.synchronize()
-        assert last_kernel(ops) == ""
-    assert bool((out.flat[~torch.isnan(out.flat)] == SENT).all())
+        assert_declined(ops, d, out)
     if what == "other_precisions":      # (the descriptor itself is one the kernel runs)
         d.precision = 4
         assert f16_ok(ops, d) == 1
@@ -213,11 +160,7 @@ def test_fp32_operands_would_qualify_but_are_not_launched(ops):
     A, B = operands(ops, *maps(128, 128, 2, 82, seed=71), images=False)
     out = Out(128, 5 * 128)
     d = make_desc(ops, A, B, out, form=2, precision=4, atomic=True)
-    assert f16_ok(ops, d) == 2
-    assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
-    torch.cuda.synchronize()
-    assert last_kernel(ops) == ""
-    assert bool((out.flat[~torch.isnan(out.flat)] == SENT).all())
+    assert_declined(ops, d, out, ok=2)
 
 
 # ------------------------------------------------------------------ ops.wgrad
@@ -284,41 +227,10 @@ def test_mpd_period_against_oracle(fp16x3, lib_option):
     ops = fp16x3
     lib_option("x6p", 2)
     ops.FP16X3_TAP_MIN_ROWS = ops.FP16X3_TAP3_MIN_ROWS = ops.FP16X3_TAPW_MIN_ROWS = ops.FP16X3_TAPW3_MIN_ROWS = 1
-    import test_hip_disc_autograd as T
-    do, dh = T._models("mpd")
-    sub_o, sub_h = do.discriminators[0], dh.discriminators[0]
-    _, y_hat = T._inputs()
-
-    def loss_of(score, fmap):
-        gen = torch.Generator().manual_seed(77)
-        loss = torch.relu(1 + score).mean()
-        for m in fmap:
-            loss = loss + (m * torch.randn(m.shape, generator=gen).to(m.device)).sum() / math.sqrt(m.numel())
-        return loss
-
-    def hip_run():
-        for p in sub_h.parameters():
-            p.grad = None
-        yh = y_hat.to(DEV).requires_grad_(True)
-        w0 = ops.FP16X3_TAPW3_LAUNCHES
-        score, fmap = sub_h(yh)
-        loss_of(score, fmap).backward()
-        torch.cuda.synchronize()
-        return score, fmap, yh.grad, ops.FP16X3_TAPW3_LAUNCHES - w0
-
-    score, fmap, gx, tapw3 = hip_run()
-    print(f"[h3ws] period {sub_h.period}: {tapw3} launches on the stride-3 tap-walking weight gradient")
+    r = subdisc_against_oracle(ops, "mpd", ("FP16X3_TAPW3_LAUNCHES",),
+                               "mpd period 2, fp16x3 tap routes and both tap-walking weight gradients")
+    tapw3 = r.fwd[0] + r.bwd[0]
+    print(f"[h3ws] period {r.sub.period}: {tapw3} launches on the stride-3 tap-walking weight gradient")
     assert tapw3 >= 2, "a stride-3 layer's weight gradient never reached the kernel"
-    sides = T._hip_sides(types.SimpleNamespace(discriminators=[sub_h]), "mpd", y_hat.to(DEV))[0]
-    yo = y_hat.clone().requires_grad_(True)
-    do.zero_grad(set_to_none=True)
-    so, fo = T._with_sides(sides, lambda: sub_o(yo))
-    loss_of(so, fo).backward()
-    pairs = [("score", score, so.detach())] + [(f"fmap.{i}", m, fo[i].detach()) for i, m in enumerate(fmap)]
-    pairs += [("y_hat", gx, yo.grad)]
-    pairs += [(k, p.grad, dict(sub_o.named_parameters())[k].grad) for k, p in sub_h.named_parameters()]
-    do.zero_grad(set_to_none=True)
-    T._compare(pairs, "mpd period 2, fp16x3 tap routes and both tap-walking weight gradients")
     ops.FP16X3_TAPW3_MIN_ROWS = ops.FP16X3_TAP_OFF
-    _, _, _, tapw3 = hip_run()
-    assert tapw3 == 0
+    assert r.rerun() == ((0,), (0,))

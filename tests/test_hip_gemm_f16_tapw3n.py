@@ -1,5 +1,5 @@
 """fp16x3 weight gradient of the MPD's 32 -> 128 layer, scaled inside the kernel, on the GPU: gemm_h3wsn_kernel<5, 3>
-(csrc/gemm_f16wsn.hip) against float64 over guarded outputs (the helpers of tests/test_hip_gemm_f16_tapw3.py and
+(csrc/gemm_f16wsn.hip) against float64 over guarded outputs (the helpers of tests/fp16x3_gpu.py and
 tests/test_hip_gemm_routes.py; the gradient sits in a NaN-poisoned buffer, the map is an unbounded operand: exactly its
 buffer), the scale moves of a block's walk, the descriptors it must decline, ops.wgrad's routing, and one period of the
 MPD against the CPU oracle with the layer's weight gradient on the kernel.  Cin = 32 and Cout = 128 throughout.
@@ -10,23 +10,20 @@ element 2^-28 below the running maximum in force is subnormal in hi) with the op
 running ones: a running maximum never exceeds them, so the tolerance does not depend on the grid."""
 import ctypes as C
 import math
-import types
 
 import pytest
 import torch
 
-import test_hip_gemm_f16_tapw as tapw
-from test_hip_gemm_f16 import TOL, mode_name
-from test_hip_gemm_f16_tapw import f16_ok
-from test_hip_gemm_f16_tapw3 import HALO, STEP, hout_of, maps, operands
-from test_hip_gemm_routes import DEV, SENT, Out, last_kernel, make_desc, rnd
+from fp16x3_emul import FLOOR
+from fp16x3_gpu import (HALO, TOL, assert_declined, f16_ok, fp16x3_mode, hout_of, maps, maps_s1, operands, operands_s1,
+                        ops, ran, same_bits, subdisc_against_oracle)
+from test_hip_gemm_routes import DEV, Out, last_kernel, make_desc, rnd
 
 pytestmark = pytest.mark.gpu
 
 NAME = "h3wsn<taps=5,step=3>"
-EINVAL = -1
+STEP = 3
 CIN, COUT = 32, 128
-FLOOR = 2.0 ** -28
 SHAPES = [(1, 7, 0),          # Hp = 7: one partial slab, windows overhanging both buffer ends
           (1, 34, 0),         # Hp = 16: exactly one slab, the tightest fit 3 Hout = Hin + 2
           (3, 37, 0),         # Hp = 17
@@ -39,36 +36,22 @@ SHAPES = [(1, 7, 0),          # Hp = 7: one partial slab, windows overhanging bo
                               # sequence boundaries
 
 
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from flow2gan_amd import ops as o
-    return o
-
-
 @pytest.fixture
 def fp16x3(ops):
     """the fp16x3 mode; thresholds and the mode are restored afterwards (the tests assign the thresholds themselves)"""
     names = ("FP16X3_TAPW3N_MIN_ROWS", "FP16X3_TAPW3_MIN_ROWS", "FP16X3_TAPW_MIN_ROWS", "FP16X3_TAP_MIN_ROWS",
              "FP16X3_TAP3_MIN_ROWS", "FP16X3_WGRAD_MIN_ROWS", "X6_MIN_K")
-    was, vals = mode_name(ops), [getattr(ops, n) for n in names]
-    ops.set_gemm_precision("fp16x3")
-    try:
+    with fp16x3_mode(ops, *names):
         yield ops
-    finally:
-        for n, v in zip(names, vals):
-            setattr(ops, n, v)
-        ops.set_gemm_precision(was)
 
 
 def is_h3wsn(ops):
-    return last_kernel(ops) == NAME and ops.L.lib.f2g_gemm_last_path() == 6
+    return ran(ops, NAME)
 
 
 # ------------------------------------------------------------------ operands, launch, reference
 def ops_of(ops, x, gy, **kw):
-    """the fp32 operands themselves (tests/test_hip_gemm_f16_tapw3.py: operands, without its images)"""
+    """the fp32 operands themselves (tests/fp16x3_gpu.py: operands, without its images)"""
     return operands(ops, x, gy, images=False, **kw)
 
 
@@ -177,12 +160,13 @@ def test_three_launches_give_the_same_bits(ops):
     x, gy = maps(CIN, COUT, S, Hin, seed=41)
     A, B = ops_of(ops, x, gy)
     c0 = rnd(COUT, 5 * CIN, seed=42)
-    bits = []
-    for _ in range(3):
+
+    def go():
         out = Out(COUT, 5 * CIN, c0)
         launch8(ops, A, B, out)
-        bits.append(out.flat.view(torch.int32).clone())
-    assert torch.equal(bits[0], bits[1]) and torch.equal(bits[0], bits[2])
+        return out.flat.view(torch.int32).clone()
+
+    same_bits(go)
 
 
 def test_inf_in_one_channel_stays_in_its_output_columns(ops):
@@ -218,7 +202,7 @@ def test_descriptors_the_kernel_declines(ops, what):
     Cin, Cout, S, Hin = (64 if what == "unit64" else CIN), (256 if what == "cols256" else COUT), 2, 82
     taps = 3 if what == "taps3" else 5
     if what == "overhang":      # a stride-1 geometry (P0 = HpIn = 32, pad0 = 2) with step0 flipped to 3 below
-        A, B = tapw.operands(ops, *tapw.maps(Cin, Cout, S, 28, seed=61), images=False)
+        A, B = operands_s1(ops, *maps_s1(Cin, Cout, S, 28, seed=61), images=False)
     else:
         A, B = ops_of(ops, *maps(Cin, Cout, S, Hin, seed=61), taps=taps)
     out = Out(Cout, taps * Cin)
@@ -243,11 +227,7 @@ def test_descriptors_the_kernel_declines(ops, what):
     precisions = (0, 1, 2, 3) if what == "other_precisions" else (4,)
     for prec in precisions:
         d.precision = prec
-        assert f16_ok(ops, d) == 0
-        assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
-        torch.cuda.synchronize()
-        assert last_kernel(ops) == ""
-    assert bool((out.flat[~torch.isnan(out.flat)] == SENT).all())
+        assert_declined(ops, d, out)
     if what == "other_precisions":      # (the descriptor itself is one the kernel runs)
         d.precision = 4
         assert f16_ok(ops, d) == 1
@@ -320,41 +300,10 @@ def test_mpd_period_against_oracle(fp16x3, lib_option):
     lib_option("x6p", 2)
     ops.FP16X3_TAP_MIN_ROWS = ops.FP16X3_TAP3_MIN_ROWS = ops.FP16X3_TAPW_MIN_ROWS = ops.FP16X3_TAPW3_MIN_ROWS = 1
     ops.FP16X3_TAPW3N_MIN_ROWS = 1
-    import test_hip_disc_autograd as T
-    do, dh = T._models("mpd")
-    sub_o, sub_h = do.discriminators[0], dh.discriminators[0]
-    _, y_hat = T._inputs()
-
-    def loss_of(score, fmap):
-        gen = torch.Generator().manual_seed(77)
-        loss = torch.relu(1 + score).mean()
-        for m in fmap:
-            loss = loss + (m * torch.randn(m.shape, generator=gen).to(m.device)).sum() / math.sqrt(m.numel())
-        return loss
-
-    def hip_run():
-        for p in sub_h.parameters():
-            p.grad = None
-        yh = y_hat.to(DEV).requires_grad_(True)
-        w0 = ops.FP16X3_TAPW3N_LAUNCHES
-        score, fmap = sub_h(yh)
-        loss_of(score, fmap).backward()
-        torch.cuda.synchronize()
-        return score, fmap, yh.grad, ops.FP16X3_TAPW3N_LAUNCHES - w0
-
-    score, fmap, gx, n = hip_run()
-    print(f"[h3wsn] period {sub_h.period}: {n} launches on the in-kernel-scaled stride-3 weight gradient")
+    r = subdisc_against_oracle(ops, "mpd", ("FP16X3_TAPW3N_LAUNCHES",),
+                               "mpd period 2, fp16x3 tap routes and the three tap-walking weight gradients")
+    n = r.fwd[0] + r.bwd[0]
+    print(f"[h3wsn] period {r.sub.period}: {n} launches on the in-kernel-scaled stride-3 weight gradient")
     assert n >= 1, "the 32 -> 128 layer's weight gradient never reached the kernel"
-    sides = T._hip_sides(types.SimpleNamespace(discriminators=[sub_h]), "mpd", y_hat.to(DEV))[0]
-    yo = y_hat.clone().requires_grad_(True)
-    do.zero_grad(set_to_none=True)
-    so, fo = T._with_sides(sides, lambda: sub_o(yo))
-    loss_of(so, fo).backward()
-    pairs = [("score", score, so.detach())] + [(f"fmap.{i}", m, fo[i].detach()) for i, m in enumerate(fmap)]
-    pairs += [("y_hat", gx, yo.grad)]
-    pairs += [(k, p.grad, dict(sub_o.named_parameters())[k].grad) for k, p in sub_h.named_parameters()]
-    do.zero_grad(set_to_none=True)
-    T._compare(pairs, "mpd period 2, fp16x3 tap routes and the three tap-walking weight gradients")
     ops.FP16X3_TAPW3N_MIN_ROWS = ops.FP16X3_TAP_OFF
-    _, _, _, n = hip_run()
-    assert n == 0
+    assert r.rerun() == ((0,), (0,))

@@ -6,42 +6,26 @@ step against the CPU oracle with forward, data gradient and weight gradient all 
 Tolerance of the GEMM cases: tests/test_hip_gemm_f16.py's, |got - want| <= 1.8e-6 * (|A|^T |B| + |what the output
 held|) per element: a power-of-two scale per column leaves the sum over rows exactly, so the per-product bound is the
 forward kernel's 3 * 2^-22, beside the suite's 1e-6 for exact-class fp32 accumulation."""
-import ctypes as C
-import random
-
 import pytest
 import torch
 
 import fp16x3_cols_emul as cols_emul
-from test_hip_gemm_f16 import TINY, TOL, mode_name
+from fp16x3_gpu import (EINVAL, TOL, as_cols_image, assert_declined, f16_ok, fp16x3_mode, ops, ran, same_bits,
+                        stage1_against_oracle)
 from test_hip_gemm_routes import DEV, NAN, SENT, Out, check, last_kernel, launch, make_desc, plain, products, rnd, run, win1
 
 pytestmark = pytest.mark.gpu
 
 NAME = "h3w"
-EINVAL = -1
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from flow2gan_amd import ops as o
-    return o
 
 
 @pytest.fixture
 def fp16x3(ops):
     """the mode with all three of its thresholds lowered: forward kernel from K = 32 and one output column on, the
-    weight-gradient kernel from one reduction row on; restored through set_gemm_precision"""
-    was = mode_name(ops), ops.FP16X3_MIN_K, ops.FP16X3_MIN_N, ops.FP16X3_WGRAD_MIN_ROWS
-    ops.set_gemm_precision("fp16x3")
-    ops.FP16X3_MIN_K, ops.FP16X3_MIN_N, ops.FP16X3_WGRAD_MIN_ROWS = 32, 1, 1
-    try:
+    weight-gradient kernel from one reduction row on"""
+    with fp16x3_mode(ops, "FP16X3_MIN_K", "FP16X3_MIN_N", "FP16X3_WGRAD_MIN_ROWS"):
+        ops.FP16X3_MIN_K, ops.FP16X3_MIN_N, ops.FP16X3_WGRAD_MIN_ROWS = 32, 1, 1
         yield ops
-    finally:
-        ops.FP16X3_MIN_K, ops.FP16X3_MIN_N, ops.FP16X3_WGRAD_MIN_ROWS = was[1:]
-        ops.set_gemm_precision(was[0])
 
 
 # ------------------------------------------------------------------ the column image
@@ -134,31 +118,14 @@ def test_column_image_declines_what_it_cannot_address(ops):
 
 
 # ------------------------------------------------------------------ GEMM against float64
-def as_cols_image(ops, op):
-    """replace the fp32 operand `op` (test_hip_gemm_routes.Op over a NaN-poisoned buffer) by its column image: a copy
-    of the buffer -- poison included -- whose rows' columns f2g_split_f16x2_cols rewrote"""
-    o = op.o
-    op.img = op.flat.clone()
-    op.rs = torch.full((o.cols + 8,), NAN, device=DEV)
-    op.work = torch.empty(o.cols, device=DEV, dtype=torch.int32)
-    ops.call("f2g_split_f16x2_cols", op.img.data_ptr() + 4 * op.off, op.rs.data_ptr() + 16, op.work.data_ptr(),
-             op.flat.data_ptr() + 4 * op.off, o.seq_stride, o.rows, o.cols)
-    o.base, o.split, o.rscale = op.img.data_ptr() + 4 * op.off, 6, op.rs.data_ptr() + 16
-    return op
-
-
 def operands(ops, R, M, N, seed, scale_a=1.0):
     A = as_cols_image(ops, plain(ops, rnd(R, M, seed=seed) * scale_a))
     B = as_cols_image(ops, plain(ops, rnd(R, N, seed=seed + 50, scale=R ** -0.5)))
     return A, B
 
 
-def f16_ok(ops, d):
-    return ops.L.lib.f2g_gemm_f16_ok(C.byref(d))
-
-
 def is_h3w(ops):
-    return last_kernel(ops) == NAME and ops.L.lib.f2g_gemm_last_path() == 6
+    return ran(ops, NAME)
 
 
 @pytest.mark.parametrize("N", [32, 128, 160])
@@ -211,13 +178,14 @@ def test_wgrad_inf_stays_in_its_output_row(ops):
 
 def test_wgrad_three_launches_give_the_same_bits(ops):
     A, B = operands(ops, 777, 132, 160, seed=14)
-    bits = []
-    for _ in range(3):
+
+    def go():
         out = Out(132, 160)
         launch(ops, A, B, out, form=2, precision=4)
         assert is_h3w(ops)
-        bits.append(out.flat.view(torch.int32).clone())
-    assert torch.equal(bits[0], bits[1]) and torch.equal(bits[0], bits[2])
+        return out.flat.view(torch.int32).clone()
+
+    same_bits(go)
 
 
 DECLINED = ["windowed", "split5", "no_scales", "bf16_out", "m_mod_4", "other_precisions", "form0", "split_k_plain"]
@@ -250,11 +218,7 @@ def test_descriptors_the_kernel_declines(ops, what):
     precisions = (0, 1, 2, 3) if what == "other_precisions" else (4,)
     for prec in precisions:
         d.precision = prec
-        assert f16_ok(ops, d) == 0
-        assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
-        torch.cuda.synchronize()
-        assert last_kernel(ops) == ""
-    assert bool((out.flat[~torch.isnan(out.flat)] == SENT).all())
+        assert_declined(ops, d, out)
     if what == "other_precisions":      # (the descriptor itself is one the kernel runs)
         d.precision = 4
         assert f16_ok(ops, d) == 1
@@ -265,11 +229,7 @@ def test_fp32_operands_would_qualify_but_are_not_launched(ops):
     A, B = plain(ops, rnd(R, M, seed=1)), plain(ops, rnd(R, N, seed=2))
     out = Out(M, N)
     d = make_desc(ops, A, B, out, form=2, precision=4)
-    assert f16_ok(ops, d) == 2
-    assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
-    torch.cuda.synchronize()
-    assert last_kernel(ops) == ""
-    assert bool((out.flat[~torch.isnan(out.flat)] == SENT).all())
+    assert_declined(ops, d, out, ok=2)
 
 
 # ------------------------------------------------------------------ ops.wgrad
@@ -306,42 +266,7 @@ def test_stage1_against_oracle_with_fp16x3_weight_gradients(fp16x3):
     """the construction of test_hip_gemm_f16.py::test_stage1_and_infer_against_oracle (the TINY config, B = 3, odd T)
     with the weight-gradient threshold lowered as well, at that test's tolerances: forward, data gradient and weight
     gradient of the pointwise convolutions all run in the fp16x3 arithmetic"""
-    ops = fp16x3
-    import flow2gan_amd as f2g
-    import flow2gan_oracle as O
-    torch.manual_seed(3)
-    mo = O.MelAudioGenerator(**TINY).train()
-    mh = f2g.MelAudioGenerator(**TINY)
-    mh.load_state_dict(mo.state_dict())
-    mh = mh.to(DEV).train()
-    mo.branch_dropout = mh.branch_dropout = 0.0
-    gen = torch.Generator().manual_seed(4)
-    B, Tn = 3, 5120
-    audio = 0.1 * torch.randn(B, Tn, generator=gen)
-    lens = torch.tensor([5120, 3000, 4097])
-    mel = O.LogMelSpectrogram()(audio)
-    noise = 0.1 * torch.randn(B, Tn, generator=gen)
-    t = torch.tensor([[0.1], [0.5], [0.9]])
-    st = random.getstate()
-    random.seed(5)
-    lo = mo(mel, audio, lens, noise=noise, t=t)
-    lo.backward()
-    random.setstate(st)
-    random.seed(5)
-    f0 = ops.FP16X3_LAUNCHES
-    lh = mh(mel.to(DEV), audio.to(DEV), lens, noise=noise.to(DEV), t=t.to(DEV))
-    f1, w1 = ops.FP16X3_LAUNCHES, ops.FP16X3_WGRAD_LAUNCHES
-    lh.backward()
-    f2, w2 = ops.FP16X3_LAUNCHES, ops.FP16X3_WGRAD_LAUNCHES
-    random.setstate(st)
-    print(f"fp16x3 launches: forward {f1 - f0}, data gradients {f2 - f1}, weight gradients {w2 - w1}; "
-          f"loss {float(lh):.7f} oracle {float(lo):.7f}")
-    assert f1 > f0 and f2 > f1, "forward or data gradients never reached the fp16x3 kernel"
-    assert w2 > w1, "the backward pass never reached the fp16x3 weight-gradient kernel"
-    assert abs(float(lh) - float(lo)) < 2e-5 * abs(float(lo))
-    po = dict(mo.named_parameters())
-    errs = sorted(((float((p.grad.cpu() - po[n].grad).abs().max()) / (float(po[n].grad.abs().max()) + 1e-12), n)
-                   for n, p in mh.named_parameters()), reverse=True)
-    print("worst gradients:", errs[:3])
-    assert all(p.grad is not None for p in mh.parameters())
-    assert errs[0][0] < 2e-3, errs[:8]
+    r = stage1_against_oracle(fp16x3, ("FP16X3_LAUNCHES", "FP16X3_WGRAD_LAUNCHES"))
+    print(f"fp16x3 launches: forward {r.fwd[0]}, data gradients {r.bwd[0]}, weight gradients {r.bwd[1]}")
+    assert r.fwd[0] > 0 and r.bwd[0] > 0, "forward or data gradients never reached the fp16x3 kernel"
+    assert r.bwd[1] > 0, "the backward pass never reached the fp16x3 weight-gradient kernel"

@@ -11,52 +11,30 @@ output held| + |bias|) + 2^-28 * (bmax sum_r |a| + amax sum_r |b|), TOL = tests/
 maxima over the whole operands (finite values): a running maximum never exceeds them, so the tolerance does not depend
 on the grid."""
 import ctypes as C
-import random
 
 import pytest
 import torch
 
 import fp16x3_runk_emul as emul
-import test_fp16x3_wgradn_host as host
-from test_hip_gemm_f16 import TINY, TOL, mode_name
-from test_hip_gemm_routes import DEV, SENT, Out, last_kernel, make_desc, plain, rnd
+from fp16x3_emul import FLOOR
+from fp16x3_gpu import TOL, assert_declined, f16_ok, fp16x3_mode, ops, ran, same_bits, stage1_against_oracle
+from test_hip_gemm_routes import DEV, Out, last_kernel, make_desc, plain, rnd
 
 pytestmark = pytest.mark.gpu
 
 NAME = "h3wn"
-EINVAL = -1
-FLOOR = 2.0 ** -28
-assert TOL == host.TOL
-
-
-@pytest.fixture(scope="module")
-def ops():
-    if not torch.cuda.is_available():
-        pytest.skip("needs an MI355X")
-    from flow2gan_amd import ops as o
-    return o
 
 
 @pytest.fixture
 def fp16x3(ops):
     """the fp16x3 mode; thresholds and the mode are restored afterwards (the tests assign the thresholds themselves)"""
     names = ("FP16X3_WGRADN_MIN_ROWS", "FP16X3_WGRAD_MIN_ROWS", "FP16X3_MIN_K", "FP16X3_MIN_N")
-    was, vals = mode_name(ops), [getattr(ops, n) for n in names]
-    ops.set_gemm_precision("fp16x3")
-    try:
+    with fp16x3_mode(ops, *names):
         yield ops
-    finally:
-        for n, v in zip(names, vals):
-            setattr(ops, n, v)
-        ops.set_gemm_precision(was)
-
-
-def f16_ok(ops, d):
-    return ops.L.lib.f2g_gemm_f16_ok(C.byref(d))
 
 
 def is_h3wn(ops):
-    return last_kernel(ops) == NAME and ops.L.lib.f2g_gemm_last_path() == 6
+    return ran(ops, NAME)
 
 
 # ------------------------------------------------------------------ operands, launch, reference
@@ -176,12 +154,13 @@ def test_atomic_split_k_with_a_ragged_last_slab(ops, pattern):
 def test_three_launches_give_the_same_bits(ops):
     R, M, N = emul.MAGNITUDE_SHAPES[1]
     A, B = operands(ops, *emul.inputs("rising", R, M, N))
-    bits = []
-    for _ in range(3):
+
+    def go():
         out = Out(M, N)
         launch10(ops, A, B, out)
-        bits.append(out.flat.view(torch.int32).clone())
-    assert torch.equal(bits[0], bits[1]) and torch.equal(bits[0], bits[2])
+        return out.flat.view(torch.int32).clone()
+
+    same_bits(go)
 
 
 @pytest.mark.parametrize("side", ["A", "B"])
@@ -214,7 +193,7 @@ def test_a_non_finite_input_stays_in_its_output_line(ops, side, value):
 
 
 # ------------------------------------------------------------------ refusals
-@pytest.mark.parametrize("what", list(host.refusals(0)))
+@pytest.mark.parametrize("what", list(emul.refusals(0)))
 def test_descriptors_the_kernel_declines(ops, what):
     """f2g_gemm_f16_ok == 0 and F2G_EINVAL from f2g_gemm -- never another kernel; the output stays untouched.
     (extent: the descriptor alone, rows that no memory stands behind -- nothing is launched)"""
@@ -224,12 +203,8 @@ def test_descriptors_the_kernel_declines(ops, what):
     out = Out(M, N)
     spare = rnd(max(M, N) * 256, seed=1)
     assert f16_ok(ops, desc10(ops, A, B, out)) == 1          # (the one change below is what it declines)
-    d = host.apply(desc10(ops, A, B, out), host.refusals(spare.data_ptr())[what])
-    assert f16_ok(ops, d) == 0
-    assert ops.L.lib.f2g_gemm(C.byref(d), ops.L.stream_ptr()) == EINVAL
-    torch.cuda.synchronize()
-    assert last_kernel(ops) == ""
-    assert bool((out.flat[~torch.isnan(out.flat)] == SENT).all())
+    d = emul.apply(desc10(ops, A, B, out), emul.refusals(spare.data_ptr())[what])
+    assert_declined(ops, d, out)
 
 
 # ------------------------------------------------------------------ ops.wgrad
@@ -325,42 +300,9 @@ def test_stage1_against_oracle_with_in_kernel_scaled_weight_gradients(fp16x3):
     ops = fp16x3
     ops.FP16X3_MIN_K, ops.FP16X3_MIN_N = 32, 1
     ops.FP16X3_WGRAD_MIN_ROWS, ops.FP16X3_WGRADN_MIN_ROWS = ops.FP16X3_WGRAD_OFF, 1
-    import flow2gan_amd as f2g
-    import flow2gan_oracle as O
-    torch.manual_seed(3)
-    mo = O.MelAudioGenerator(**TINY).train()
-    mh = f2g.MelAudioGenerator(**TINY)
-    mh.load_state_dict(mo.state_dict())
-    mh = mh.to(DEV).train()
-    mo.branch_dropout = mh.branch_dropout = 0.0
-    gen = torch.Generator().manual_seed(4)
-    B, Tn = 3, 5120
-    audio = 0.1 * torch.randn(B, Tn, generator=gen)
-    lens = torch.tensor([5120, 3000, 4097])
-    mel = O.LogMelSpectrogram()(audio)
-    noise = 0.1 * torch.randn(B, Tn, generator=gen)
-    t = torch.tensor([[0.1], [0.5], [0.9]])
-    st = random.getstate()
-    random.seed(5)
-    lo = mo(mel, audio, lens, noise=noise, t=t)
-    lo.backward()
-    random.setstate(st)
-    random.seed(5)
-    f0 = ops.FP16X3_LAUNCHES
-    lh = mh(mel.to(DEV), audio.to(DEV), lens, noise=noise.to(DEV), t=t.to(DEV))
-    f1, w1, i1 = ops.FP16X3_LAUNCHES, ops.FP16X3_WGRADN_LAUNCHES, ops.FP16X3_WGRAD_LAUNCHES
-    lh.backward()
-    f2, w2, i2 = ops.FP16X3_LAUNCHES, ops.FP16X3_WGRADN_LAUNCHES, ops.FP16X3_WGRAD_LAUNCHES
-    random.setstate(st)
-    print(f"fp16x3 launches: forward {f1 - f0}, data gradients {f2 - f1}, in-kernel-scaled weight gradients {w2 - w1}; "
-          f"loss {float(lh):.7f} oracle {float(lo):.7f}")
-    assert f1 > f0 and f2 > f1, "forward or data gradients never reached the fp16x3 kernel"
-    assert w2 > w1, "the backward pass never reached gemm_h3wn_kernel"
-    assert i2 == i1, "the image route took a weight gradient"
-    assert abs(float(lh) - float(lo)) < 2e-5 * abs(float(lo))
-    po = dict(mo.named_parameters())
-    errs = sorted(((float((p.grad.cpu() - po[n].grad).abs().max()) / (float(po[n].grad.abs().max()) + 1e-12), n)
-                   for n, p in mh.named_parameters()), reverse=True)
-    print("worst gradients:", errs[:3])
-    assert all(p.grad is not None for p in mh.parameters())
-    assert errs[0][0] < 2e-3, errs[:8]
+    r = stage1_against_oracle(ops, ("FP16X3_LAUNCHES", "FP16X3_WGRADN_LAUNCHES", "FP16X3_WGRAD_LAUNCHES"))
+    print(f"fp16x3 launches: forward {r.fwd[0]}, data gradients {r.bwd[0]}, in-kernel-scaled weight gradients "
+          f"{r.bwd[1]}")
+    assert r.fwd[0] > 0 and r.bwd[0] > 0, "forward or data gradients never reached the fp16x3 kernel"
+    assert r.bwd[1] > 0, "the backward pass never reached gemm_h3wn_kernel"
+    assert r.bwd[2] == 0, "the image route took a weight gradient"
